@@ -4,7 +4,7 @@
 Headline benchmark: frame-state log-likelihoods/s + utterances/s Viterbi decode
 (BASELINE.json) of the GMM-HMM hot path on MI355X, through the C ABI.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 N > 1: either launched by `python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N` (RANK /
 LOCAL_RANK / WORLD_SIZE in the environment), or started directly -- then this process only spawns the N rank
@@ -23,6 +23,12 @@ utterance through the 10 stacked word models (A6) + arg-min word per utterance
 collective -- decode shards by utterance).  Features are resident in HBM before
 the timed region.  Arithmetic: fp64 (the reference's), which is what keeps the
 Viterbi paths bit-identical; --dtype f32 runs the fp32 likelihood kernel.
+
+A plain run sets up, warms up, times the --steps steps, writes their outputs when
+--dump-outputs DIR is given (see dump_outputs) and prints the result line.  Everything
+else runs only with --full, which adds to the line the objects "cpu_baseline", "em",
+"configs" and "pcie_inclusive" described below (the --no-* switches still drop
+single legs of a --full run).
 
 Prints ONE JSON line on rank 0 (contract in the task statement) with extra
 objects: "roofline" for the dominant kernel (the likelihood kernel; HIP-event
@@ -1214,6 +1220,27 @@ def pcie_inclusive(dev, wl, npdt, steps=6):
             "note": "upload + likelihoods + Viterbi per step from pageable host memory; one context / two contexts on two host threads"}
 
 
+def dump_outputs(out_dir, lane, max_rows=1 << 18, loglik_rows=16384):
+    """--dump-outputs: what the timed step computed in its last pass over the batch, as DIR/<name>.npy -- the word
+    models' end costs [U, W] and the decoded word per utterance (what a caller of the recogniser gets back), plus a fixed,
+    seeded sample of frames of the resident likelihood matrix.  The end costs and decoded words are float64 and the
+    likelihoods are in the batch's dtype.  Batches of more than `max_rows` utterances are sampled too (seeded), so the
+    files stay far below 64 MB."""
+    from sr.recognition import _hip
+    os.makedirs(out_dir, exist_ok=True)
+    b, rng = lane.batch, np.random.default_rng(0)
+    utts = np.arange(b.U) if b.U <= max_rows else np.sort(rng.choice(b.U, size=max_rows, replace=False))
+    ll = np.empty((b.N, b.S), dtype=b.np_dtype)
+    _hip._check(lane.ctx.lib, lane.ctx.lib.gh_loglik_fetch(lane.ctx.h, b.h, ll.ctypes.data_as(C.c_void_p)))
+    frames = np.sort(rng.choice(b.N, size=min(loglik_rows, b.N), replace=False))
+    arrays = {"end_cost": lane.end_cost[utts].astype(np.float64), "decoded_word": lane.decoded[utts].astype(np.float64),
+              "loglik_sample": ll[frames], "loglik_sample_frames": frames.astype(np.float64)}
+    if len(utts) < b.U:
+        arrays["utterances"] = utts.astype(np.float64)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -1253,7 +1280,17 @@ def main():
                                                          "GPU, 10 000 per GPU in an N-rank run)")
     ap.add_argument("--c5-utts", type=int, default=125000, help="utterances of the C5 legs (1 M / 8 GPUs)")
     ap.add_argument("--c3-utts", type=int, default=2000, help="7-word utterances of the training-step leg (C3_word_strings)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beside the headline: the CPU baselines, the EM leg, the other configs and the "
+                         "PCIe-inclusive step (each still subject to its --no-* switch); a plain run only times the headline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what rank 0's last step computed as DIR/<name>.npy (float64; "
+                         "the likelihood sample in the --dtype of the run)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if not args.full:
+        args.no_cpu_baseline = args.no_em = args.no_extra_configs = True
 
     if args.comm is None:
         args.comm = "native" if args.backend == "nccl" else "torch"
@@ -1324,9 +1361,11 @@ def main():
             r = self.lat.viterbi(self.batch, want_path=False)
             ec = r["end_cost_flat"].reshape(self.batch.U, W)
             self.decoded = np.argmin(ec, axis=1)
+            self.end_cost = ec
+            chain["done"] = self                  # the lane whose step finished last (for --dump-outputs)
 
     import threading
-    chain_lock, chain = threading.Lock(), {"last": None}
+    chain_lock, chain = threading.Lock(), {"last": None, "done": None}
     lanes = [Lane() for _ in range(max(1, args.inflight))]
     N_frames, U = lanes[0].batch.N, lanes[0].batch.U
 
@@ -1385,6 +1424,8 @@ def main():
     tot = group.sum([float(N_frames), float(U)])         # all ranks' units
     all_frames, all_utts = float(tot[0]), float(tot[1])
     accuracy = float(np.mean(decoded == wl["words"]))
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, chain["done"])
 
     if rank == 0:
         ll_avg_s = float(np.mean(ll_times)) * 1e-3

@@ -147,7 +147,7 @@ def _run_bench(extra, extras=False):
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     cmd = [sys.executable, os.path.join(root, "bench.py"), "--steps", "3", "--warmup", "1", "--ramp-seconds", "0.1",
-           "--utts", "400", "--em-utts", "300", "--em-iters", "2", "--no-cpu-baseline"] + extra
+           "--utts", "400", "--em-utts", "300", "--em-iters", "2", "--no-cpu-baseline", "--full"] + extra
     cmd += ["--c5-utts", "1000", "--c4-utts", "60", "--c4-em-utts", "40", "--c3-utts", "50"] if extras else ["--no-extra-configs"]
     p = subprocess.run(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=900)
     assert p.returncode == 0, p.stderr[-2000:]
@@ -215,7 +215,8 @@ def test_bench_under_the_drivers_launcher():
     two = _n_gpus() >= 2
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
-           "--ramp-seconds", "0.1", "--utts", "400", "--em-utts", "300", "--em-iters", "2", "--no-cpu-baseline", "--no-extra-configs"]
+           "--ramp-seconds", "0.1", "--utts", "400", "--em-utts", "300", "--em-iters", "2", "--no-cpu-baseline", "--no-extra-configs",
+           "--full"]
     if not two:
         cmd.append("--same-gpu")
     p = subprocess.run(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=900)
