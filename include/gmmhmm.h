@@ -577,6 +577,29 @@ int gh_fit_em(gh_ctx* ctx, gh_fit* fit, gh_comm* comm, int k, double* mean_io, d
               double* mu_old_io, double* sigma_old_io, double* w_old_io, const double* n_frames /*[S]*/, int max_iteration,
               int check_every, int32_t* out_converged_at);
 
+/* ------------------------------------------------------- lexical-tree spell check
+ * text_viterbi (sr/langmodel/spellchecker.py): the string-edit Viterbi of a string against a flattened prefix tree with
+ * a word-loop back edge.  Rows in preorder: 0 the root, 1..R-2 the tree, R-1 the extra space row; parent[0] =
+ * parent[R-1] = -1 and 0 <= parent[r] < r otherwise (anything else -- out of range, a cycle -- is GH_ERR_INVALID);
+ * val_code[R] in [0, n_val) names each row's value; word_ends = [R-1, the rows of property 2 ascending] (n_word_ends >= 2).
+ * The tree stays resident on the context's GPU until gh_lextree_destroy. */
+typedef struct gh_lextree gh_lextree;
+int gh_lextree_create(gh_ctx* ctx, int R, const int32_t* parent /*[R]*/, const int32_t* val_code /*[R]*/, int n_val,
+                      int n_word_ends, const int32_t* word_ends /*[n_word_ends]*/, gh_lextree** out);
+void gh_lextree_destroy(gh_lextree* tree);
+/* n_strings strings x' = '*' + x, as codes [offsets[s], offsets[s+1]) (>= 2 each) in [0, n_x_codes); dist_table
+ * [n_x_codes, n_val] holds dist(x' character, node value) as non-negative integers (sr/langmodel/spellchecker.py,
+ * text_viterbi's dist_fun).  Out: best_cost[s] (the reference's cost, exact), path_len[s] and, back to back in string
+ * order, the preorder rows whose values the reference's back-trace appends (first the word end it starts from; the
+ * matched string is their values joined and reversed).  path_cap bounds the total; 1 + (C-2)(depth+1) per string always
+ * suffices.  Costs are kept in uint16 (LDS) when (max dist + 1)(depth + C + 1) < 65535, else uint32 (global memory;
+ * GMMHMM_LEXTREE_FORM=32 forces it); beyond 32 bits GH_ERR_UNSUPPORTED.  Decisions are chunked by the scratch budget
+ * (gh_ctx_last_chunks). */
+int gh_text_viterbi(gh_ctx* ctx, const gh_lextree* tree, int64_t n_strings, const int64_t* offsets /*[n_strings+1]*/,
+                    const int32_t* codes, int n_x_codes, const int64_t* dist_table /*[n_x_codes, n_val]*/,
+                    int64_t* best_cost /*[n_strings]*/, int32_t* path_len /*[n_strings]*/, int32_t* path_rows /*[path_cap]*/,
+                    int64_t path_cap);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,8 +1,9 @@
 # -*- coding: utf-8 -*-
 """MI355X-native drop-in for the `sr` package's recognition core.
 
-Only `sr.recognition` (the GMM-HMM hot path) is provided; the reference's wav /
-MFCC / audio-capture facade (sr/core.py) is out of scope.  The names the
+Provided: `sr.recognition` (the GMM-HMM hot path) and `sr.langmodel` (lexical-tree
+spell check; imported on its own, `import sr.langmodel`, as in the reference); the
+reference's wav / audio-capture facade (sr/core.py) is out of scope.  The names the
 reference re-exports from `sr` (sr/__init__.py:2) are re-exported here too.
 """
 from .core import delta_feature  # noqa: F401  (reference sr/__init__.py:1; the wav / file drivers are out of scope)

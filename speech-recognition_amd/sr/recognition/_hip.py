@@ -143,6 +143,10 @@ SIGNATURES = {
     "gh_stats_allreduce": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]),
     "gh_comm_allreduce_host": (C.c_int, [C.c_void_p, C.c_void_p, _c_f64p, C.c_int64, C.c_int]),
     "gh_comm_barrier": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "gh_lextree_create": (C.c_int, [C.c_void_p, C.c_int, _c_i32p, _c_i32p, C.c_int, C.c_int, _c_i32p, C.POINTER(C.c_void_p)]),
+    "gh_lextree_destroy": (None, [C.c_void_p]),
+    "gh_text_viterbi": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, _c_i64p, _c_i32p, C.c_int, _c_i64p, _c_i64p, _c_i32p,
+                                  _c_i32p, C.c_int64]),
 }
 
 
@@ -1262,3 +1266,50 @@ def distance_matrix(ctx, x, y, var=None):
                                                _ptr(v, _c_f64p), 0 if v is None else v.shape[0],
                                                _ptr(out, _c_f64p)))
     return out
+
+
+class LexTree:
+    """A flattened lexical tree resident on one GPU (gh_lextree): preorder rows, the space row last, `parent` (-1 for
+    the root and the space row), value codes and the word ends ([space row, property-2 rows ascending])."""
+
+    def __init__(self, ctx, parent, val_code, n_val, word_ends, depth):
+        self.ctx = ctx
+        self.lib = ctx.lib
+        self.depth = int(depth)
+        self.n_val = int(n_val)
+        parent = np.ascontiguousarray(parent, dtype=np.int32)
+        val_code = np.ascontiguousarray(val_code, dtype=np.int32)
+        word_ends = np.ascontiguousarray(word_ends, dtype=np.int32)
+        h = C.c_void_p()
+        _check(self.lib, self.lib.gh_lextree_create(ctx.h, len(parent), _ptr(parent, _c_i32p), _ptr(val_code, _c_i32p),
+                                                    self.n_val, len(word_ends), _ptr(word_ends, _c_i32p), C.byref(h)))
+        self.h = h
+
+    def viterbi(self, offsets, codes, dist_table):
+        """gh_text_viterbi over strings given as codes of '*' + x ([offsets[s], offsets[s+1])) against `dist_table`
+        [n_x_codes, n_val] (non-negative integers) -> (best costs int64 [n], list of preorder row arrays)."""
+        offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+        codes = np.ascontiguousarray(codes, dtype=np.int32)
+        table = np.ascontiguousarray(dist_table, dtype=np.int64)
+        n = len(offsets) - 1
+        cols = np.diff(offsets)
+        cap = int(np.sum(1 + (cols - 2) * (self.depth + 1))) if n else 0
+        best = np.empty(n, dtype=np.int64)
+        plen = np.empty(n, dtype=np.int32)
+        rows = np.empty(max(cap, 1), dtype=np.int32)
+        _check(self.lib, self.lib.gh_text_viterbi(self.ctx.h, self.h, n, _ptr(offsets, _c_i64p), _ptr(codes, _c_i32p),
+                                                  table.shape[0], _ptr(table, _c_i64p), _ptr(best, _c_i64p),
+                                                  _ptr(plen, _c_i32p), _ptr(rows, _c_i32p), cap))
+        ends = np.cumsum(plen)
+        return best, [rows[e - l:e] for e, l in zip(ends, plen)]
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.lib.gh_lextree_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass

@@ -613,6 +613,149 @@ def g15(R):
 
 ALL["G15"] = g15
 
+
+# ----------------------------------------------------------------- sr.langmodel (lexical-tree spell check)
+DICT1 = os.path.join(REF, "tests", "test_data", "dict1.txt")
+
+
+def load_langmodel():
+    """The reference's sr.langmodel (pure Python; its text_viterbi uses np.int, aliased by load_reference)."""
+    return importlib.import_module("sr.langmodel")
+
+
+def dict1_words():
+    """tests/test_data/dict1.txt: a one-column table with the header `words`, one word per line."""
+    with open(DICT1) as f:
+        lines = f.read().split("\n")
+    assert lines[0] == "words"
+    return [w for w in lines[1:] if w]
+
+
+def small_word_lists():
+    """~20 seeded small vocabularies: short words over small alphabets, duplicates and one-letter words included."""
+    rng = np.random.default_rng(181)
+    lists = []
+    for i in range(20):
+        alpha = "abcde" if i % 3 else "abcdefghij"
+        n = int(rng.integers(2, 25))
+        words = ["".join(rng.choice(list(alpha), size=int(rng.integers(1, 7)))) for _ in range(n)]
+        if i % 4 == 0:
+            words += [words[0], words[-1]]            # duplicates
+        if i % 5 == 1:
+            words += list(rng.choice(list(alpha), size=3))  # one-letter words
+        lists.append([str(w) for w in words])
+    return lists
+
+
+def flatten_reference_tree(L, tree):
+    """Preorder rows of a reference tree (its own get_nodes) with the parent of every row (the reference's
+    `transitions`, spellchecker.py, computed through an identity map instead of nodes.index: same rows, O(R))."""
+    nodes = []
+    L.get_nodes(nodes, tree)
+    row = {id(n): i for i, n in enumerate(nodes)}
+    parent = np.full(len(nodes) + 1, -1, dtype=np.int32)
+    for i, n in enumerate(nodes):
+        for ch in n.children:
+            parent[row[id(ch)]] = i
+    prop = np.array([n.property for n in nodes], dtype=np.int8)
+    word_ends = np.concatenate([[len(nodes)], np.nonzero(prop == 2)[0]]).astype(np.int32)
+    return dict(vals=np.array([n.val for n in nodes]), prop=prop, parent=parent, word_ends=word_ends,
+                max_level=np.array(tree.get_max_level()))
+
+
+def g18(R):
+    """sr.langmodel.lextree_from_words on dict1 and on ~20 seeded small word lists: the tree node for node (preorder
+    values, properties, parents, word ends) and the caller's list after the call (padded in place, shortened)."""
+    L = load_langmodel()
+    lists = [dict1_words()] + small_word_lists()
+    out = dict(n=np.array(len(lists)))
+    for i, words in enumerate(lists):
+        given = list(words)
+        tree = L.lextree_from_words(words)
+        f = flatten_reference_tree(L, tree)
+        out.update({"words%d" % i: np.array(given), "after%d" % i: np.array(words)})
+        out.update({k + "%d" % i: v for k, v in f.items()})
+    save("G18_lextree", **out)
+
+
+def dist_vowel3(a, b):
+    """The custom integer distance of G19 (and of its tests): 0 equal, 1 two vowels, 3 otherwise."""
+    if a == b:
+        return 0
+    return 1 if (a in "aeiou" and b in "aeiou") else 3
+
+
+def typo_text(rng, words, n_chars):
+    """Dictionary words with random typos (substitution, deletion, insertion, transposition), joined by spaces."""
+    letters = "abcdefghijklmnopqrstuvwxyz"
+    out, n = [], 0
+    while n < n_chars:
+        w = list(words[int(rng.integers(len(words)))])
+        for _ in range(int(rng.integers(0, 3))):
+            k = int(rng.integers(len(w)))
+            op = int(rng.integers(4))
+            if op == 0:
+                w[k] = letters[int(rng.integers(26))]
+            elif op == 1 and len(w) > 1:
+                del w[k]
+            elif op == 2:
+                w.insert(k, letters[int(rng.integers(26))])
+            elif op == 3 and k + 1 < len(w):
+                w[k], w[k + 1] = w[k + 1], w[k]
+        out.append("".join(w))
+        n += len(out[-1]) + 1
+    return " ".join(out)
+
+
+_G19_TREES = {}
+
+
+def _g19_case(args):
+    tree_key, x, dist = args
+    L = load_langmodel()
+    tree = _G19_TREES[tree_key]
+    with quiet():
+        if dist == "vowel3":
+            cost, s = L.text_viterbi(x, tree, dist_fun=dist_vowel3)
+        else:
+            cost, s = L.text_viterbi(x, tree)
+    return float(cost), s
+
+
+def g19(R):
+    """The reference's text_viterbi: small trees x ~100 strings (lengths 1 and 2, characters absent from the tree, the
+    custom integer distance dist_vowel3), dict1 x 20 short strings, and dict1 x one seeded ~2 000-character typo text
+    (the long case costs minutes of reference CPU: the cases run in a process pool)."""
+    import multiprocessing as mp
+    L = load_langmodel()
+    rng = np.random.default_rng(191)
+    lists = small_word_lists()
+    cases = []   # (tree key, x, dist)
+    for t in range(5):
+        _G19_TREES["s%d" % t] = L.lextree_from_words(list(lists[t]))
+        for j in range(20):
+            n = 1 + j % 2 if j < 4 else int(rng.integers(1, 10))
+            alpha = "abcdefghij" + ("xyz *" if j % 3 == 0 else "")      # x, y, z: in no small tree; ' ' and '*' too
+            x = "".join(rng.choice(list(alpha), size=n))
+            cases.append(("s%d" % t, str(x), "vowel3" if j % 4 == 3 else "mismatch"))
+    words = dict1_words()
+    _G19_TREES["dict1"] = L.lextree_from_words(list(words))
+    for j in range(20):
+        x = typo_text(rng, words, int(rng.integers(1, 12)))[: int(rng.integers(1, 12))].strip() or "a"
+        cases.append(("dict1", x, "mismatch"))
+    cases.append(("dict1", typo_text(np.random.default_rng(1919), words, 2000), "mismatch"))
+    order = sorted(range(len(cases)), key=lambda i: -len(cases[i][1]) * (30000 if cases[i][0] == "dict1" else 1))
+    with mp.get_context("fork").Pool(int(os.environ.get("GOLDEN_JOBS", "8"))) as pool:
+        res = dict(zip(order, pool.map(_g19_case, [cases[i] for i in order], chunksize=1)))
+    out = dict(n_small_lists=np.array(5), tree=np.array([c[0] for c in cases]), x=np.array([c[1] for c in cases]),
+               dist=np.array([c[2] for c in cases]), cost=np.array([res[i][0] for i in range(len(cases))]),
+               matched=np.array([res[i][1] for i in range(len(cases))]))
+    save("G19_text_viterbi", **out)
+
+
+ALL["G18"] = g18
+ALL["G19"] = g19
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--only", default="")
