@@ -76,8 +76,10 @@ int gh_ctx_last_chunks(const gh_ctx* ctx);
  *          them per component (round 4; a no-op launch for ordinary models).
  *   bit 1  (off by default; GMMHMM_LSE=f32exp sets it at creation) the fp64 likelihood kernel takes the exponentials of its
  *          log-sum-exp in FP32: maximum, differences and the final max + log(sum) stay fp64, the terms 2^(a - max) <= 1
- *          and their sum are fp32.  |delta nll| <= ~2.4e-7 absolute; bench.py reports the kernel both ways with the
- *          measured difference and path mismatch rates.  Mixtures of >= 4 components, fp64 batches. */
+ *          and their sum are fp32.  |delta nll| <= B(M_pad) = 4.4e-7, 5.2e-7, 7.7e-7, 9.8e-7, 1.2e-6, 1.4e-6 absolute for
+ *          M_pad = 4, 8, 16, 32, 48, 64 padded components, plus 2^-50 |nll| (derived in DESIGN.md section 4.1); bench.py
+ *          reports the kernel both ways with the measured difference and path mismatch rates.  Mixtures of >= 4
+ *          components, fp64 batches. */
 int gh_ctx_set_compat(gh_ctx* ctx, int flags);
 /* raw hipStream_t of the context (for torch interop) */
 void* gh_ctx_stream(gh_ctx* ctx);

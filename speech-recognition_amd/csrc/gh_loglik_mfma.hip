@@ -180,9 +180,14 @@ __device__ __forceinline__ void tile_lse(const V& a, int width, T& mx, T& sm, co
 // ---- opt-in epilogue with the exponentials in FP32 (gh_ctx_set_compat bit 1 / GMMHMM_LSE=f32exp; fp64 batches only).
 // The maximum, `a - max` and the final `max + log(sum)` stay fp64; the terms 2^((a - max)/128) <= 1 go through
 // v_cvt_f32_f64 + v_exp_f32, their sum and its v_log_f32 stay fp32: 2 instructions on the shared fp64 pipe per term
-// instead of ~10.  A term carries v_exp_f32's relative error (~1.2e-7), so the log-sum-exp -- and with it the
-// negative log-likelihood -- moves by at most ~2.4e-7 ABSOLUTE (on costs of ~60: 4e-9 relative, north star 1e-5).
-// Off by default: bench.py reports the kernel both ways together with max |delta nll| and the path mismatch rates.
+// instead of ~10.  Bound (derived in DESIGN section 4.1; u = 2^-24; v_exp_f32 taken as 1 ulp = 2^-23 relative, v_log_f32
+// as 1 ulp of its result log2(sum) <= log2(M_pad); d = 2, 3, 4 fp32 sum levels for M_pad = 4, 8, >= 16; T = M_pad/16
+// tiles per state from 32 on, else 1):
+//     |delta nll| <= B(M_pad) = (d + T - 1 + W((M_pad - 1)/e)) u + T 2^-23 + ln2 2^(floor(log2 log2 M_pad) - 23) + 1e-12
+// ABSOLUTE, plus fp64 rounding (2^-50 |nll|): 4.4e-7 (M_pad 4), 5.2e-7 (8), 7.7e-7 (16), 9.8e-7 (32), 1.2e-6 (48),
+// 1.4e-6 (64).  tests/test_gpu_lse_f32.py asserts it.  (A mantissa / exponent split before v_log_f32 keeps the last term
+// at ln2 2^-23 for every M_pad: measured max |delta nll| 1.9e-7 instead of 4.8e-7 at M_pad 32-64, but 0.7 % slower on
+// configs[1]; not kept.)  Off by default: bench.py reports the kernel both ways with max |delta nll| and the decode changes.
 __device__ __forceinline__ float exp2s_fe(double y) { return __builtin_amdgcn_exp2f((float)y * 0.0078125f); }
 template <int W> __device__ __forceinline__ float pair_sum_f(float v) { float a, b; pair_of<W>(v, a, b); return a + b; }
 template <typename V>

@@ -237,7 +237,8 @@ class Context:
         """underflow=True (a context's default): likelihoods of states whose every weighted density underflows fp64 come
         back as +inf, like the reference's linear-domain GMM.evaluate (hmm_state.py:114-120); False: log domain throughout,
         finite costs.  lse_f32=True: the fp64 likelihood kernel takes the exponentials of its log-sum-exp in fp32
-        (|delta nll| <= ~2.4e-7 absolute; faster).  See gh_ctx_set_compat."""
+        (faster; |delta nll| <= B(M_pad) = 4.4e-7, 5.2e-7, 7.7e-7, 9.8e-7, 1.2e-6, 1.4e-6 absolute for M_pad = 4, 8, 16, 32,
+        48, 64 padded components, plus 2^-50 |nll|: DESIGN.md section 4.1).  See gh_ctx_set_compat."""
         _check(self.lib, self.lib.gh_ctx_set_compat(self.h, (1 if underflow else 0) | (2 if lse_f32 else 0)))
 
     @property
