@@ -248,10 +248,14 @@ int gh_lattices_set_beam(gh_lattices* l, int beam);
  * gh_forward_backward are chosen by form; anything else runs on the row-per-lane kernels).  Bit 0: one left-to-right
  * chain (hmm.py:126-135); bit 1: K layers of the same W words (build_state_sequences, continuous_speech.py:13-53);
  * bit 2: word-loop grammar; bit 3: one word per layer, a graph per transcript (continuous_speech.py:80); bit 4:
- * one-word chains for forward-backward.  < 0: NULL argument.
+ * one-word chains for forward-backward; bit 5: bigram grammar -- the word loop with one non-emitting ENTRY row per word
+ * (rows: start | states 1..n-1 of every word | entry rows | state 0 of every word; last state of v -> entry row of w at
+ * the bigram cost, entry row of w -> state 0 of w at cost 0, start row -> state 0 of w at the start cost).
+ * < 0: NULL argument.
  * What the forms take: words of 2 .. 8, 12 or 16 states with arcs from s, s-1, s-2; bit 1: up to 16 words per layer
  * and 8 layers (16 layers for words of <= 8 states), or 17 .. 64 words per layer with <= 8 layers of <= 8 states;
- * bit 2: up to 16 words, or 17 .. 64 words of <= 8 states; bit 3: transcripts of up to 16 words. */
+ * bit 2: up to 16 words, or 17 .. 64 words of <= 8 states; bit 3: transcripts of up to 16 words; bit 5: 2 .. 16 words
+ * (not 16 states with s-2 arcs); one word is the loop form. */
 int gh_lattices_forms(const gh_lattices* l);
 
 /* --------------------------------------------------- A6: decode_hmm_states

@@ -179,8 +179,15 @@ static int viterbi_impl(gh_ctx* ctx, const gh_lattices* lat, const gh_batch* b, 
         if (no_layers) use_layers = false;
         if (b->any_T1) use_layers = false;   // T == 1: the reference's column wrap (lean kernel)
     }
+    // bigram form (gh_viterbi_bigram.hip): the loop form with word-to-word costs, same conditions
+    bool use_bigram = !use_chain && !use_layers && lat->bigram_ok && uniform && !out_costs && lat->beam <= 0;
+    {
+        const bool no_bigram = forced_kernel() != 0;
+        if (no_bigram) use_bigram = false;
+        if (b->any_T1) use_bigram = false;   // T == 1: the reference's column wrap (lean kernel)
+    }
     // sequence form (forced-alignment graphs, one per distinct transcript; gh_seq.hip)
-    bool use_seq = !use_chain && !use_layers && lat->seq_ok && !out_costs && lat->beam <= 0;
+    bool use_seq = !use_chain && !use_layers && !use_bigram && lat->seq_ok && !out_costs && lat->beam <= 0;
     {
         const bool no_seq = forced_kernel() != 0;
         if (no_seq) use_seq = false;
@@ -188,7 +195,7 @@ static int viterbi_impl(gh_ctx* ctx, const gh_lattices* lat, const gh_batch* b, 
     }
     GH_REQUIRE(!lat->deferred_src || use_seq, "gh_viterbi: internal: a transcripts handle left the sequence-form path unexpanded");
     // layer-form kernels in label mode: the back-trace writes the label sequences itself, no path is materialised
-    const bool labels_direct = use_layers && want_labels && !out_path;
+    const bool labels_direct = (use_layers || use_bigram) && want_labels && !out_path;
     std::vector<int64_t> own_path_off;  // label mode: the path lives on the device only, capacities are ours
     if ((want_labels || want_segments) && !out_path && !labels_direct) {
         own_path_off.assign(U + 1, 0);
@@ -243,6 +250,7 @@ static int viterbi_impl(gh_ctx* ctx, const gh_lattices* lat, const gh_batch* b, 
                 const int l = utt_lattice ? utt_lattice[u] : 0;
                 // (blocks padded to 8 entries = 16 bytes: the lean kernel flushes back-pointers with 16-byte stores)
                 const size_t need = use_layers ? gh_layers_bp_entries(lat->h_layers, b->offsets[u + 1] - b->offsets[u])
+                                    : use_bigram ? gh_bigram_bp_entries(lat->h_layers, b->offsets[u + 1] - b->offsets[u])
                                     : use_seq ? gh_seq_bp_entries(lat->seq_N, lat->seq_skip, b->offsets[u + 1] - b->offsets[u])
                                                : ((size_t)(b->offsets[u + 1] - b->offsets[u]) * lat->lat[l].R + 7) & ~size_t(7);
                 if (acc && (acc + need) * 2 > BP_BUDGET) {
@@ -379,6 +387,22 @@ static int viterbi_impl(gh_ctx* ctx, const gh_lattices* lat, const gh_batch* b, 
             if (!rc && want_path) rc = gh_launch_lattice_backtrace(ctx, c, lat->h_layers, chunk_begin[k], chunk_begin[k + 1] - chunk_begin[k]);
             if (rc) return rc;
         }
+    }
+    if (use_bigram) {
+        gh_layers_args c;
+        memset(&c, 0, sizeof c);
+        c.lf = lat->d_layers; c.end_slot = lat->d_lf_end_slot; c.end_rows = lat->d_end_rows; c.n_end = lat->lat[0].n_end; c.S = S;
+        c.nll = b->nll; c.utt_off = b->d_offsets; c.perm = b->d_perm; c.bp = d_bp; c.bp_off = d_bpoff;
+        c.end_cost = d_endcost; c.best_end = d_bestend; c.path = d_path; c.path_off = d_pathoff; c.path_len = d_pathlen;
+        c.flag = d_flag2;
+        if (labels_direct) { c.row_label = d_rowlabel; c.labels = d_labels; c.label_off = d_labeloff; c.n_labels = d_nlabels; }
+        for (size_t k = 0; k + 1 < chunk_begin.size(); ++k) {
+            const int64_t u0 = chunk_begin[k], nu = chunk_begin[k + 1] - u0;
+            rc = gh_launch_viterbi_bigram(ctx, c, lat->h_layers, u0, nu, b->dtype == GH_F64, want_path);
+            if (!rc && want_path) rc = gh_launch_bigram_backtrace(ctx, c, lat->h_layers, u0, nu);
+            if (rc) return rc;
+        }
+        use_layers = true;   // (from here on: "a lattice kernel has run", the row-per-lane kernels are skipped)
     }
     if (use_seq) {
         gh_layers_args c;

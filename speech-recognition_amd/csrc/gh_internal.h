@@ -191,6 +191,11 @@ static inline bool gh_seq_n_ok(int N) { return (N >= 2 && N <= 8) || N == 12 || 
 // rows loop_row+1+w = state 0 of word w.  Last states feed the loop row, the start row (cost cin0) and the loop row
 // (cost cin) feed the first states, all in the same column.  gh_viterbi runs it with FOUR utterances per wave: DPP
 // row = utterance, lane = word (gh_viterbi_layers.hip, viterbi_loop_kernel).
+// BIGRAM form (K = 1, loop = 2; gh_lattices::bigram_ok, not layers_ok): the loop form with ONE ENTRY ROW PER WORD instead of
+// the single loop row (continuous_speech.build_bigram_grammar) -- rows loop_row + w = non-emitting entry row of word w, fed
+// by the last state of every word v at cost bg[v][w]; rows loop_row + W + w = state 0 of word w, fed by the start row
+// (cin0), by its entry row at cost 0 and by itself.  Same lane layout; the one row minimum becomes a 16 x 16 min-plus
+// step (gh_viterbi_bigram.hip).  Up to GH_LAYERS_ROWW words.
 struct gh_layerform {
     int32_t K, W, N, skip;      // layers, words per layer, states per word, any s-2 arc
     int32_t P, R, loop, loop_row;
@@ -199,6 +204,9 @@ struct gh_layerform {
     double c0[GH_LAYERS_MAXW][GH_LAYERS_MAXN], c1[GH_LAYERS_MAXW][GH_LAYERS_MAXN], c2[GH_LAYERS_MAXW][GH_LAYERS_MAXN];
     double cin[GH_LAYERS_MAXW], cout[GH_LAYERS_MAXW];   // +inf = no such arc
     double cin0[GH_LAYERS_MAXW];                        // loop form: arc from the start row into state 0 (arcs bit4)
+    // BIGRAM form (loop = 2, up to GH_LAYERS_ROWW words): loop_row is the FIRST of the W entry rows
+    double bg[GH_LAYERS_ROWW][GH_LAYERS_ROWW];          // bg[v][w]: last state of word v -> entry row of word w, +inf = no such arc
+    uint16_t bg_in[GH_LAYERS_ROWW];                     // bit v of bg_in[w]: that arc exists
 };
 
 // SEQUENCE form: a forced-alignment lattice (continuous_speech.py:80: build_state_sequences(models, [[l] for l in labels])) --
@@ -267,6 +275,7 @@ struct gh_lattices {
     gh_fbchain* d_fbchain;
     bool layers_ok;                  // L == 1 and the graph is a gh_layerform (layers or loop: h_layers.loop)
     gh_layerform h_layers;
+    bool bigram_ok = false;          // L == 1 and the graph is in bigram form (h_layers.loop == 2; layers_ok stays false)
     gh_layerform* d_layers;
     int32_t* d_lf_end_slot;          // [R] position of a row in the end list or -1
     bool seq_ok;                     // every graph is in sequence form with the same N

@@ -2,6 +2,7 @@
 // dead arc flags, levels, narrow/wide row ordering, transposed CSR, chain form detection.
 #include "gh_internal.h"
 #include "gh_host.h"
+#include "gh_viterbi.h"
 
 // ----------------------------------------------------------------- lattices
 extern "C" int gh_lattices_create(gh_ctx* ctx, int L, const int64_t* row_off, const int32_t* row_state,
@@ -475,9 +476,81 @@ extern "C" int gh_lattices_create(gh_ctx* ctx, int L, const int64_t* row_off, co
             lt->layers_ok = true;
         }
     }
+    // ---- bigram form (gh_layerform with loop = 2): the loop grammar with one non-emitting ENTRY row per word ----
+    // (one word: the layout IS the loop form's, recognised above)
+    if (!lt->layers_ok && L == 1 && !lt->has_nan_arc && !lt->has_self_arc) {
+        const int R = lt->lat[0].R;
+        gh_layerform& f = lt->h_layers;
+        memset(&f, 0, sizeof f);
+        bool ok = R >= 7 && h_state[0] < 0;
+        int Lr = 1, W = 0;
+        if (ok) {
+            while (Lr < R && h_state[Lr] >= 0) ++Lr;                 // states 1 .. N-1 of every word
+            while (Lr + W < R && h_state[Lr + W] < 0) ++W;           // the entry rows
+            ok = Lr > 1 && W >= 2 && W <= GH_LAYERS_ROWW && Lr + 2 * W == R && (Lr - 1) % W == 0;
+            for (int r = Lr + W; ok && r < R; ++r) if (h_state[r] < 0) ok = false;
+        }
+        const int N = ok ? (Lr - 1) / W + 1 : 0;
+        ok = ok && gh_seq_n_ok(N) && lt->lat[0].n_start == 1 && (h_start[0] & 1);
+        auto row_of = [&](int w, int sx) { return sx == 0 ? Lr + W + w : 1 + w * (N - 1) + (sx - 1); };
+        std::vector<int> wof(R, -1), sof(R, -1);
+        for (int w = 0; ok && w < W; ++w)
+            for (int sx = 0; sx < N; ++sx) { wof[row_of(w, sx)] = w; sof[row_of(w, sx)] = sx; }
+        for (int w = 0; w < GH_LAYERS_MAXW; ++w) {
+            f.cin[w] = f.cout[w] = f.cin0[w] = INFINITY;
+            for (int sx = 0; sx < GH_LAYERS_MAXN; ++sx) f.c0[w][sx] = f.c1[w][sx] = f.c2[w][sx] = INFINITY;
+        }
+        for (int v = 0; v < GH_LAYERS_ROWW; ++v)
+            for (int w = 0; w < GH_LAYERS_ROWW; ++w) f.bg[v][w] = INFINITY;
+        bool skip = false;
+        const int32_t* ptr = h_ptr.data();
+        for (int r = 0; ok && r < R; ++r)
+            for (int p = ptr[r]; ok && p < ptr[r + 1]; ++p) {
+                const int o = (int)(h_prow[p] & GH_ARC_ROW);
+                const double c = h_pcost[p];
+                if (r == 0) { ok = false; break; }                                   // nothing enters the start row
+                if (r >= Lr && r < Lr + W) {                                         // last state of word v -> entry row of word w
+                    const int w = r - Lr, v = wof[o];
+                    if (v < 0 || sof[o] != N - 1 || ((f.bg_in[w] >> v) & 1)) { ok = false; break; }
+                    f.bg[v][w] = c;
+                    f.bg_in[w] |= (uint16_t)(1u << v);
+                } else if (o == 0 || (o >= Lr && o < Lr + W)) {                      // start row / the word's own entry row -> state 0
+                    const int w = wof[r];
+                    const int bit = o == 0 ? 16 : 8;
+                    if (sof[r] != 0 || (f.arcs[w][0] & bit)) { ok = false; break; }
+                    if (o == 0) f.cin0[w] = c;
+                    else if (o != Lr + w || c != 0.0) { ok = false; break; }         // (entry row -> state 0 costs nothing)
+                    f.arcs[w][0] |= (uint8_t)bit;
+                } else {                                                             // inside a word: from s, s-1, s-2
+                    const int w = wof[r], d = sof[r] - sof[o];
+                    if (w < 0 || wof[o] != w || d < 0 || d > 2) { ok = false; break; }
+                    double& t = d == 0 ? f.c0[w][sof[r]] : d == 1 ? f.c1[w][sof[r]] : f.c2[w][sof[r]];
+                    if (!std::isinf(t)) { ok = false; break; }
+                    t = c;
+                    f.arcs[w][sof[r]] |= (uint8_t)(1 << d);
+                    if (d == 2) skip = true;
+                }
+            }
+        for (int w = 0; ok && w < W; ++w) if (!(f.arcs[w][0] & 8)) ok = false;       // every word is entered through its entry row
+        ok = ok && gh_bigram_n_ok(N, skip ? 1 : 0);
+        if (ok) {
+            lf_slot.assign(R, -1);
+            for (int k = 0; ok && k < (int)h_end.size(); ++k) {
+                const int r = h_end[k];
+                if (h_state[r] < 0 || lf_slot[r] >= 0) ok = false;
+                else lf_slot[r] = k;
+            }
+        }
+        if (ok) {
+            for (int w = 0; w < W; ++w)
+                for (int sx = 0; sx < N; ++sx) f.state[w][sx] = h_state[row_of(w, sx)];
+            f.K = 1; f.W = W; f.N = N; f.skip = skip ? 1 : 0; f.P = W * N; f.R = R; f.loop = 2; f.loop_row = Lr;
+            lt->bigram_ok = true;
+        }
+    }
     UploadArena ar;
     std::vector<gh_layerform> one(1, lt->h_layers);
-    if (lt->layers_ok) { ar.add(&lt->d_layers, one); ar.add(&lt->d_lf_end_slot, lf_slot); }
+    if (lt->layers_ok || lt->bigram_ok) { ar.add(&lt->d_layers, one); ar.add(&lt->d_lf_end_slot, lf_slot); }
     if (lt->chain_ok) {
         ar.add(&lt->d_ch_cost0, ch0); ar.add(&lt->d_ch_cost1, ch1); ar.add(&lt->d_ch_cost2, ch2);
         ar.add(&lt->d_ch_info, chinfo); ar.add(&lt->d_ch_end_slot, chslot); ar.add(&lt->d_ch_group_row0, chgroups);
@@ -517,7 +590,8 @@ extern "C" int gh_lattices_set_beam(gh_lattices* l, int beam) {
 extern "C" int gh_lattices_forms(const gh_lattices* l) {
     if (!l) return -1;
     const bool loop = l->layers_ok && l->h_layers.loop;
-    return (l->chain_ok ? 1 : 0) | (l->layers_ok && !loop ? 2 : 0) | (loop ? 4 : 0) | (l->seq_ok ? 8 : 0) | (l->fbchain_ok ? 16 : 0);
+    return (l->chain_ok ? 1 : 0) | (l->layers_ok && !loop ? 2 : 0) | (loop ? 4 : 0) | (l->seq_ok ? 8 : 0) | (l->fbchain_ok ? 16 : 0) |
+           (l->bigram_ok ? 32 : 0);
 }
 
 extern "C" int64_t gh_viterbi_path_cap(const gh_lattices* lat, int l, int64_t T) {

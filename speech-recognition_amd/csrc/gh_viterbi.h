@@ -141,3 +141,10 @@ size_t gh_seq_bp_entries(int N, int skip, int64_t T);
 int gh_launch_viterbi_seq(gh_ctx* ctx, const gh_layers_args& a, int N, int skip, int64_t u_begin, int64_t n_utts, bool f64,
                           bool want_path);
 int gh_launch_seq_backtrace(gh_ctx* ctx, const gh_layers_args& a, int N, int skip, int64_t u_begin, int64_t n_utts);
+// bigram form (gh_viterbi_bigram.hip: the loop form with one entry row per word): forward sweep, four utterances per wave,
+// and its back-trace (path or label mode); gh_bigram_n_ok: the word sizes the kernel is instantiated for
+bool gh_bigram_n_ok(int N, int skip);
+size_t gh_bigram_bp_entries(const gh_layerform& f, int64_t T);
+int gh_launch_viterbi_bigram(gh_ctx* ctx, const gh_layers_args& a, const gh_layerform& f, int64_t u_begin, int64_t n_utts,
+                             bool f64, bool want_path);
+int gh_launch_bigram_backtrace(gh_ctx* ctx, const gh_layers_args& a, const gh_layerform& f, int64_t u_begin, int64_t n_utts);

@@ -1043,7 +1043,7 @@ class Lattices:
         _check(self.ctx.lib, self.ctx.lib.gh_lattices_set_beam(self.h, k))
         self.beam = k
 
-    FORMS = ("chain", "layers", "loop", "sequence", "fb_chain")
+    FORMS = ("chain", "layers", "loop", "sequence", "fb_chain", "bigram")
 
     def forms(self):
         """Names of the special forms the graphs were recognised in (gh_lattices_forms): they select the kernels."""

@@ -11,7 +11,7 @@ import numpy as np
 
 from . import _hip
 from . import _pack
-from .continuous_speech import packed_lattice, packed_loop_lattice
+from .continuous_speech import packed_lattice, packed_loop_lattice, packed_bigram_lattice
 
 __all__ = ["IsolatedWordRecognizer", "ContinuousDecoder", "InFlight", "path_to_words", "sequence_report", "train_words"]
 
@@ -319,9 +319,14 @@ class ContinuousDecoder:
     column (main.py:60).
     grammar="loop": the word-loop grammar (`build_loop_grammar`) -- any number of
     words, cost = min over K of the K-layer costs, on a graph of 2 + W*n rows instead of
-    1 + K*(W*n + 1)."""
+    1 + K*(W*n + 1).
+    grammar="bigram": the loop grammar with word-to-word costs (`build_bigram_grammar`): `bigram` is a [W, W] cost
+    matrix (`bigram[v, w]`: word w after word v, +inf = forbidden) with optional start costs `initial` [W], or a
+    `sr.langmodel.BigramModel`, whose `costs(lm_scale)` are then used.  Up to 16 words of 2..8, 12 or 16 states
+    run on the bigram-form kernel; anything larger decodes on the row-per-lane kernels, same results."""
 
-    def __init__(self, models, n_layers=7, device=None, dtype=np.float64, grammar="layers", word_penalty=0.0, ctx=None):
+    def __init__(self, models, n_layers=7, device=None, dtype=np.float64, grammar="layers", word_penalty=0.0, ctx=None,
+                 bigram=None, initial=None, lm_scale=1.0):
         self.ctx = ctx if ctx is not None else _hip.default_context(device)
         self.dtype = dtype
         # (single-Gaussian word models decode through the likelihood kernel here: mahalanobis() is the one-component
@@ -335,8 +340,19 @@ class ContinuousDecoder:
         elif grammar == "loop":
             graph, self.nes_rows = packed_loop_lattice(wt, self.n, word_penalty)
             self._max_labels = lambda T: T // max(1, self.n - 1) + 2      # a word spans at least n - 1 column steps
+        elif grammar == "bigram":
+            if bigram is None:
+                raise ValueError("grammar='bigram' needs `bigram`: a [W, W] cost matrix or a BigramModel")
+            if hasattr(bigram, "costs"):
+                if initial is not None:
+                    raise ValueError("`initial` comes from the BigramModel; pass either a model or cost arrays")
+                if bigram.n_words != W:
+                    raise ValueError("the BigramModel has %d words, the decoder %d" % (bigram.n_words, W))
+                initial, bigram = bigram.costs(lm_scale)
+            graph, self.nes_rows = packed_bigram_lattice(wt, self.n, bigram, initial)
+            self._max_labels = lambda T: T // max(1, self.n - 1) + 2      # as for the loop grammar
         else:
-            raise ValueError("grammar must be 'layers' or 'loop', not %r" % (grammar,))
+            raise ValueError("grammar must be 'layers', 'loop' or 'bigram', not %r" % (grammar,))
         self.grammar = grammar
         self.row_state = graph["row_state"]
         self.lat = _hip.Lattices(self.ctx, [graph])

@@ -25,7 +25,7 @@ from .hmm_state import GMM, NES, mahalanobis
 from .hmm import HMM
 from .lockstep import LockstepFitter, PartitionStream, fast_partition_ok
 
-__all__ = ["build_state_sequences", "build_loop_grammar", "continuous_train", "forced_alignments", "aligned_frame_states",
+__all__ = ["build_state_sequences", "build_loop_grammar", "build_bigram_grammar", "continuous_train", "forced_alignments", "aligned_frame_states",
            "cut_segments"]
 
 
@@ -158,6 +158,95 @@ def packed_loop_lattice(word_transitions, n_per_word, word_penalty=0.0, state_ba
     return dict(row_state=row_state, arc_to=np.asarray(to, dtype=np.int32), arc_from=np.asarray(frm, dtype=np.int32),
                 arc_cost=np.asarray(cost, dtype=np.float64), start_rows=np.array([0], dtype=np.int32),
                 end_rows=np.asarray(ends, dtype=np.int32)), [0, loop_row]
+
+
+def _bigram_layout(W, n):
+    """Row bookkeeping of the bigram grammar: (R, entry_row [W], row_of [W, n])."""
+    if n < 2:
+        raise ValueError("a bigram grammar needs words of at least two states, not %d" % n)
+    first = 1 + W * (n - 1)
+    row_of = np.empty((W, n), dtype=np.int64)
+    row_of[:, 1:] = 1 + np.arange(W)[:, None] * (n - 1) + np.arange(n - 1)[None, :]
+    row_of[:, 0] = first + W + np.arange(W)
+    return 1 + W * (n - 1) + 2 * W, first + np.arange(W), row_of
+
+
+def _bigram_costs(W, bigram, initial):
+    """(B [W, W], init [W]) as float64 after validation: finite or +inf, never NaN or -inf."""
+    B = np.array(bigram, dtype=np.float64)
+    init = np.zeros(W) if initial is None else np.array(initial, dtype=np.float64)
+    if B.shape != (W, W):
+        raise ValueError("bigram costs must have shape (%d, %d), not %s" % (W, W, B.shape))
+    if init.shape != (W,):
+        raise ValueError("initial costs must have shape (%d,), not %s" % (W, init.shape))
+    for name, a in (("bigram", B), ("initial", init)):
+        if np.isnan(a).any() or np.isneginf(a).any():
+            raise ValueError("%s costs must be finite or +inf (forbidden): found NaN or -inf" % name)
+    return B, init
+
+
+def build_bigram_grammar(hmms: List[HMM], bigram, initial=None):
+    """Word loop with WORD-TO-WORD costs: `bigram[v, w]` is the cost of word w following word v (+inf: forbidden),
+    `initial[w]` the cost of starting with word w (default 0; +inf: the word cannot start an utterance) -- e.g. the
+    `costs()` of a `sr.langmodel.BigramModel`.
+
+    Same return convention as `build_loop_grammar` and decodable by `decode_hmm_states` as is: the loop grammar's one
+    loop row becomes one non-emitting ENTRY row per destination word,
+        0: non-emitting start | states 1..n-1 of every word | entry rows L_0 .. L_{W-1} | state 0 of every word,
+    with arcs last state of v -> L_w (cost bigram[v, w]), L_w -> state 0 of w (cost 0), start -> state 0 of w (cost
+    initial[w]), all same-column hops from rows the sweep has already visited in the column (decode.py:97-98,109-111).
+    Ties between predecessor words go to the lower word (first minimum in ascending origin order)."""
+    n = len(hmms[0].gmm_states)
+    W = len(hmms)
+    B, init = _bigram_costs(W, bigram, initial)
+    R, entry, row_of = _bigram_layout(W, n)
+    trans = np.full((R, R), np.inf)
+    seq = [None] * R
+    seq[0] = NES()
+    ends = []
+    for w, word in enumerate(hmms):
+        assert n == len(word.gmm_states)
+        rows = row_of[w]
+        seq[entry[w]] = NES()
+        for i in range(n):
+            seq[rows[i]] = word.gmm_states[i]
+        trans[np.ix_(rows, rows)] = word.transitions
+        trans[rows[0], 0] = init[w]
+        trans[rows[0], entry[w]] = 0
+        trans[entry[w], row_of[:, n - 1]] = B[:, w]
+        ends.append(int(rows[n - 1]))
+    return seq, trans, ends
+
+
+def packed_bigram_lattice(word_transitions, n_per_word, bigram, initial=None, state_base=None):
+    """`build_bigram_grammar` as a graph dict for `_hip.Lattices` (row_state = word * n + state) and its non-emitting
+    rows; forbidden (+inf) pairs and starts are left out of the arc list."""
+    W = len(word_transitions)
+    B, init = _bigram_costs(W, bigram, initial)
+    R, entry, row_of = _bigram_layout(W, n_per_word)
+    row_state = np.full(R, -1, dtype=np.int32)
+    to, frm, cost, ends = [], [], [], []
+    for w in range(W):
+        base = w * n_per_word if state_base is None else state_base[w]
+        rows = row_of[w]
+        row_state[rows] = base + np.arange(n_per_word)
+        wt = np.asarray(word_transitions[w])
+        if wt.shape != (n_per_word, n_per_word):
+            raise ValueError("word %d: transitions of shape %s, expected (%d, %d)" % (w, wt.shape, n_per_word, n_per_word))
+        i, j = np.nonzero(~np.isinf(wt))
+        to += list(rows[i]) + [rows[0]]
+        frm += list(rows[j]) + [entry[w]]
+        cost += list(wt[i, j]) + [0.0]
+        if not np.isinf(init[w]):
+            to.append(rows[0]); frm.append(0); cost.append(init[w])
+        v = np.flatnonzero(~np.isinf(B[:, w]))
+        to += [entry[w]] * len(v)
+        frm += list(row_of[v, n_per_word - 1])
+        cost += list(B[v, w])
+        ends.append(int(rows[n_per_word - 1]))
+    return dict(row_state=row_state, arc_to=np.asarray(to, dtype=np.int32), arc_from=np.asarray(frm, dtype=np.int32),
+                arc_cost=np.asarray(cost, dtype=np.float64), start_rows=np.array([0], dtype=np.int32),
+                end_rows=np.asarray(ends, dtype=np.int32)), [0] + [int(r) for r in entry]
 
 
 def transcript_state_sets(label_seqs, n, n_words):

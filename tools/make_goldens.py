@@ -756,6 +756,71 @@ def g19(R):
 ALL["G18"] = g18
 ALL["G19"] = g19
 
+def g20(R):
+    """Bigram grammar run through the reference's OWN decode_hmm_states: the loop graph of G14 with one non-emitting
+    ENTRY row per destination word instead of the single loop row -- [start NES | states 1..n-1 of every word |
+    entry NES of every word | state 0 of every word]; last state of v -> entry of w at cost B[v, w], entry of w ->
+    state 0 of w at cost 0, start -> state 0 of w at cost init[w].  Three cost sets: c0 random finite; c1 with
+    forbidden (+inf) pairs and starts; c2 small integers with words 0 / 1 and 2 / 3 sharing their parameters, so that
+    two predecessor words tie exactly in every column and the reference's first minimum decides.  Stored: graph
+    arcs, the reference's cost matrices / paths / digits."""
+    rng = np.random.default_rng(201)
+    W, n, M, D = 4, 3, 2, 6
+    means, vars_, w, trans = synth_model(rng, W, n, M, D)
+    Rr = 1 + W * (n - 1) + 2 * W
+    first = 1 + W * (n - 1)
+    row_of = np.empty((W, n), dtype=np.int64)
+    for wd in range(W):
+        row_of[wd, 1:] = 1 + wd * (n - 1) + np.arange(n - 1)
+        row_of[wd, 0] = first + W + wd
+    B0 = rng.uniform(0.0, 4.0, size=(W, W))
+    B1 = rng.uniform(0.0, 4.0, size=(W, W))
+    B1[0, 1] = B1[1, 1] = B1[2, 0] = B1[3, 2] = B1[3, 3] = np.inf
+    B2 = np.array([[2.0, 2.0, 1.0, 3.0], [2.0, 2.0, 1.0, 3.0], [1.0, 1.0, 4.0, 2.0], [1.0, 1.0, 4.0, 2.0]])
+    cases = [(B0, rng.uniform(0.0, 2.0, size=W), False), (B1, np.array([0.5, np.inf, 1.5, np.inf]), False),
+             (B2, np.array([1.0, 1.0, 2.0, 2.0]), True)]
+    out = dict(word_trans=trans, n_utts=np.array(3), n_cases=np.array(len(cases)))
+    for ci, (B, init, twins) in enumerate(cases):
+        mm, vv, ww = means.copy(), vars_.copy(), w.copy()
+        if twins:
+            for a, b in ((0, 1), (2, 3)):
+                mm[b], vv[b], ww[b] = mm[a], vv[a], ww[a]
+        hmms = [make_hmm(R, mm[i], vv[i], ww[i], trans) for i in range(W)]
+        ids = {g.id: (wi, si) for wi, h in enumerate(hmms) for si, g in enumerate(h.gmm_states)}
+        tr = np.full((Rr, Rr), np.inf)
+        seq = [None] * Rr
+        seq[0] = R.NES()
+        ends = []
+        for wd, h in enumerate(hmms):
+            rows = row_of[wd]
+            seq[first + wd] = R.NES()
+            for i in range(n):
+                seq[rows[i]] = h.gmm_states[i]
+            tr[np.ix_(rows, rows)] = h.transitions
+            tr[rows[0], 0] = init[wd]
+            tr[rows[0], first + wd] = 0
+            tr[first + wd, row_of[:, n - 1]] = B[:, wd]
+            ends.append(int(rows[n - 1]))
+        fi, fj = np.nonzero(~np.isinf(tr))
+        row_word = np.array([-1 if type(s) is R.NES else ids[s.id][0] for s in seq])
+        row_state = np.array([-1 if type(s) is R.NES else ids[s.id][1] for s in seq])
+        pp = "c%d_" % ci
+        out.update({pp + "B": B, pp + "init": init, pp + "means": mm, pp + "vars": vv, pp + "w": ww,
+                    pp + "arc_to": fi, pp + "arc_from": fj, pp + "arc_cost": tr[fi, fj],
+                    pp + "row_word": row_word, pp + "row_state": row_state, pp + "ends": np.array(ends)})
+        urng = np.random.default_rng(2010 + ci)
+        for u, nw in enumerate((1, 3, 5)):
+            words = urng.integers(0, W, size=nw)
+            x = synth_utt(urng, mm, vv, words, 7, 11)
+            with quiet():
+                costs, path = R.decode_hmm_states(x, seq, tr, end_points=[[e, -1] for e in ends])
+            out.update({pp + "x%d" % u: x, pp + "words%d" % u: words, pp + "costs%d" % u: costs, pp + "path%d" % u: path,
+                        pp + "digits%d" % u: np.array(reference_postprocess(R, path, seq, hmms))})
+    save("G20_bigram_grammar", **out)
+
+
+ALL["G20"] = g20
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--only", default="")

@@ -1,6 +1,6 @@
 # -*- coding: utf-8 -*-
-"""Randomised sweep of the word-template Viterbi kernels -- layer form (K-layer lattice), loop form (word-loop grammar), sequence
-form (forced alignment, a graph per transcript) -- against the row-per-lane lean kernel, which implements the same
+"""Randomised sweep of the word-template Viterbi kernels -- layer form (K-layer lattice), loop form (word-loop grammar), bigram
+form (the loop grammar with word-to-word costs), sequence form (forced alignment, a graph per transcript) -- against the row-per-lane lean kernel, which implements the same
 decode_hmm_states semantics (decode.py:80-146) by another route: random word counts (1 .. 16, and 17 .. 64 for the wide layer kernel), states per word (2 .. 8, 12,
 16), layers (1 .. 16), skip arcs, penalties, fp64 / fp32, utterances from too short to long.  End costs BITWISE, the chosen
 end, paths and labels equal.
@@ -17,7 +17,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "speech-recognition_amd"))
 from sr.recognition import _hip
-from sr.recognition.continuous_speech import packed_lattice, packed_loop_lattice
+from sr.recognition.continuous_speech import packed_lattice, packed_loop_lattice, packed_bigram_lattice
 
 trials = int(sys.argv[1]) if len(sys.argv) > 1 else 60
 rng = np.random.default_rng(int(sys.argv[2]) if len(sys.argv) > 2 else 0)
@@ -134,6 +134,21 @@ for trial in range(trials):
             if "loop" not in lat.forms():
                 problems.append("loop grammar not taken as loop form (%s)" % sorted(lat.forms()))
             problems += compare("loop", lat, b, n, graph["row_state"])
+            lat.close()
+        # bigram form (2 .. 16 words; 16 states with skip arcs and anything wider stay on the row-per-lane kernels):
+        # random costs, 10-30 % of the pairs forbidden -- every word keeps one way in -- and some words that cannot start
+        if W >= 2:
+            B = rng.uniform(0.0, 4.0, size=(W, W))
+            B[rng.random((W, W)) < rng.uniform(0.1, 0.3)] = np.inf
+            B[rng.integers(0, W, size=W), np.arange(W)] = rng.uniform(0.0, 4.0, size=W)
+            init = rng.uniform(0.0, 2.0, size=W)
+            init[rng.random(W) < 0.3] = np.inf
+            init[int(rng.integers(0, W))] = 0.5
+            graph = packed_bigram_lattice(wt, n, B, init)[0]
+            lat = _hip.Lattices(ctx, [graph])
+            if ("bigram" in lat.forms()) != (W <= 16 and not (n == 16 and skip)):
+                problems.append("bigram grammar: forms %s" % sorted(lat.forms()))
+            problems += compare("bigram", lat, b, n, graph["row_state"])
             lat.close()
         # sequence form: every utterance against its own transcript
         keys, graphs, utt_graph = {}, [], np.empty(U, dtype=np.int32)
