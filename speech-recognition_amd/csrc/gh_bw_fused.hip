@@ -29,6 +29,7 @@
 // that produced gamma (same model: gh_gmm::serial == gh_batch::nll_serial is checked).  r = gamma exp(log(w pdf) + nll).
 #include "gh_internal.h"
 #include "gh_host.h"
+#include "gh_wave.h"
 
 namespace {
 
@@ -38,43 +39,20 @@ struct bwf_wg { int32_t graph, u_begin, u_end, pad; };           // utterances u
 struct bwf_pair { int32_t sa, sb, wg_begin, wg_end, p, m0; };     // column group p of a graph (states sa, sb (or -1), or -- WIDE --
                                                                   // components m0 .. m0 + 15 of state sa), its workgroups
 
-__device__ __forceinline__ double bwf_vmax(double a, double b) {
-    double r;
-    asm("v_max_f64 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
-    return r;
-}
-template <int CTRL> __device__ __forceinline__ double bwf_dpp(double v) {
-    const int lo = __builtin_amdgcn_mov_dpp(__double2loint(v), CTRL, 0xF, 0xF, true);
-    const int hi = __builtin_amdgcn_mov_dpp(__double2hiint(v), CTRL, 0xF, 0xF, true);
-    return __hiloint2double(hi, lo);
-}
 // all-reduce over the 8 lanes {8g .. 8g+7}: xor 1 (quad_perm 1,0,3,2), xor 2 (quad_perm 2,3,0,1), then the mirror image
 // inside the half row (lane i <-> 7 - i): every lane of one quad meets a lane of the other
 __device__ __forceinline__ double max8(double v) {
-    v = bwf_vmax(v, bwf_dpp<0xB1>(v));
-    v = bwf_vmax(v, bwf_dpp<0x4E>(v));
-    v = bwf_vmax(v, bwf_dpp<0x141>(v));
+    v = vmax(v, dpp_mov<0xB1>(v));
+    v = vmax(v, dpp_mov<0x4E>(v));
+    v = vmax(v, dpp_mov<0x141>(v));
     return v;
 }
 __device__ __forceinline__ double sum8(double v) {
-    v += bwf_dpp<0xB1>(v);
-    v += bwf_dpp<0x4E>(v);
-    v += bwf_dpp<0x141>(v);
+    v += dpp_mov<0xB1>(v);
+    v += dpp_mov<0x4E>(v);
+    v += dpp_mov<0x141>(v);
     return v;
 }
-// 2^(y/128) for finite y <= 0 (or NaN): table + degree-4 polynomial (see gh_loglik_mfma.hip, exp2s)
-__device__ __forceinline__ double bwf_exp2s(double y, const double* __restrict__ tab) {
-    const double n = __builtin_rint(y);
-    const double r = y - n;
-    const int ni = (int)n;
-    const double t = tab[ni & 127];
-    double p = fma(r, 3.583032305400251285e-11, 2.6466421444330968834e-08);
-    p = fma(p, r, 1.4662262387640424337e-05);
-    p = fma(p, r, 5.4152123481245727298e-03);
-    p = p * r;
-    return __builtin_ldexp(fma(t, p, t), ni >> 7);
-}
-
 // KS = k-steps of the density GEMM (K = 4 KS = 2 KP), LT = 16-column tiles of each half of Z (D + 1 <= 16 LT)
 // One WAVE per (utterance group of a word, state pair): the wave walks its utterances in 16-frame blocks, looks at the
 // pair's two gamma columns first and SKIPS a block whose 16 frames carry no occupancy for either state -- posteriors are
@@ -157,7 +135,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) void
     double Cj = GH_LSE_OFF64;
     if (valid) {
         const double c = lc - 0.5 * sm2;
-        Cj = (c == -INFINITY) ? GH_LSE_OFF64 : bwf_vmax(c * GH_LSE_SCALE64, GH_LSE_OFF64);
+        Cj = (c == -INFINITY) ? GH_LSE_OFF64 : vmax(c * GH_LSE_SCALE64, GH_LSE_OFF64);
     }
     // accumulation operand A = Z^T: this lane feeds column 16 t + j of the linear tiles (x[d] - c[d]; d = D: the ones
     // column, read from the zero padding with "centre" -1) and of the squared tiles
@@ -247,13 +225,13 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) void
             if (NORM) {
                 // log(w pdf) - log sum_m' w pdf = y + K nll: the likelihood kernel's own normaliser
                 const int hs = WIDE ? 0 : (j >> 3);
-                const double e = bwf_exp2s(y + nt[fr * 2 + hs], tab);
+                const double e = exp2s(y + nt[fr * 2 + hs], tab);
                 const double g = gt[fr * 2 + hs];
                 const double wgt = ((g > occ_floor) | (g != g)) ? g : 0.0;
                 R[r] = (valid & (fr < nf) & (wgt != 0.0)) ? e * wgt : 0.0;
             } else {
                 const double mx = max8(y);
-                const double e = bwf_exp2s(y - mx, tab);
+                const double e = exp2s(y - mx, tab);
                 const double s8 = sum8(e);
                 const double g = gt[fr * 2 + (j >> 3)];
                 const double wgt = ((g > occ_floor) | (g != g)) ? g : 0.0;

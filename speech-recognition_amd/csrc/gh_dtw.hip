@@ -16,12 +16,9 @@
 // HBM scratch and lane 0 walks them until cell (0,0) (decode.py:70-76).
 #include "gh_internal.h"
 #include "gh_dtw.h"
+#include "gh_wave.h"
 
 namespace {
-
-// workgroup barrier that orders LDS traffic only: the frame prefetch and the back-pointer / cost stores stay in flight
-// (a full __syncthreads waits for their round trips: three per column)
-__device__ __forceinline__ void dtw_lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
 // STAGED: template rows, variances, arc costs and the current frame are read from LDS (address space known at compile
 // time: with one pointer that may be LDS or global the compiler falls back to flat loads and spills the selects)
@@ -146,7 +143,7 @@ __global__ __launch_bounds__(1024) void dtw_kernel(gh_dtw_args a) {
         }
         col(cb)[i] = c;
         mark(cb)[i] = 0;
-        dtw_lds_barrier();
+        lds_barrier();
         unsigned char mk = 0;
         if (a.beam > 0 && act) {
             // rank in ascending (value, row) order == position in np.argsort of the column
@@ -162,10 +159,10 @@ __global__ __launch_bounds__(1024) void dtw_kernel(gh_dtw_args a) {
             // and +inf elsewhere (reset by the next column's row 0)
             costs[(int64_t)i * T + j] = mk ? ((j == T - 1) ? -1.0 : INF) : c;
         }
-        dtw_lds_barrier();
+        lds_barrier();
         mark(cb)[i] = mk;
         x_park((j + 1) & 1);
-        dtw_lds_barrier();
+        lds_barrier();
         pb = cb;
     }
     __syncthreads();   // (full barrier: the back-pointers written above are read back below)

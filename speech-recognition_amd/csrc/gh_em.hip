@@ -36,6 +36,7 @@
 #include "gh_internal.h"
 #include "gh_host.h"
 #include "gh_fb.h"
+#include "gh_wave.h"
 
 struct gh_em {
     gh_ctx* ctx;
@@ -163,12 +164,6 @@ __global__ __launch_bounds__(256) void em_tail_seq_kernel(const double* __restri
     if (tid == 0) { tail[S] = red[0]; tail[S + 1] = (double)U; }
 }
 
-__device__ __forceinline__ bool em_close(double a, double b) {   // np.isclose(a, b) with numpy's default tolerances
-    if (a == b) return true;
-    if (!(a - a == 0.0) || !(b - b == 0.0)) return false;
-    return fabs(a - b) <= 1e-8 + 1e-5 * fabs(b);
-}
-
 // M-step of one state per block from the (all-reduced) packed buffer: parallel.m_step + the floor / occupancy rules of
 // train.BaumWelchTrainer.iteration + _update_transitions, and the allclose test against the parameters it replaces.
 __global__ __launch_bounds__(256) void em_mstep_kernel(const double* __restrict__ packed, int64_t n_stats, int n, int M, int D,
@@ -195,7 +190,7 @@ __global__ __launch_bounds__(256) void em_mstep_kernel(const double* __restrict_
         if (sg == sg && sg < var_floor) sg = var_floor;      // np.maximum(sigma, var_floor): NaN stays NaN
         const bool ok = s0 > min_occ;
         const double mu1 = ok ? mu : mu0, v1 = ok ? sg : v0;
-        bad += !em_close(mu1, mu0) + !em_close(v1, v0);
+        bad += !np_isclose(mu1, mu0) + !np_isclose(v1, v0);
         mean[at] = mu1;
         var[at] = v1;
     }
@@ -203,7 +198,7 @@ __global__ __launch_bounds__(256) void em_mstep_kernel(const double* __restrict_
         const double s0 = st[tid * W1];
         const double w0 = weight[(int64_t)s * M + tid];
         const double w1 = (s0 > min_occ) ? s0 / counts : w0;
-        bad += !em_close(w1, w0);
+        bad += !np_isclose(w1, w0);
         weight[(int64_t)s * M + tid] = w1;
     }
     if (tid == 0 && update_trans) {

@@ -13,6 +13,7 @@
 #include "gh_internal.h"
 #include "gh_fb.h"
 #include "gh_xnum.h"
+#include "gh_wave.h"
 
 namespace {
 
@@ -27,9 +28,6 @@ __device__ __forceinline__ void lse_add(double v, double& m, double& s) {
     }
 }
 __device__ __forceinline__ double lse_val(double m, double s) { return (s > 0.0) ? m + log(s) : -INFINITY; }
-
-// workgroup barrier that orders LDS traffic only (the alpha / occupancy stores and the prefetch loads stay in flight)
-__device__ __forceinline__ void fb_lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
 // The graph (both CSRs, row tables, level offsets) is staged into LDS once per workgroup and the next column's
 // emissions / alpha column travel from HBM while the current column is processed: walking the CSR and fetching the
@@ -147,10 +145,10 @@ __global__ void fb_kernel(gh_fb_args a) {
                 alpha[(int64_t)t * R + r] = v;
                 if (o_alpha) o_alpha[(int64_t)r * T + t] = v;
             }
-            fb_lds_barrier();
+            lds_barrier();
         }
         em_park(emn, t + 1);
-        fb_lds_barrier();
+        lds_barrier();
         { double* t_ = prev; prev = cur; cur = t_; }
         { double* t_ = em0; em0 = emn; emn = t_; }
     }
@@ -193,7 +191,7 @@ __global__ void fb_kernel(gh_fb_args a) {
         alpha_prefetch(t - 1);
         em_prefetch(t - 1);
         for (int s = tid; s < S; s += bd) occ[s] = 0.0;
-        fb_lds_barrier();
+        lds_barrier();
         auto beta_row = [&](int i, double av) {   // row i of the level order; av = its alpha in this column
             const int r = g_order[i];
             double m = NEG, sm = 0.0;
@@ -234,7 +232,7 @@ __global__ void fb_kernel(gh_fb_args a) {
             } else {
                 for (int i = i0 + tid; i < i1; i += bd) beta_row(i, alpha[(int64_t)t * R + g_order[i]]);
             }
-            fb_lds_barrier();
+            lds_barrier();
         }
         if (a.occ) {
             double* orow = a.occ + (f0 + t) * S;
@@ -243,7 +241,7 @@ __global__ void fb_kernel(gh_fb_args a) {
         em_park(emn, t - 1);
         { double* t_ = nxt; nxt = cur; cur = t_; }
         { double* t_ = em1; em1 = em0; em0 = emn; emn = t_; }   // window slides down: (t, t+1) -> (t-1, t)
-        fb_lds_barrier();
+        lds_barrier();
         for (int r = tid; r < R; r += bd) cur[r] = NEG;  // same-column reads see only rows of this column
     }
     if (a.self_xi) {
@@ -280,10 +278,11 @@ __device__ __forceinline__ double lse2(double x, double y) {
 // and an integer add, the one transcendental per cell is the split exponential of the emission cost (the log-domain
 // version -- exp per term, log per sum -- took 0.34 ms per 12 500 utterances, compute bound at 8 % of HBM).
 template <int CTRL> __device__ __forceinline__ xnum fbc_dpp(xnum v) {
+    // a lane without a source: zero.  (High half first, on the shared int form: the order of the two halves is the order
+    // of the two v_mov_b32_dpp in the kernels' code.)
     xnum o;
-    o.f = __hiloint2double(__builtin_amdgcn_update_dpp(0, __double2hiint(v.f), CTRL, 0xF, 0xF, true),
-                           __builtin_amdgcn_update_dpp(0, __double2loint(v.f), CTRL, 0xF, 0xF, true));
-    o.e = __builtin_amdgcn_update_dpp(XN_ZERO_E, v.e, CTRL, 0xF, 0xF, false);
+    o.f = __hiloint2double(dpp_upd<CTRL, 0xF, true>(0, __double2hiint(v.f)), dpp_upd<CTRL, 0xF, true>(0, __double2loint(v.f)));
+    o.e = dpp_upd<CTRL>(XN_ZERO_E, v.e);
     return o;
 }
 

@@ -15,6 +15,7 @@
 #include "gh_internal.h"
 #include "gh_host.h"
 #include "gh_refit.h"
+#include "gh_wave.h"
 
 namespace {
 
@@ -1005,12 +1006,6 @@ __global__ void fit_em_prepare_kernel(int S, int k, int D, const double* __restr
     logc[g] = log(weight[g]) - 0.5 * (D * log2pi + sl);
 }
 
-__device__ __forceinline__ bool fit_close(double a, double b) {   // np.isclose(a, b), default tolerances
-    if (a == b) return true;
-    if (!(a - a == 0.0) || !(b - b == 0.0)) return false;
-    return fabs(a - b) <= 1e-8 + 1e-5 * fabs(b);
-}
-
 // GMM.em_update (hmm_state.py:134-159) of one state per block: M-step from the centred statistics, parameters installed,
 // then the allclose test against the previous iteration's; a state that passes stops, the others remember the new values
 __global__ __launch_bounds__(256) void fit_em_update_kernel(int k, int D, int plen, const double* __restrict__ stats,
@@ -1049,13 +1044,13 @@ __global__ __launch_bounds__(256) void fit_em_update_kernel(int k, int D, int pl
         if (sg <= 0) atomicOr(counter + 1, 16);              // update_models raises before the convergence test (hmm_state.py:149); < 0: below the sums' rounding noise
         mean[at] = mu;
         var[at] = sg;
-        mine += !fit_close(mu, old_mu[at]) + !fit_close(sg, old_sigma[at]);
+        mine += !np_isclose(mu, old_mu[at]) + !np_isclose(sg, old_sigma[at]);
     }
     if (tid < k) {
         const double w = st[tid * Wd] / nframes[s];
         diff += !same(w, weight[(int64_t)s * k + tid]);
         weight[(int64_t)s * k + tid] = w;
-        mine += !fit_close(w, old_w[(int64_t)s * k + tid]);
+        mine += !np_isclose(w, old_w[(int64_t)s * k + tid]);
     }
     if (mine) atomicAdd(&bad, mine);
     if (diff) atomicAdd(&moved, diff);

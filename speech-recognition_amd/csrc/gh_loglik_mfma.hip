@@ -30,6 +30,7 @@
 //     optionally driven by a block table that restricts every utterance to its own state range
 //     (gh_loglik_subset).
 #include "gh_internal.h"
+#include "gh_wave.h"
 
 namespace {
 
@@ -82,33 +83,6 @@ template <> struct Dom<double> {
 template <> struct Dom<float> {
     static constexpr float inv_k = (float)(1.0 / GH_LSE_SCALE32), off = GH_LSE_OFF32, off_test = GH_LSE_OFF32 * 0.1f;
 };
-
-// IEEE maxNum in ONE instruction (fmax() adds a v_max x,x canonicalisation per operand that comes
-// out of an MFMA); a NaN operand loses, two NaNs give NaN
-__device__ __forceinline__ double vmax(double a, double b) {
-    double r;
-    asm("v_max_f64 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
-    return r;
-}
-__device__ __forceinline__ float vmax(float a, float b) {
-    float r;
-    asm("v_max_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
-    return r;
-}
-
-// 2^(y/128) for finite y <= 0 (or NaN)
-__device__ __forceinline__ double exp2s(double y, const double* __restrict__ tab) {
-    const double n = __builtin_rint(y);
-    const double r = y - n;
-    const int ni = (int)n;  // v_cvt_i32_f64 saturates
-    const double t = tab[ni & 127];
-    double p = fma(r, 3.583032305400251285e-11, 2.6466421444330968834e-08);  // (ln2/128)^k / k!, k = 4, 3
-    p = fma(p, r, 1.4662262387640424337e-05);
-    p = fma(p, r, 5.4152123481245727298e-03);
-    p = p * r;  // 2^(r/128) - 1
-    return __builtin_ldexp(fma(t, p, t), ni >> 7);
-}
-__device__ __forceinline__ float exp2s(float y, const double*) { return __builtin_amdgcn_exp2f(y); }
 
 // K ln s for s in [1, M] (or NaN)
 __device__ __forceinline__ double logs(double s, const double* __restrict__ tab) {

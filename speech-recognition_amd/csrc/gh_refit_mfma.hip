@@ -32,6 +32,7 @@
 // (t / var * t, summed in order, np.argmin's first minimum) -- see km_exact().
 #include "gh_refit.h"
 #include "gh_host.h"
+#include "gh_wave.h"
 
 namespace {
 
@@ -40,29 +41,6 @@ constexpr double RF_LN_UNDERFLOW = -745.1332191019412;   // exp(x) rounds to +0 
 
 __device__ __forceinline__ double rf_mfma(double a, double b, double c) {
     return __builtin_amdgcn_mfma_f64_4x4x4f64(a, b, c, 0, 0, 0);
-}
-template <int CTRL> __device__ __forceinline__ double rf_dpp(double v) {
-    const int lo = __builtin_amdgcn_mov_dpp(__double2loint(v), CTRL, 0xF, 0xF, true);
-    const int hi = __builtin_amdgcn_mov_dpp(__double2hiint(v), CTRL, 0xF, 0xF, true);
-    return __hiloint2double(hi, lo);
-}
-template <int CTRL> __device__ __forceinline__ int rf_dpp(int v) { return __builtin_amdgcn_mov_dpp(v, CTRL, 0xF, 0xF, true); }
-__device__ __forceinline__ double rf_vmax(double a, double b) {   // one instruction; a NaN operand loses
-    double r;
-    asm("v_max_f64 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
-    return r;
-}
-// 2^(y/128) for y <= 0 (or NaN), as in gh_loglik_mfma.hip: table of 2^(j/128) + degree-4 polynomial
-__device__ __forceinline__ double rf_exp2s(double y, const double* __restrict__ tab) {
-    const double n = __builtin_rint(y);
-    const double r = y - n;
-    const int ni = (int)n;
-    const double t = tab[ni & 127];
-    double p = fma(r, 3.583032305400251285e-11, 2.6466421444330968834e-08);
-    p = fma(p, r, 1.4662262387640424337e-05);
-    p = fma(p, r, 5.4152123481245727298e-03);
-    p = p * r;
-    return __builtin_ldexp(fma(t, p, t), ni >> 7);
 }
 __device__ __forceinline__ double rf_rcp(double s) {              // 1 / s for s in [1, 32] (or NaN)
     double y = __builtin_amdgcn_rcp(s);
@@ -182,12 +160,6 @@ __device__ void rf_reduce_slabs(const double* __restrict__ partial, int plen, in
     }
 }
 
-__device__ __forceinline__ bool rf_close(double a, double b) {   // np.isclose(a, b), default tolerances
-    if (a == b) return true;
-    if (!(a - a == 0.0) || !(b - b == 0.0)) return false;
-    return fabs(a - b) <= 1e-8 + 1e-5 * fabs(b);
-}
-
 // =========================================================================================== mixture EM
 // operands of one state for the next pass, by the whole block: P[((cg 2 + h) KS + st) 16 + 4 j + kk] = coefficient of
 // component 4 cg + j at feature 4 st + kk, h = 0: of x^2 (-iv / 2), h = 1: of x (iv (mean - shift)), the constant
@@ -274,14 +246,14 @@ __device__ bool em_update_state(const rf_em_args& a, int s, int it, const double
         rf_publish(a.var + at, sg);
         if (n_l < 2) { mu_l[n_l] = mu; sg_l[n_l] = sg; }
         ++n_l;
-        mine += !rf_close(mu, a.old_mu[at]) + !rf_close(sg, a.old_sigma[at]);
+        mine += !np_isclose(mu, a.old_mu[at]) + !np_isclose(sg, a.old_sigma[at]);
     }
     if (tid < k) {
         const double w = st[tid * Wd] / a.nframes[s];
         diff += !same(w, a.weight[(int64_t)s * k + tid]);
         rf_publish(a.weight + (int64_t)s * k + tid, w);
         w_l = w;
-        mine += !rf_close(w, a.old_w[(int64_t)s * k + tid]);
+        mine += !np_isclose(w, a.old_w[(int64_t)s * k + tid]);
     }
     if (mine) atomicAdd(&lds_i[0], mine);
     if (diff) atomicAdd(&lds_i[1], diff);
@@ -402,21 +374,21 @@ __global__ __launch_bounds__(64 * RF_WAVES) __attribute__((amdgpu_waves_per_eu((
         // ---- responsibilities: the components of a frame sit in the CG registers of a quad of lanes ----
         double mx = -INFINITY;
 #pragma unroll
-        for (int cg = 0; cg < CG; ++cg) { l[cg] = aq[cg] + al[cg]; mx = rf_vmax(mx, l[cg]); }
-        mx = rf_vmax(mx, rf_dpp<0xB1>(mx));
-        mx = rf_vmax(mx, rf_dpp<0x4E>(mx));
+        for (int cg = 0; cg < CG; ++cg) { l[cg] = aq[cg] + al[cg]; mx = vmax(mx, l[cg]); }
+        mx = vmax(mx, dpp_mov<0xB1>(mx));
+        mx = vmax(mx, dpp_mov<0x4E>(mx));
         double sum = 0.0;
 #pragma unroll
         for (int cg = 0; cg < CG; ++cg) {
             // the reference's linear-domain densities: a product that underflows is exactly 0 (its exponent alone, or with
             // weight and normaliser)
             const bool dead = (l[cg] < thr) || (l[cg] - cst[cg] < thr);
-            const double e = rf_exp2s(l[cg] - mx, sT);
+            const double e = exp2s(l[cg] - mx, sT);
             l[cg] = dead ? 0.0 : e;
             sum += l[cg];
         }
-        sum += rf_dpp<0xB1>(sum);
-        sum += rf_dpp<0x4E>(sum);
+        sum += dpp_mov<0xB1>(sum);
+        sum += dpp_mov<0x4E>(sum);
         const double inv = (sum == 0.0) ? 0.0 : rf_rcp(sum);          // (a NaN stays a NaN)
 #pragma unroll
         for (int cg = 0; cg < CG; ++cg) l[cg] = act ? l[cg] * inv : 0.0;
@@ -683,7 +655,7 @@ __global__ __launch_bounds__(64 * RF_WAVES) __attribute__((amdgpu_waves_per_eu(K
             if (gq[cg] < best) { best = gq[cg]; bi = 4 * cg + lo; }
         }
 #define RF_AMIN(CTRL)                                                                  \
-        { const double ob = rf_dpp<CTRL>(best); const int oi = rf_dpp<CTRL>(bi);         \
+        { const double ob = dpp_mov<CTRL>(best); const int oi = dpp_mov<CTRL>(bi);         \
           if (ob < best || (ob == best && oi < bi)) { best = ob; bi = oi; } }
         RF_AMIN(0xB1) RF_AMIN(0x4E)
 #undef RF_AMIN
@@ -692,12 +664,12 @@ __global__ __launch_bounds__(64 * RF_WAVES) __attribute__((amdgpu_waves_per_eu(K
         int near = 0;
 #pragma unroll
         for (int cg = 0; cg < CG; ++cg) near += (4 * cg + lo < k) && (gq[cg] <= best + tau);
-        near += rf_dpp<0xB1>(near);
-        near += rf_dpp<0x4E>(near);
+        near += dpp_mov<0xB1>(near);
+        near += dpp_mov<0x4E>(near);
         const bool redo = (best > -INFINITY && near > 1) || !(xx - xx == 0.0) || !(best < INFINITY);
         if (__builtin_amdgcn_ballot_w64(redo) != 0ull) {              // rare: the reference's own operations decide
             if (redo && act && lo == 0) bi = km_exact(a.c.X + (f0 + my_frame) * D, cen, var, ld, k, D);
-            const int b0 = rf_dpp<0x00>(bi);                          // (lane j = 0 of the quad holds the answer)
+            const int b0 = dpp_mov<0x00>(bi);                          // (lane j = 0 of the quad holds the answer)
             if (redo) bi = b0;
         }
         if (act && lo == 0) {

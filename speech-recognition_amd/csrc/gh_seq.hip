@@ -12,38 +12,17 @@
 // utterance; forward-backward used the generic fb_kernel, 5 of 64 lanes busy.
 #include "gh_internal.h"
 #include "gh_viterbi.h"
+#include "gh_wave.h"
 #include "gh_fb.h"
 #include "gh_xnum.h"
 #include <cstring>
 
 namespace {
 
-__device__ __forceinline__ double sq_vmin(double a, double b) {
-    double r;
-    asm("v_min_f64 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
-    return r;
-}
-// lane i <- lane i-1 inside the 16-lane row; lane 0 of a row keeps `fill`
-__device__ __forceinline__ double row_shr1(double v, double fill) {
-    const int lo = __builtin_amdgcn_update_dpp(__double2loint(fill), __double2loint(v), 0x111, 0xF, 0xF, false);
-    const int hi = __builtin_amdgcn_update_dpp(__double2hiint(fill), __double2hiint(v), 0x111, 0xF, 0xF, false);
-    return __hiloint2double(hi, lo);
-}
-// lane i <- lane i+1 inside the row; lane 15 keeps `fill`
-__device__ __forceinline__ double row_shl1(double v, double fill) {
-    const int lo = __builtin_amdgcn_update_dpp(__double2loint(fill), __double2loint(v), 0x101, 0xF, 0xF, false);
-    const int hi = __builtin_amdgcn_update_dpp(__double2hiint(fill), __double2hiint(v), 0x101, 0xF, 0xF, false);
-    return __hiloint2double(hi, lo);
-}
-__device__ __forceinline__ void sq_push_bit(uint32_t& word, unsigned long long mask) {
-    unsigned long long carry_out;
-    asm("v_addc_co_u32 %0, %1, %2, %2, %3" : "=v"(word), "=s"(carry_out) : "v"(word), "s"(mask));
-}
-
 template <typename ET, int N, bool SKIP, bool WANT_BP>
 __global__ __launch_bounds__(64) void viterbi_seq_kernel(gh_layers_args a, int64_t slot_end) {
-    constexpr int HB = N + (SKIP ? N - 2 : 0);                // decision bits per column and lane (<= 30: N = 16 with skips)
-    constexpr int CPW = 32 / HB;
+    constexpr int HB = gh_seq_hb(N, SKIP);                      // decision bits per column and lane (<= 30: N = 16 with skips)
+    constexpr int CPW = gh_seq_cpw(N, SKIP);
     constexpr int PF = N > 8 ? 2 : 4;                          // columns of emissions in flight (12 / 16 states: the ring is registers)
     static_assert(HB < 32, "the decision bits of a column and lane live in one word");
     const int lane = threadIdx.x, kk = lane >> 4, k = lane & 15;
@@ -99,23 +78,23 @@ __global__ __launch_bounds__(64) void viterbi_seq_kernel(gh_layers_args a, int64
                     if (SKIP && s >= 2) {
                         const double v2 = c2[s] + prev[s - 2];
                         const bool b_a = v1 < v2;
-                        const double m = sq_vmin(v1, v2);
+                        const double m = vmin(v1, v2);
                         const bool b_b = v0 < m;
-                        best = sq_vmin(v0, m);
-                        if (WANT_BP) { sq_push_bit(word, __ballot(b_a)); sq_push_bit(word, __ballot(b_b)); }
+                        best = vmin(v0, m);
+                        if (WANT_BP) { push_bit(word, __ballot(b_a)); push_bit(word, __ballot(b_b)); }
                     } else {
                         const bool b = v0 < v1;
-                        best = sq_vmin(v0, v1);
-                        if (WANT_BP) sq_push_bit(word, __ballot(b));
+                        best = vmin(v0, v1);
+                        if (WANT_BP) push_bit(word, __ballot(b));
                     }
-                    prev[s] = sq_vmin(best + e[s], INF);
+                    prev[s] = vmin(best + e[s], INF);
                 }
                 // the non-emitting row behind this layer has one origin: hand it to the next lane (same column)
                 const double nin = row_shr1(prev[N - 1] + cout, (t == 0) ? 0.0 : INF);   // lane 0: the start row
                 const double cn = nin + cin;
                 const bool b0 = base0 < cn;                   // the non-emitting row (lower row index) wins ties
-                if (WANT_BP) sq_push_bit(word, __ballot(b0));
-                prev[0] = sq_vmin(sq_vmin(base0, cn) + e[0], INF);
+                if (WANT_BP) push_bit(word, __ballot(b0));
+                prev[0] = vmin(vmin(base0, cn) + e[0], INF);
                 if (WANT_BP) {
                     const int ci = t % CPW;
                     if (ci == CPW - 1 || t == T - 1) {
@@ -166,8 +145,8 @@ __global__ __launch_bounds__(64) void viterbi_seq_kernel(gh_layers_args a, int64
 // (layer bk, state bs) in column j; a lane keeps the decision word of its current (word index, layer) in a register.
 template <int N, bool SKIP>
 __global__ __launch_bounds__(64) void seq_backtrace_kernel(gh_layers_args a, int64_t slot_end) {
-    constexpr int HB = N + (SKIP ? N - 2 : 0);
-    constexpr int CPW = 32 / HB;
+    constexpr int HB = gh_seq_hb(N, SKIP);
+    constexpr int CPW = gh_seq_cpw(N, SKIP);
     const int64_t slot = a.slot0 + (int64_t)blockIdx.x * 64 + threadIdx.x;
     if (slot >= slot_end) return;
     const int64_t u = a.perm ? a.perm[slot] : slot;
@@ -250,13 +229,13 @@ __global__ __launch_bounds__(64) void seq_backtrace_kernel(gh_layers_args a, int
 __device__ __forceinline__ xnum xn_row_shr1(xnum v, xnum fill) {
     xnum o;
     o.f = row_shr1(v.f, fill.f);
-    o.e = __builtin_amdgcn_update_dpp(fill.e, v.e, 0x111, 0xF, 0xF, false);
+    o.e = dpp_upd<0x111>(fill.e, v.e);
     return o;
 }
 __device__ __forceinline__ xnum xn_row_shl1(xnum v, xnum fill) {
     xnum o;
     o.f = row_shl1(v.f, fill.f);
-    o.e = __builtin_amdgcn_update_dpp(fill.e, v.e, 0x101, 0xF, 0xF, false);
+    o.e = dpp_upd<0x101>(fill.e, v.e);
     return o;
 }
 
@@ -464,21 +443,11 @@ __global__ __launch_bounds__(64) void fb_seq_kernel(gh_fbseq_args a, int64_t slo
 // above), log P, gamma and xi are bit-identical to the lane = layer kernel's whenever a graph has one end row.
 // Also written: the frame range of every CELL with occupancy above the floor (row_lo / row_hi), which lets the fused
 // statistics kernel walk a state pair's own frames instead of its layer's.
-__device__ __forceinline__ double wave_shr1d(double v, double fill) {
-    const int lo = __builtin_amdgcn_update_dpp(__double2loint(fill), __double2loint(v), 0x138, 0xF, 0xF, false);
-    const int hi = __builtin_amdgcn_update_dpp(__double2hiint(fill), __double2hiint(v), 0x138, 0xF, 0xF, false);
-    return __hiloint2double(hi, lo);
-}
-__device__ __forceinline__ double wave_shl1d(double v, double fill) {
-    const int lo = __builtin_amdgcn_update_dpp(__double2loint(fill), __double2loint(v), 0x130, 0xF, 0xF, false);
-    const int hi = __builtin_amdgcn_update_dpp(__double2hiint(fill), __double2hiint(v), 0x130, 0xF, 0xF, false);
-    return __hiloint2double(hi, lo);
-}
 __device__ __forceinline__ xnum xn_wave_shr1(xnum v, xnum fill) {
-    return xnum{wave_shr1d(v.f, fill.f), __builtin_amdgcn_update_dpp(fill.e, v.e, 0x138, 0xF, 0xF, false)};
+    return xnum{wave_shr1(v.f, fill.f), dpp_upd<0x138>(fill.e, v.e)};
 }
 __device__ __forceinline__ xnum xn_wave_shl1(xnum v, xnum fill) {
-    return xnum{wave_shl1d(v.f, fill.f), __builtin_amdgcn_update_dpp(fill.e, v.e, 0x130, 0xF, 0xF, false)};
+    return xnum{wave_shl1(v.f, fill.f), dpp_upd<0x130>(fill.e, v.e)};
 }
 
 template <typename ET, int N, bool SKIP, bool OCC_LDS>
@@ -643,9 +612,7 @@ __global__ __launch_bounds__(64) void fb_seq_cell_kernel(gh_fbseq_args a) {
 }  // namespace
 
 size_t gh_seq_bp_entries(int N, int skip, int64_t T) {
-    const int hb = N + (skip ? N - 2 : 0);
-    const int cpw = 32 / hb;
-    return (size_t)((T + cpw - 1) / cpw) * 16 * 2;
+    return gh_bp_entries(T, gh_seq_cpw(N, skip), 16, 32);
 }
 
 int gh_launch_viterbi_seq(gh_ctx* ctx, const gh_layers_args& a, int N, int skip, int64_t u_begin, int64_t n_utts, bool f64,
@@ -660,19 +627,7 @@ int gh_launch_viterbi_seq(gh_ctx* ctx, const gh_layers_args& a, int N, int skip,
         if (want_path) hipLaunchKernelGGL((viterbi_seq_kernel<ET, NN, SK, true>), grid, blk, 0, ctx->stream, b, slot_end);  \
         else hipLaunchKernelGGL((viterbi_seq_kernel<ET, NN, SK, false>), grid, blk, 0, ctx->stream, b, slot_end);           \
     } while (0)
-#define GH_SQ_N(ET)                                                                          \
-    switch (N) {                                                                             \
-        case 2: GH_SQ(ET, 2, false); break;                                                  \
-        case 3: if (skip) GH_SQ(ET, 3, true); else GH_SQ(ET, 3, false); break;               \
-        case 4: if (skip) GH_SQ(ET, 4, true); else GH_SQ(ET, 4, false); break;               \
-        case 5: if (skip) GH_SQ(ET, 5, true); else GH_SQ(ET, 5, false); break;               \
-        case 6: if (skip) GH_SQ(ET, 6, true); else GH_SQ(ET, 6, false); break;               \
-        case 7: if (skip) GH_SQ(ET, 7, true); else GH_SQ(ET, 7, false); break;               \
-        case 8: if (skip) GH_SQ(ET, 8, true); else GH_SQ(ET, 8, false); break;               \
-        case 12: if (skip) GH_SQ(ET, 12, true); else GH_SQ(ET, 12, false); break;            \
-        case 16: if (skip) GH_SQ(ET, 16, true); else GH_SQ(ET, 16, false); break;            \
-        default: gh_set_error("gh_viterbi: sequence form with %d states per word", N); return GH_ERR_UNSUPPORTED; \
-    }
+#define GH_SQ_N(ET) GH_NSKIP_SWITCH(N, skip, 16, GH_SQ, ET, "gh_viterbi: sequence form with %d states per word", N)
     if (f64) { GH_SQ_N(double) } else { GH_SQ_N(float) }
 #undef GH_SQ_N
 #undef GH_SQ
@@ -686,19 +641,8 @@ int gh_launch_seq_backtrace(gh_ctx* ctx, const gh_layers_args& a, int N, int ski
     b.slot0 = u_begin;
     const dim3 grid((unsigned)((n_utts + 63) / 64)), blk(64);
     const int64_t slot_end = u_begin + n_utts;
-#define GH_SB(NN, SK) hipLaunchKernelGGL((seq_backtrace_kernel<NN, SK>), grid, blk, 0, ctx->stream, b, slot_end)
-    switch (N) {
-        case 2: GH_SB(2, false); break;
-        case 3: if (skip) GH_SB(3, true); else GH_SB(3, false); break;
-        case 4: if (skip) GH_SB(4, true); else GH_SB(4, false); break;
-        case 5: if (skip) GH_SB(5, true); else GH_SB(5, false); break;
-        case 6: if (skip) GH_SB(6, true); else GH_SB(6, false); break;
-        case 7: if (skip) GH_SB(7, true); else GH_SB(7, false); break;
-        case 8: if (skip) GH_SB(8, true); else GH_SB(8, false); break;
-        case 12: if (skip) GH_SB(12, true); else GH_SB(12, false); break;
-        case 16: if (skip) GH_SB(16, true); else GH_SB(16, false); break;
-        default: gh_set_error("gh_viterbi: sequence form with %d states per word", N); return GH_ERR_UNSUPPORTED;
-    }
+#define GH_SB(ET, NN, SK) hipLaunchKernelGGL((seq_backtrace_kernel<NN, SK>), grid, blk, 0, ctx->stream, b, slot_end)
+    GH_NSKIP_SWITCH(N, skip, 16, GH_SB, , "gh_viterbi: sequence form with %d states per word", N)
 #undef GH_SB
     GH_HIP(hipGetLastError());
     return GH_OK;
@@ -723,17 +667,7 @@ int gh_launch_fb_seq(gh_ctx* ctx, const gh_fbseq_args& a, int N, int skip, int64
         if (occ_lds) hipLaunchKernelGGL((fb_seq_cell_kernel<ET, NN, SK, true>), grid, blk, (size_t)a.S * 8, ctx->stream, b); \
         else hipLaunchKernelGGL((fb_seq_cell_kernel<ET, NN, SK, false>), grid, blk, 0, ctx->stream, b);                      \
     } while (0)
-#define GH_FC_N(ET)                                                                          \
-    switch (N) {                                                                             \
-        case 2: GH_FC(ET, 2, false); break;                                                  \
-        case 3: if (skip) GH_FC(ET, 3, true); else GH_FC(ET, 3, false); break;               \
-        case 4: if (skip) GH_FC(ET, 4, true); else GH_FC(ET, 4, false); break;               \
-        case 5: if (skip) GH_FC(ET, 5, true); else GH_FC(ET, 5, false); break;               \
-        case 6: if (skip) GH_FC(ET, 6, true); else GH_FC(ET, 6, false); break;               \
-        case 7: if (skip) GH_FC(ET, 7, true); else GH_FC(ET, 7, false); break;               \
-        case 8: if (skip) GH_FC(ET, 8, true); else GH_FC(ET, 8, false); break;               \
-        default: gh_set_error("gh_forward_backward: sequence form with %d states per word", N); return GH_ERR_UNSUPPORTED; \
-    }
+#define GH_FC_N(ET) GH_NSKIP_SWITCH(N, skip, 8, GH_FC, ET, "gh_forward_backward: sequence form with %d states per word", N)
         if (f64) { GH_FC_N(double) } else { GH_FC_N(float) }
 #undef GH_FC_N
 #undef GH_FC
@@ -749,17 +683,7 @@ int gh_launch_fb_seq(gh_ctx* ctx, const gh_fbseq_args& a, int N, int skip, int64
         if (occ_lds) hipLaunchKernelGGL((fb_seq_kernel<ET, NN, SK, true>), grid, blk, (size_t)4 * a.S * 8, ctx->stream, b, slot_end); \
         else hipLaunchKernelGGL((fb_seq_kernel<ET, NN, SK, false>), grid, blk, 0, ctx->stream, b, slot_end);                    \
     } while (0)
-#define GH_FS_N(ET)                                                                          \
-    switch (N) {                                                                             \
-        case 2: GH_FS(ET, 2, false); break;                                                  \
-        case 3: if (skip) GH_FS(ET, 3, true); else GH_FS(ET, 3, false); break;               \
-        case 4: if (skip) GH_FS(ET, 4, true); else GH_FS(ET, 4, false); break;               \
-        case 5: if (skip) GH_FS(ET, 5, true); else GH_FS(ET, 5, false); break;               \
-        case 6: if (skip) GH_FS(ET, 6, true); else GH_FS(ET, 6, false); break;               \
-        case 7: if (skip) GH_FS(ET, 7, true); else GH_FS(ET, 7, false); break;               \
-        case 8: if (skip) GH_FS(ET, 8, true); else GH_FS(ET, 8, false); break;               \
-        default: gh_set_error("gh_forward_backward: sequence form with %d states per word", N); return GH_ERR_UNSUPPORTED; \
-    }
+#define GH_FS_N(ET) GH_NSKIP_SWITCH(N, skip, 8, GH_FS, ET, "gh_forward_backward: sequence form with %d states per word", N)
     if (f64) { GH_FS_N(double) } else { GH_FS_N(float) }
 #undef GH_FS_N
 #undef GH_FS

@@ -2,6 +2,7 @@
 //   * k-means assignment  (reference: inner N x k loop of kmeans, kmeans.py:180-186)
 //   * mixture-EM E-step sufficient statistics (reference: GMM.em, hmm_state.py:127-143)
 #include "gh_internal.h"
+#include "gh_wave.h"
 #include <cstring>
 #include <cmath>
 
@@ -164,9 +165,6 @@ __global__ __launch_bounds__(256) void em_stats_kernel(const double* __restrict_
 // in a fixed order -- no float atomics.  Statistics are centred on the current means.
 constexpr int BW_MAXP = 8;  // (component, dimension) pairs per lane of bw_stats_kernel: M*(D+1) <= 8*256
 
-// workgroup barrier that orders LDS traffic only (no wait for outstanding global loads / store acknowledgements)
-__device__ __forceinline__ void bw_lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-
 // MF = accumulate on the matrix cores (needs M <= 8 and 2D + 1 <= 128): see the accumulation phase below.
 // MAXCT / MAXP bound the column tiles and the (component, dimension) pairs per lane at compile time (register arrays).
 template <bool MF, int MAXCT, int MAXP>
@@ -258,12 +256,12 @@ __global__ __launch_bounds__(256) void bw_stats_kernel(const double* __restrict_
             }
             if (tid < M) pc[tid] = logc[(int64_t)s * M + tid];
             if (MF) for (int i = tid; i < 8 * NCT * 16; i += 256) gt[i] = 0.0;
-            bw_lds_barrier();
+            lds_barrier();
             // component log-densities of every (frame, component) pair of the tile on all 256 lanes (the lanes of a
             // frame read the same feature row: LDS broadcast), four independent partial sums per pair; then one
             // lane per frame normalises over the components
             for (int f = tid; f < F; f += 256) wt[f] = (f < nf) ? occ[(n0 + f) * S + s] : 0.0;
-            bw_lds_barrier();
+            lds_barrier();
             if (MF) {
                 // densities AND the normalisation over the components in one phase: lane = (frame, component slot of
                 // 8); max / sum over the 8 slots by xor shuffles -- no intermediate LDS round trip, no second barrier
@@ -320,7 +318,7 @@ __global__ __launch_bounds__(256) void bw_stats_kernel(const double* __restrict_
                 }
                 rt[MF ? f * RS + m : m * F + f] = ll;
             }
-            bw_lds_barrier();
+            lds_barrier();
             if (tid < F) {
                 const int f = tid;
                 const double wgt = wt[f];
@@ -350,7 +348,7 @@ __global__ __launch_bounds__(256) void bw_stats_kernel(const double* __restrict_
                 }
             }
             }   // !MF
-            bw_lds_barrier();
+            lds_barrier();
             if (MF) {
                 // ---- accumulation on the matrix cores: G[m, c] = sum_f r[f, m] Z[f, c] with ONE operand for all
                 // components, Z[f] = [1 | x_f - c_s | (x_f - c_s)^2] centred on the state's first component mean
@@ -400,7 +398,7 @@ __global__ __launch_bounds__(256) void bw_stats_kernel(const double* __restrict_
                         }
                     }
                 }
-                bw_lds_barrier();
+                lds_barrier();
 #pragma unroll
                 for (int h = 0; h < MAXP; ++h) {
                     const int p = tid + 256 * h;
@@ -416,7 +414,7 @@ __global__ __launch_bounds__(256) void bw_stats_kernel(const double* __restrict_
                         o[1 + D + d] = so2[h] + (g2 - dl * (2.0 * g1 - dl * s0));
                     }
                 }
-                bw_lds_barrier();
+                lds_barrier();
                 continue;
             }
 #pragma unroll
@@ -441,7 +439,7 @@ __global__ __launch_bounds__(256) void bw_stats_kernel(const double* __restrict_
                 if (d == D) o[0] = so1[h] + a1;
                 else { o[1 + d] = so1[h] + a1; o[1 + D + d] = so2[h] + a2; }
             }
-            bw_lds_barrier();  // rt / pm are rewritten by the next state (the slab stores stay in flight)
+            lds_barrier();  // rt / pm are rewritten by the next state (the slab stores stay in flight)
         }
     }
 }

@@ -148,3 +148,60 @@ size_t gh_bigram_bp_entries(const gh_layerform& f, int64_t T);
 int gh_launch_viterbi_bigram(gh_ctx* ctx, const gh_layers_args& a, const gh_layerform& f, int64_t u_begin, int64_t n_utts,
                              bool f64, bool want_path);
 int gh_launch_bigram_backtrace(gh_ctx* ctx, const gh_layers_args& a, const gh_layerform& f, int64_t u_begin, int64_t n_utts);
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Decision-word layout of the register forms above, ONE definition for the sweep that writes the words, the back-trace that
+// reads them and the host function that sizes the scratch: decision bits per column and lane (layer forms: and register
+// set / layer) for words of N states, and the columns that share one decision word.
+constexpr int gh_layer_hb(int N, bool skip) { return N + 1 + (skip ? N - 2 : 0); }    // layer form, narrow and wide
+constexpr int gh_loop_hb(int N, bool skip) { return N + 2 + (skip ? N - 2 : 0); }     // loop form, narrow and wide
+constexpr int gh_bigram_hb(int N, bool skip) { return N + 5 + (skip ? N - 2 : 0); }   // in-word bits, 4 bits of predecessor word, 2 bits of state 0
+constexpr int gh_seq_hb(int N, bool skip) { return N + (skip ? N - 2 : 0); }
+// layer form: `sets` register sets (2: up to 8 layers, 4: up to 16) share a word, 64 bits wide when 32 do not hold them
+constexpr int gh_layer_word_bits(int N, bool skip, int sets) { return sets * gh_layer_hb(N, skip) > 32 ? 64 : 32; }
+constexpr int gh_layer_cpw(int N, bool skip, int sets) { return gh_layer_word_bits(N, skip, sets) / (sets * gh_layer_hb(N, skip)); }
+constexpr int gh_loop_cpw(int N, bool skip) { return 32 / gh_loop_hb(N, skip); }
+constexpr int gh_bigram_cpw(int N, bool skip) { return 32 / gh_bigram_hb(N, skip); }
+constexpr int gh_seq_cpw(int N, bool skip) { return 32 / gh_seq_hb(N, skip); }
+// back-pointer scratch of T frames in uint16 units (the lattice kernels' common unit): `lanes` words per cpw columns
+constexpr size_t gh_bp_entries(int64_t T, int cpw, int lanes, int word_bits) {
+    return (size_t)((T + cpw - 1) / cpw) * lanes * (word_bits / 16);
+}
+
+// columns per word for N = 2 .. 8, 12, 16 without and with skip arcs (0: not built; a two-state word has no skip arc)
+namespace gh_layout_check {
+constexpr int NS[9] = {2, 3, 4, 5, 6, 7, 8, 12, 16};
+template <typename F> constexpr bool same(F cpw, const int (&plain)[9], const int (&skip)[9]) {
+    for (int i = 0; i < 9; ++i)
+        if ((plain[i] && cpw(NS[i], false) != plain[i]) || (skip[i] && cpw(NS[i], true) != skip[i])) return false;
+    return true;
+}
+static_assert(same([](int N, bool s) { return gh_layer_cpw(N, s, 2); }, {5, 4, 3, 2, 2, 2, 1, 1, 1}, {5, 3, 2, 1, 1, 1, 1, 1, 1}), "layer form, two sets");
+static_assert(same([](int N, bool s) { return gh_layer_cpw(N, s, 4); }, {2, 2, 1, 1, 1, 1, 1, 0, 0}, {2, 1, 1, 1, 1, 1, 1, 0, 0}), "layer form, four sets");
+static_assert(same(gh_loop_cpw, {8, 6, 5, 4, 4, 3, 3, 2, 1}, {8, 5, 4, 3, 2, 2, 2, 1, 1}), "loop form");
+static_assert(same(gh_bigram_cpw, {4, 4, 3, 3, 2, 2, 2, 1, 1}, {4, 3, 2, 2, 2, 1, 1, 1, 0}), "bigram form");
+static_assert(same(gh_seq_cpw, {16, 10, 8, 6, 5, 4, 4, 2, 2}, {16, 8, 5, 4, 3, 2, 2, 1, 1}), "sequence form");
+static_assert(gh_layer_word_bits(16, false, 2) == 64 && gh_layer_word_bits(12, false, 2) == 32 && gh_layer_word_bits(8, true, 2) == 32 &&
+              gh_layer_word_bits(12, true, 2) == 64 && gh_layer_word_bits(7, false, 4) == 32 && gh_layer_word_bits(8, false, 4) == 64 &&
+              gh_layer_word_bits(4, true, 4) == 32 && gh_layer_word_bits(5, true, 4) == 64, "layer form: where the words turn 64 bits wide");
+static_assert(4 * gh_layer_hb(8, true) <= 64 && gh_loop_hb(8, true) <= 32, "wide forms: one word per column (and four layers)");
+static_assert(gh_bigram_hb(16, true) > 32, "bigram form: 16 states with skip arcs do not fit a word");
+}  // namespace gh_layout_check
+
+// ---------------------------------------------------------------------------------------------------------------------
+// The one switch over states per word x skip arcs that picks a template instantiation: CALL(ET, N, SKIP) is a statement,
+// ET is handed through untouched, MAXN names the word sizes a form is built for -- 8; 16 (also 12 and 16); 16_NO_SKIP16
+// (the same without 16 states with skip arcs).  Anything else sets the error text (printf arguments) and returns
+// GH_ERR_UNSUPPORTED from the calling function.
+#define GH_NSKIP_CASE(NN, skip, CALL, ET) case NN: if (skip) CALL(ET, NN, true); else CALL(ET, NN, false); break;
+#define GH_NSKIP_FROM_12_8(skip, CALL, ET)
+#define GH_NSKIP_FROM_12_16(skip, CALL, ET) GH_NSKIP_CASE(12, skip, CALL, ET) GH_NSKIP_CASE(16, skip, CALL, ET)
+#define GH_NSKIP_FROM_12_16_NO_SKIP16(skip, CALL, ET) GH_NSKIP_CASE(12, skip, CALL, ET) case 16: if (!(skip)) { CALL(ET, 16, false); break; }
+#define GH_NSKIP_SWITCH(n, skip, MAXN, CALL, ET, ...)                                     \
+    switch (n) {                                                                          \
+        case 2: CALL(ET, 2, false); break;                                                \
+        GH_NSKIP_CASE(3, skip, CALL, ET) GH_NSKIP_CASE(4, skip, CALL, ET) GH_NSKIP_CASE(5, skip, CALL, ET) \
+        GH_NSKIP_CASE(6, skip, CALL, ET) GH_NSKIP_CASE(7, skip, CALL, ET) GH_NSKIP_CASE(8, skip, CALL, ET) \
+        GH_NSKIP_FROM_12_##MAXN(skip, CALL, ET)                                           \
+        default: gh_set_error(__VA_ARGS__); return GH_ERR_UNSUPPORTED;                    \
+    }

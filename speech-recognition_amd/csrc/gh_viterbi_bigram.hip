@@ -13,7 +13,7 @@
 //     control gfx90a+ has for 64-bit operands too), v = 0 .. 15 IN ASCENDING ORDER.  Ascending v is ascending origin
 //     row, so a strict '<' between neighbours of a reduction tree whose left operand is always the lower v is the
 //     reference's first minimum; no (value, v) pair has to be compared, as a reduction over row ROTATIONS would need
-//     (there lane w meets v = w, w+1, .., 15, 0, .., w-1).  16 broadcast + add, then 15 x (compare, v_min_f64, select v);
+//     (there lane w meets v = w, w+1, .., 15, 0, .., w-1).  16 broadcast + add, then 15 x (compare, vmin, select v);
 //   * the arg-min v (4 bits) is shifted into the lane's decision word behind the in-word decision bits of the column:
 //     N + 5 (+ N - 2 with skip arcs) bits per column and lane -- ONE stream of wider records at fewer columns per
 //     32-bit word (N = 5: 3 columns instead of the loop form's 4) rather than a second stream of nibbles: the forward
@@ -26,31 +26,12 @@
 // left to the row-per-lane kernels).  No scratch in the column loop for any of them (kernel-resource-usage remarks).
 #include "gh_internal.h"
 #include "gh_viterbi.h"
+#include "gh_wave.h"
 
 namespace {
 
-__device__ __forceinline__ double vmin(double a, double b) {   // IEEE minNum in ONE instruction: a NaN operand loses
-    double r;
-    asm("v_min_f64 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
-    return r;
-}
-
-// the value of lane V of every 16-lane DPP row, in all lanes of that row
-template <int V> __device__ __forceinline__ double row_lane(double v) {
-    const int lo = __builtin_amdgcn_mov_dpp(__double2loint(v), 0x150 + V, 0xF, 0xF, true);
-    const int hi = __builtin_amdgcn_mov_dpp(__double2hiint(v), 0x150 + V, 0xF, 0xF, true);
-    return __hiloint2double(hi, lo);
-}
-
-// word = 2 * word + bit, the bit taken from a compare's lane mask: one VALU instruction
-__device__ __forceinline__ void push_bit(uint32_t& word, unsigned long long mask) {
-    unsigned long long carry_out;
-    asm("v_addc_co_u32 %0, %1, %2, %2, %3" : "=v"(word), "=s"(carry_out) : "v"(word), "s"(mask));
-}
-
 template <int N, bool SKIP> struct BigramBits {
-    static constexpr int HB = N + 5 + (SKIP ? N - 2 : 0);     // in-word bits, 4 bits of predecessor word, 2 bits of state 0
-    static constexpr int CPW = 32 / HB;
+    static constexpr int HB = gh_bigram_hb(N, SKIP), CPW = gh_bigram_cpw(N, SKIP);
     static_assert(CPW >= 1, "the decision bits of a column must fit one word");
 };
 
@@ -317,24 +298,11 @@ bool gh_bigram_n_ok(int N, int skip) { return gh_seq_n_ok(N) && !(N == 16 && ski
 
 // back-pointer scratch of one utterance of T frames, in uint16 units (the lattice kernels' common unit)
 size_t gh_bigram_bp_entries(const gh_layerform& f, int64_t T) {
-    const int hb = f.N + 5 + (f.skip ? f.N - 2 : 0);
-    const int cpw = 32 / hb;
-    return (size_t)((T + cpw - 1) / cpw) * 16 * 2;
+    return gh_bp_entries(T, gh_bigram_cpw(f.N, f.skip), 16, 32);
 }
 
-#define GH_BG_CASES(ET, MACRO)                   \
-    switch (f.N) {                               \
-        case 2: MACRO(ET, 2, false); break;      \
-        case 3: if (f.skip) MACRO(ET, 3, true); else MACRO(ET, 3, false); break; \
-        case 4: if (f.skip) MACRO(ET, 4, true); else MACRO(ET, 4, false); break; \
-        case 5: if (f.skip) MACRO(ET, 5, true); else MACRO(ET, 5, false); break; \
-        case 6: if (f.skip) MACRO(ET, 6, true); else MACRO(ET, 6, false); break; \
-        case 7: if (f.skip) MACRO(ET, 7, true); else MACRO(ET, 7, false); break; \
-        case 8: if (f.skip) MACRO(ET, 8, true); else MACRO(ET, 8, false); break; \
-        case 12: if (f.skip) MACRO(ET, 12, true); else MACRO(ET, 12, false); break; \
-        case 16: if (!f.skip) { MACRO(ET, 16, false); break; }                     \
-        default: gh_set_error("gh_viterbi: bigram form with %d states per word (skip arcs: %d)", f.N, f.skip); return GH_ERR_UNSUPPORTED; \
-    }
+#define GH_BG_CASES(ET, MACRO) \
+    GH_NSKIP_SWITCH(f.N, f.skip, 16_NO_SKIP16, MACRO, ET, "gh_viterbi: bigram form with %d states per word (skip arcs: %d)", f.N, f.skip)
 
 int gh_launch_viterbi_bigram(gh_ctx* ctx, const gh_layers_args& a, const gh_layerform& f, int64_t u_begin, int64_t n_utts,
                              bool f64, bool want_path) {

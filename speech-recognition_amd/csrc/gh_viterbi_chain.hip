@@ -12,17 +12,11 @@
 // likelihood matrix.  Back-pointers are 1 byte per cell (which of the three arcs won).
 #include "gh_internal.h"
 #include "gh_viterbi.h"
+#include "gh_wave.h"
 
 namespace {
 
 constexpr int PF = 8;  // emission prefetch depth (columns)
-
-// lane i <- lane i-1 (lane 0 keeps `fill`)
-__device__ __forceinline__ double wave_shr1(double v, double fill) {
-    const int lo = __builtin_amdgcn_update_dpp(__double2loint(fill), __double2loint(v), 0x138, 0xF, 0xF, false);
-    const int hi = __builtin_amdgcn_update_dpp(__double2hiint(fill), __double2hiint(v), 0x138, 0xF, 0xF, false);
-    return __hiloint2double(hi, lo);
-}
 
 template <typename ET, bool WANT_BP, bool WANT_COSTS, bool SKIP>
 __global__ __launch_bounds__(64) void viterbi_chain_kernel(gh_chain_args a) {

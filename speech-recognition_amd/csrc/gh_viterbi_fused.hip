@@ -22,6 +22,7 @@
 // (rocprofv3: SQ_ACTIVE_INST_VALU = 94 % of a SIMD's cycles) -- not by HBM; bench.py reports both fractions.
 #include "gh_internal.h"
 #include "gh_viterbi.h"
+#include "gh_wave.h"
 #include <type_traits>
 
 namespace {
@@ -30,19 +31,9 @@ constexpr int FT = 32;  // frames per LDS tile
 
 __device__ __forceinline__ double fma_(double a, double b, double c) { return __builtin_fma(a, b, c); }
 __device__ __forceinline__ float fma_(float a, float b, float c) { return __builtin_fmaf(a, b, c); }
-// IEEE minNum in ONE instruction: a NaN operand loses (fmin() adds canonicalising v_max x,x around it)
-__device__ __forceinline__ double vmin(double a, double b) {
-    double r;
-    asm("v_min_f64 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
-    return r;
-}
 // lane i <- lane i-1, lane 0 <- +0.0 (bound_ctrl): the first row of a lane group starts a chain, its r-1 / r-2 arcs cost
 // +inf, and +inf + 0 is still +inf -- no fill registers
-__device__ __forceinline__ double wave_shr1z(double v) {
-    const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(v), 0x138, 0xF, 0xF, true);
-    const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(v), 0x138, 0xF, 0xF, true);
-    return __hiloint2double(hi, lo);
-}
+__device__ __forceinline__ double wave_shr1z(double v) { return dpp_upd<0x138, 0xF, true>(0.0, v); }
 
 // sqrt(1/(2 var)), -mean sqrt(1/(2 var)), -logc and the underflow threshold of every lattice row, k-major ([2 DVp + 2][Rp])
 // so that a wave's loads are contiguous.  Rows >= R repeat row 0 (never active).

@@ -19,7 +19,7 @@
 //     the column depends on it (words have >= 2 states), so the layers of a column are independent instruction
 //     streams for the scheduler;
 //   * back-pointers are decision BITS (self arc strictly better?), shifted into one 32-bit word per lane with
-//     v_addc_co_u32 straight from the compare's SGPR mask: 2 (N + 1) bits per column and lane, 128 B per column for
+//     push_bit straight from the compare's SGPR mask: 2 (N + 1) bits per column and lane, 128 B per column for
 //     N = 5 against 716 B of uint16 back-pointers per column in the row-per-lane kernel;
 //   * each lane streams the N emissions of its word from the resident [N, S] matrix (saddr + per-lane byte offset,
 //     PF columns in flight);
@@ -29,27 +29,9 @@
 // barriers, ~5 900 cycles per column).
 #include "gh_internal.h"
 #include "gh_viterbi.h"
+#include "gh_wave.h"
 
 namespace {
-
-__device__ __forceinline__ double vmin(double a, double b) {   // IEEE minNum in ONE instruction: a NaN operand loses
-    double r;
-    asm("v_min_f64 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
-    return r;
-}
-
-template <int CTRL, int ROW_MASK> __device__ __forceinline__ double dpp_f64(double old, double v) {
-    const int lo = __builtin_amdgcn_update_dpp(__double2loint(old), __double2loint(v), CTRL, ROW_MASK, 0xF, false);
-    const int hi = __builtin_amdgcn_update_dpp(__double2hiint(old), __double2hiint(v), CTRL, ROW_MASK, 0xF, false);
-    return __hiloint2double(hi, lo);
-}
-
-// rotation inside the 16-lane rows: every lane has a source, so no `old` value has to be set up (v_mov_b32_dpp only)
-template <int CTRL> __device__ __forceinline__ double row_rot(double v) {
-    const int lo = __builtin_amdgcn_mov_dpp(__double2loint(v), CTRL, 0xF, 0xF, true);
-    const int hi = __builtin_amdgcn_mov_dpp(__double2hiint(v), CTRL, 0xF, 0xF, true);
-    return __hiloint2double(hi, lo);
-}
 
 // minimum over the 16 lanes of a DPP row, left in every lane of the row (row_ror:1,2,4,8)
 __device__ __forceinline__ double row_min16(double v) {
@@ -60,29 +42,14 @@ __device__ __forceinline__ double row_min16(double v) {
     return v;
 }
 
-// word = 2 * word + bit, the bit taken from a compare's lane mask: one VALU instruction
-__device__ __forceinline__ void push_bit(uint32_t& word, unsigned long long mask) {
-    unsigned long long carry_out;
-    asm("v_addc_co_u32 %0, %1, %2, %2, %3" : "=v"(word), "=s"(carry_out) : "v"(word), "s"(mask));
-}
-
-// ... and for the 64-bit decision words of the wide word models (12 / 16 states): the carry of the low half goes on
-__device__ __forceinline__ void push_bit(uint64_t& word, unsigned long long mask) {
-    uint32_t lo = (uint32_t)word, hi = (uint32_t)(word >> 32);
-    unsigned long long c1, c2;
-    asm("v_addc_co_u32 %0, %1, %2, %2, %3" : "=v"(lo), "=s"(c1) : "v"(lo), "s"(mask));
-    asm("v_addc_co_u32 %0, %1, %2, %2, %3" : "=v"(hi), "=s"(c2) : "v"(hi), "s"(c1));
-    word = ((uint64_t)hi << 32) | lo;
-}
-
 // decision bits of one column and lane in the layer form: H register sets (2: up to 8 layers, 4: up to 16) of N + 1 (+ N - 2
 // with skip arcs); two sets fit a 32-bit word up to 8 states per word (and 12 without skip arcs), a 64-bit word up to 16;
 // four sets fit 64 bits up to 8 states per word
 template <int N, bool SKIP, int H = 2> struct LayerBits {
-    static constexpr int HB = N + 1 + (SKIP ? N - 2 : 0);
+    static constexpr int HB = gh_layer_hb(N, SKIP);
     static constexpr int BITS = H * HB;
-    static constexpr bool WIDE = BITS > 32;
-    static constexpr int CPW = (WIDE ? 64 : 32) / BITS;
+    static constexpr bool WIDE = gh_layer_word_bits(N, SKIP, H) == 64;
+    static constexpr int CPW = gh_layer_cpw(N, SKIP, H);
     static_assert(BITS <= 64, "the decision bits of a column must fit one word");
 };
 template <bool WIDE> struct DecisionWord { using type = uint32_t; };
@@ -188,7 +155,7 @@ __global__ __launch_bounds__(64) void viterbi_layers_kernel(gh_layers_args a) {
             const double rm = row_min16(cand);
             if (WANT_BP) push_bit(word, __ballot(cand == rm));
             // ... handed to the next layer: rows 1-3 take the row above, row 0 the start row / layer 3
-            const double nin = dpp_f64<0x142, 0xE>(carry, rm);
+            const double nin = dpp_upd<0x142, 0xE>(carry, rm);
             carry = __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(rm), 63),
                                      __builtin_amdgcn_readlane(__double2loint(rm), 63));
             // state 0: the non-emitting row (lower row index: it wins ties) against the self arc
@@ -259,8 +226,8 @@ __global__ __launch_bounds__(64) void viterbi_layers_kernel(gh_layers_args a) {
 // bits: N + 2 (+ N - 2 with skip arcs) per column and lane, 16 lanes x 4 B per CPW columns and utterance.
 // The back-trace is a second kernel (lattice_backtrace_kernel, one lane per utterance).
 template <int N, bool SKIP> struct LoopBits {
-    static constexpr int HB = N + 2 + (SKIP ? N - 2 : 0);
-    static constexpr int CPW = 32 / HB;
+    static constexpr int HB = gh_loop_hb(N, SKIP);
+    static constexpr int CPW = gh_loop_cpw(N, SKIP);
 };
 
 template <typename ET, int N, bool SKIP, bool WANT_BP>
@@ -407,7 +374,7 @@ __global__ __launch_bounds__(64) void lattice_backtrace_kernel(gh_layers_args a,
     constexpr int BITS = LOOP ? HB : H * HB;
     constexpr bool WIDE = !LOOP && LayerBits<N, SKIP, H>::WIDE;  // 64-bit decision words (viterbi_layers_kernel)
     using WT = typename DecisionWord<WIDE>::type;
-    constexpr int CPW = (WIDE ? 64 : 32) / BITS;
+    constexpr int CPW = LOOP ? LoopBits<N, SKIP>::CPW : LayerBits<N, SKIP, H>::CPW;
     constexpr int LPW = LOOP ? 16 : 64;                       // decision words per word index
     __shared__ uint8_t s_arcs[GH_LAYERS_MAXW * GH_LAYERS_MAXN];
     const gh_layerform* __restrict__ lf = a.lf;
@@ -556,30 +523,12 @@ __global__ __launch_bounds__(64) void lattice_backtrace_kernel(gh_layers_args a,
 // back-pointer scratch of one utterance of T frames, in uint16 units (the lattice kernels' common unit)
 size_t gh_layers_bp_entries(const gh_layerform& f, int64_t T) {
     if (f.W > GH_LAYERS_ROWW) return f.loop ? gh_loop_wide_bp_entries(T) : gh_layers_wide_bp_entries(T);
-    if (f.loop) {
-        const int hb = f.N + 2 + (f.skip ? f.N - 2 : 0);
-        const int cpw = 32 / hb;
-        return (size_t)((T + cpw - 1) / cpw) * 16 * 2;
-    }
-    const int hb = f.N + 1 + (f.skip ? f.N - 2 : 0), sets = f.K > 8 ? 4 : 2;
-    const int wbits = sets * hb > 32 ? 64 : 32;               // (LayerBits)
-    const int cpw = wbits / (sets * hb);
-    return (size_t)((T + cpw - 1) / cpw) * 64 * (wbits / 16);
+    if (f.loop) return gh_bp_entries(T, gh_loop_cpw(f.N, f.skip), 16, 32);
+    const int sets = f.K > 8 ? 4 : 2;
+    return gh_bp_entries(T, gh_layer_cpw(f.N, f.skip, sets), 64, gh_layer_word_bits(f.N, f.skip, sets));
 }
 
-#define GH_LY_CASES(ET, MACRO)                   \
-    switch (f.N) {                               \
-        case 2: MACRO(ET, 2, false); break;      \
-        case 3: if (f.skip) MACRO(ET, 3, true); else MACRO(ET, 3, false); break; \
-        case 4: if (f.skip) MACRO(ET, 4, true); else MACRO(ET, 4, false); break; \
-        case 5: if (f.skip) MACRO(ET, 5, true); else MACRO(ET, 5, false); break; \
-        case 6: if (f.skip) MACRO(ET, 6, true); else MACRO(ET, 6, false); break; \
-        case 7: if (f.skip) MACRO(ET, 7, true); else MACRO(ET, 7, false); break; \
-        case 8: if (f.skip) MACRO(ET, 8, true); else MACRO(ET, 8, false); break; \
-        case 12: if (f.skip) MACRO(ET, 12, true); else MACRO(ET, 12, false); break; \
-        case 16: if (f.skip) MACRO(ET, 16, true); else MACRO(ET, 16, false); break; \
-        default: gh_set_error("gh_viterbi: layer form with %d states per word", f.N); return GH_ERR_UNSUPPORTED; \
-    }
+#define GH_LY_CASES(ET, MACRO) GH_NSKIP_SWITCH(f.N, f.skip, 16, MACRO, ET, "gh_viterbi: layer form with %d states per word", f.N)
 
 int gh_launch_viterbi_layers(gh_ctx* ctx, const gh_layers_args& a, const gh_layerform& f, int64_t u_begin, int64_t n_utts,
                              bool f64, bool want_path) {

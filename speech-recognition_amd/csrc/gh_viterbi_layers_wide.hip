@@ -17,20 +17,9 @@
 // The back-trace is its own kernel (one lane per utterance, as lattice_backtrace_kernel).
 #include "gh_internal.h"
 #include "gh_viterbi.h"
+#include "gh_wave.h"
 
 namespace {
-
-__device__ __forceinline__ double vmin(double a, double b) {   // IEEE minNum in ONE instruction: a NaN operand loses
-    double r;
-    asm("v_min_f64 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
-    return r;
-}
-
-template <int CTRL> __device__ __forceinline__ double row_rot(double v) {
-    const int lo = __builtin_amdgcn_mov_dpp(__double2loint(v), CTRL, 0xF, 0xF, true);
-    const int hi = __builtin_amdgcn_mov_dpp(__double2hiint(v), CTRL, 0xF, 0xF, true);
-    return __hiloint2double(hi, lo);
-}
 
 // minimum over the 64 lanes, left in every lane: inside the 16-lane rows by row_ror:1,2,4,8, across them through the scalar unit
 __device__ __forceinline__ double wave_min(double v) {
@@ -42,21 +31,12 @@ __device__ __forceinline__ double wave_min(double v) {
     return vmin(vmin(at(0), at(16)), vmin(at(32), at(48)));
 }
 
-// word = 2 * word + bit, the bit taken from a compare's lane mask (two v_addc_co_u32: the low half's carry goes on)
-__device__ __forceinline__ void push_bit(uint64_t& word, unsigned long long mask) {
-    uint32_t lo = (uint32_t)word, hi = (uint32_t)(word >> 32);
-    unsigned long long c1, c2;
-    asm("v_addc_co_u32 %0, %1, %2, %2, %3" : "=v"(lo), "=s"(c1) : "v"(lo), "s"(mask));
-    asm("v_addc_co_u32 %0, %1, %2, %2, %3" : "=v"(hi), "=s"(c2) : "v"(hi), "s"(c1));
-    word = ((uint64_t)hi << 32) | lo;
-}
-
 constexpr int WL_SETS = 2;                 // sets of four layers: K <= 8
 
 template <typename ET, int N, bool SKIP, bool WANT_BP>
 __global__ __launch_bounds__(64) void viterbi_layers_wide_kernel(gh_layers_args a) {
     constexpr int KM = 4 * WL_SETS;
-    constexpr int HB = N + 1 + (SKIP ? N - 2 : 0);            // decision bits per column, lane and layer
+    constexpr int HB = gh_layer_hb(N, SKIP);                  // decision bits per column, lane and layer
     constexpr int PF = 2;                                     // columns of emissions in flight
     static_assert(4 * HB <= 64, "four layers' decision bits share a 64-bit word");
     const int lane = threadIdx.x, w = lane;
@@ -195,7 +175,7 @@ __global__ __launch_bounds__(64) void viterbi_layers_wide_kernel(gh_layers_args 
 // layer bk's bits sit (3 - (bk & 3)) HB bits up.  MODE 0: the (row, column) path; MODE 1: only the label sequence.
 template <int N, bool SKIP, int MODE>
 __global__ __launch_bounds__(64) void lattice_backtrace_wide_kernel(gh_layers_args a, int64_t slot_end) {
-    constexpr int HB = N + 1 + (SKIP ? N - 2 : 0);
+    constexpr int HB = gh_layer_hb(N, SKIP);
     __shared__ uint8_t s_arcs[GH_LAYERS_MAXW * GH_LAYERS_MAXN];
     const gh_layerform* __restrict__ lf = a.lf;
     for (int i = threadIdx.x; i < GH_LAYERS_MAXW * GH_LAYERS_MAXN; i += 64) s_arcs[i] = (&lf->arcs[0][0])[i];
@@ -347,10 +327,6 @@ __global__ __launch_bounds__(64) void viterbi_loop_wide_kernel(gh_layers_args a)
     for (int s = 0; s < N; ++s) prev[s] = INF;
     uint32_t* bp = WANT_BP ? reinterpret_cast<uint32_t*>(a.bp + a.bp_off[slot]) + lane : nullptr;
     __builtin_amdgcn_s_waitcnt(0x0F70);
-    auto push32 = [](uint32_t& word, unsigned long long mask) {
-        unsigned long long carry_out;
-        asm("v_addc_co_u32 %0, %1, %2, %2, %3" : "=v"(word), "=s"(carry_out) : "v"(word), "s"(mask));
-    };
     auto column = [&](int t, const ET (&ev)[N]) {
         double e[N];
 #pragma unroll
@@ -368,25 +344,25 @@ __global__ __launch_bounds__(64) void viterbi_loop_wide_kernel(gh_layers_args a)
                 const double m = vmin(v1, v2);
                 const bool b_b = v0 < m;
                 best = vmin(v0, m);
-                if (WANT_BP) { push32(word, __ballot(b_a)); push32(word, __ballot(b_b)); }
+                if (WANT_BP) { push_bit(word, __ballot(b_a)); push_bit(word, __ballot(b_b)); }
             } else {
                 const bool b = v0 < v1;
                 best = vmin(v0, v1);
-                if (WANT_BP) push32(word, __ballot(b));
+                if (WANT_BP) push_bit(word, __ballot(b));
             }
             prev[s] = vmin(best + e[s], INF);
         }
         // the loop row: minimum over the words' last states of THIS column
         const double cand = prev[N - 1] + cout;
         const double rm = wave_min(cand);
-        if (WANT_BP) push32(word, __ballot(cand == rm));
+        if (WANT_BP) push_bit(word, __ballot(cand == rm));
         // state 0: start row (row 0), loop row, self -- ascending origin, strict '<'
         const double cs = ((t == 0) ? 0.0 : INF) + cin0;
         const double cl = rm + cin;
         const bool b_l = cl < cs;
         const double m2 = vmin(cl, cs);
         const bool b_s = base0 < m2;
-        if (WANT_BP) { push32(word, __ballot(b_l)); push32(word, __ballot(b_s)); }
+        if (WANT_BP) { push_bit(word, __ballot(b_l)); push_bit(word, __ballot(b_s)); }
         prev[0] = vmin(vmin(base0, m2) + e[0], INF);
         if (WANT_BP) bp[(int64_t)t * 64] = word;
     };
@@ -432,7 +408,7 @@ __global__ __launch_bounds__(64) void viterbi_loop_wide_kernel(gh_layers_args a)
 // its back-trace: one lane per utterance, the decision word of (column j, word bw) is bpu[j 64 + bw]
 template <int N, bool SKIP, int MODE>
 __global__ __launch_bounds__(64) void loop_backtrace_wide_kernel(gh_layers_args a, int64_t slot_end) {
-    constexpr int HB = N + 2 + (SKIP ? N - 2 : 0);
+    constexpr int HB = gh_loop_hb(N, SKIP);
     __shared__ uint8_t s_arcs[GH_LAYERS_MAXW * GH_LAYERS_MAXN];
     const gh_layerform* __restrict__ lf = a.lf;
     for (int i = threadIdx.x; i < GH_LAYERS_MAXW * GH_LAYERS_MAXN; i += 64) s_arcs[i] = (&lf->arcs[0][0])[i];
@@ -537,21 +513,11 @@ __global__ __launch_bounds__(64) void loop_backtrace_wide_kernel(gh_layers_args 
 }  // namespace
 
 // decision words of one utterance of T frames in uint16 units: two 64-bit words per column and lane
-size_t gh_layers_wide_bp_entries(int64_t T) { return (size_t)T * WL_SETS * 64 * 4; }
+size_t gh_layers_wide_bp_entries(int64_t T) { return gh_bp_entries(T, 1, WL_SETS * 64, 64); }
 // ... wide loop form: one 32-bit word per column and lane
-size_t gh_loop_wide_bp_entries(int64_t T) { return (size_t)T * 64 * 2; }
+size_t gh_loop_wide_bp_entries(int64_t T) { return gh_bp_entries(T, 1, 64, 32); }
 
-#define GH_LW_CASES(MACRO)                       \
-    switch (f.N) {                               \
-        case 2: MACRO(2, false); break;          \
-        case 3: if (f.skip) MACRO(3, true); else MACRO(3, false); break; \
-        case 4: if (f.skip) MACRO(4, true); else MACRO(4, false); break; \
-        case 5: if (f.skip) MACRO(5, true); else MACRO(5, false); break; \
-        case 6: if (f.skip) MACRO(6, true); else MACRO(6, false); break; \
-        case 7: if (f.skip) MACRO(7, true); else MACRO(7, false); break; \
-        case 8: if (f.skip) MACRO(8, true); else MACRO(8, false); break; \
-        default: gh_set_error("gh_viterbi: wide layer form with %d states per word", f.N); return GH_ERR_UNSUPPORTED; \
-    }
+#define GH_LW_CASES(MACRO) GH_NSKIP_SWITCH(f.N, f.skip, 8, MACRO, , "gh_viterbi: wide layer form with %d states per word", f.N)
 
 int gh_launch_viterbi_layers_wide(gh_ctx* ctx, const gh_layers_args& a, const gh_layerform& f, int64_t u_begin, int64_t n_utts,
                                   bool f64, bool want_path) {
@@ -560,7 +526,7 @@ int gh_launch_viterbi_layers_wide(gh_ctx* ctx, const gh_layers_args& a, const gh
     b.slot0 = u_begin;
     const dim3 grid((unsigned)n_utts), blk(64);
     if (f.loop) {
-#define GH_LPW(NN, SK)                                                                                                      \
+#define GH_LPW(ET, NN, SK)                                                                                                      \
     do {                                                                                                                    \
         if (f64) {                                                                                                          \
             if (want_path) hipLaunchKernelGGL((viterbi_loop_wide_kernel<double, NN, SK, true>), grid, blk, 0, ctx->stream, b);    \
@@ -576,7 +542,7 @@ int gh_launch_viterbi_layers_wide(gh_ctx* ctx, const gh_layers_args& a, const gh
         return GH_OK;
     }
     if (f.K > 4 * WL_SETS) { gh_set_error("gh_viterbi: wide layer form with %d layers", f.K); return GH_ERR_UNSUPPORTED; }
-#define GH_LW(NN, SK)                                                                                                       \
+#define GH_LW(ET, NN, SK)                                                                                                       \
     do {                                                                                                                    \
         if (f64) {                                                                                                          \
             if (want_path) hipLaunchKernelGGL((viterbi_layers_wide_kernel<double, NN, SK, true>), grid, blk, 0, ctx->stream, b);  \
@@ -599,7 +565,7 @@ int gh_launch_lattice_backtrace_wide(gh_ctx* ctx, const gh_layers_args& a, const
     const dim3 grid((unsigned)((n_utts + 63) / 64)), blk(64);
     const int64_t slot_end = u_begin + n_utts;
     const bool labels = a.labels != nullptr;
-#define GH_BW(NN, SK)                                                                                                       \
+#define GH_BW(ET, NN, SK)                                                                                                       \
     do {                                                                                                                    \
         if (f.loop) {                                                                                                       \
             if (labels) hipLaunchKernelGGL((loop_backtrace_wide_kernel<NN, SK, 1>), grid, blk, 0, ctx->stream, b, slot_end); \

@@ -15,6 +15,7 @@
 //   * back-pointer stores use running per-level pointers; the back-trace is buffered in LDS.
 #include "gh_internal.h"
 #include "gh_viterbi.h"
+#include "gh_wave.h"
 #include <type_traits>
 
 namespace {
@@ -26,14 +27,8 @@ __device__ __forceinline__ double& lds_at(char* smem, unsigned off) { return *re
 
 // lane i <- lane i+K of the same 16-lane row (rows do not wrap: lanes past the end keep their value)
 template <int K> __device__ __forceinline__ int row_shl(int v) {
-    return __builtin_amdgcn_update_dpp(v, v, 0x100 | K, 0xF, 0xF, false);
+    return dpp_upd<0x100 | K>(v, v);
 }
-// Workgroup barrier that orders LDS traffic only (__syncthreads() also waits for every outstanding GLOBAL
-// access, vmcnt(0) -- the emission prefetch and the back-pointer flush should stay in flight across it).
-__device__ __forceinline__ void lds_barrier() {
-    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-}
-
 template <int K> __device__ __forceinline__ void min_step(double& best, int& idx) {
     const int lo = row_shl<K>(__double2loint(best)), hi = row_shl<K>(__double2hiint(best));
     const int oi = row_shl<K>(idx);
