@@ -170,6 +170,54 @@ int gh_batch_create_from_pcm(gh_ctx* ctx, gh_dtype dtype, int mode, int sample_f
                              double frame_stride, double low_freq, double high_freq, int64_t U, const void* samples,
                              const int64_t* sample_off, const int64_t* frame_off, gh_batch** out);
 
+/* Endpoint detection in front of the MFCC front-end: what AudioRecorder.record_callback (sr/audio_capture/record.py:
+ * 116-174) computes when it is fed whole chunks of `width` samples, for U int16 recordings at once.
+ * gh_endpoint_params holds the DERIVED config of AudioRecorder.__init__ (:78-88): width = 'samples per frame', stride =
+ * 'frame stride' in samples (1 <= stride <= width), speech_frames / silence_frames = the two thresholds in frames,
+ * forget / adjustment / onset / offset as they are.  A recording of C = len / width whole chunks has
+ * gh_endpoint_frames = 1 + (width / stride)(C - 1) frames (0 when C = 0), frame i = samples [i stride, i stride + width)
+ * (:132-147); frame 0 is never classified and keeps energy 0.  Energy = calc_energy (:23-31): 0 if the exact integer sum of
+ * squares is <= 1, else 10 log10(sum).  Every frame i >= 1 goes through classify_frame (:176-217) and the counters
+ * (:152-169) in fp64 in the reference's order of operations; speech_frames < consecutive speech frames while not started
+ * opens a segment at start = i stride, silence_frames < consecutive silence frames while started closes it at
+ * end = i stride + width.  max_segments = 1 is the reference (classification stops at the first end); with more the
+ * detector re-arms after an end with every piece of state left as it is and stops at the cap.
+ * samples: the recordings back to back, sample_off[U+1] (empty recordings are valid).  Out: start / end [U, max_segments]
+ * (0 where there is no segment), n_segments[U], open[U] = 1 when speech started and never ended (that segment counts, its
+ * end is the recording's last sample), frames_done[U] (may be NULL) = frames the classifier went through, the one at
+ * which it stopped included.  Optional per-frame outputs (all four or none), addressed by frame_off[U+1] built from
+ * gh_endpoint_frames: the frames' is_speech ATTRIBUTE (:205-211), level after the clamp (:202-203), background,
+ * energy; zero for frames behind the one at which detection stopped.  Recordings travel through the context's
+ * scratch in chunks bounded by the scratch budget (gh_ctx_last_chunks).
+ * Limit of the energy kernel: with Q = the widest of 8, 4, 2, 1 that divides gcd(width, stride), a frame is summed from
+ * width / Q units held in LDS and width / Q must not exceed 1280 (e.g. up to 10 240 samples per frame when the gcd is a
+ * multiple of 8, 1280 when it is odd); beyond that the call returns GH_ERR_UNSUPPORTED before anything is uploaded.
+ * A wave handles FT = 64 frames when their ((FT - 1) stride + width) / Q units fit 10 KB of LDS (1280 units), else 32,
+ * 16, ... 1: e.g. an odd gcd with stride + width > 1280 runs one frame per wave, correct and slow.
+ * gh_batch_create_from_pcm_endpointed = gh_batch_create_from_pcm on the recordings cut down to their segments, one
+ * utterance per segment in recording order, each the slice of get_samples (:243-248): [max(start - start_boundary, 0),
+ * end + 1) clipped to the recording; a recording without a segment stays whole.  One upload: endpoint kernels, the
+ * indices come back (start / end / n_segments / open as above), the frame table is built on the host, and the MFCC
+ * kernel reads the trimmed ranges of the samples already on the device.  sample_fmt must be 0 (int16).
+ * utt_frame_off [U * max_segments + 1] receives the frame offsets of the batch's utterances (the table the batch was
+ * built with), *n_utt their number. */
+typedef struct gh_endpoint_params {
+    int32_t width, stride, speech_frames, silence_frames;
+    double forget, adjustment, onset, offset;
+} gh_endpoint_params;
+int64_t gh_endpoint_frames(int64_t n_samples, int width, int stride);
+int gh_endpoints(gh_ctx* ctx, int64_t U, const int16_t* samples, const int64_t* sample_off /*[U+1]*/,
+                 const gh_endpoint_params* prm, int max_segments, int64_t* start /*[U, max_segments]*/,
+                 int64_t* end /*[U, max_segments]*/, int32_t* n_segments /*[U]*/, uint8_t* open /*[U]*/,
+                 int64_t* frames_done /*[U] or NULL*/, const int64_t* frame_off /*[U+1] or NULL*/, uint8_t* out_is_speech,
+                 double* out_level, double* out_background, double* out_energy);
+int gh_batch_create_from_pcm_endpointed(gh_ctx* ctx, gh_dtype dtype, int mode, int sample_fmt, int sample_rate,
+                                        double frame_size, double frame_stride, double low_freq, double high_freq, int64_t U,
+                                        const void* samples, const int64_t* sample_off, const gh_endpoint_params* prm,
+                                        int start_boundary, int max_segments, int64_t* start, int64_t* end,
+                                        int32_t* n_segments, uint8_t* open, int64_t* utt_frame_off, int64_t* n_utt,
+                                        gh_batch** out);
+
 /* ------------------------------------------------ A3: batched GMM.evaluate
  * nll[n, s] = -log sum_m w[s,m] N(x_n; mean[s,m], diag var[s,m])  for every
  * frame of the batch and every state (hmm_state.py:114-120, log-domain).

@@ -24,7 +24,9 @@ EXTRA = {"gh_loglik_mfma.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"],
          "gh_bw_fused.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"],
          # multiply-adds contracted per source expression, not across statements after optimisation: the ordinary and the TAIL
          # instantiation of a refit kernel then round alike (hipcc's default, fast, left them 1e-15 apart)
-         "gh_refit_mfma.hip": ["-ffp-contract=on"]}
+         "gh_refit_mfma.hip": ["-ffp-contract=on"],
+         # no contraction at all: the endpoint classifier rounds every product and sum like the reference's numpy scalars
+         "gh_endpoint.hip": ["-ffp-contract=off"]}
 
 
 def _sources():

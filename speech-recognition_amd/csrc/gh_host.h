@@ -105,3 +105,10 @@ int gh_batch_from_device_cepstra(gh_ctx* ctx, gh_dtype dtype, int mode, int C, i
                                  const int64_t* utt_offsets, size_t extra_scratch, void** extra,
                                  const std::function<hipError_t(double*, hipStream_t)>& fill, const char* who,
                                  gh_batch** out);
+
+// gh_endpoint.hip: gh_endpoints on recordings already on the device (d_pcm, indexed by sample_off) or, with d_pcm null,
+// on host samples that travel chunk by chunk through the context's scratch; the outputs are host arrays
+int gh_endpoints_run(gh_ctx* ctx, const int16_t* d_pcm, const int16_t* samples, int64_t U, const int64_t* sample_off,
+                     const gh_endpoint_params* prm, int max_segments, int64_t* start, int64_t* end, int32_t* n_segments,
+                     uint8_t* open, int64_t* frames_done, const int64_t* frame_off, uint8_t* out_is_speech,
+                     double* out_level, double* out_background, double* out_energy);

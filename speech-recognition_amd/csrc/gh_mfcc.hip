@@ -26,7 +26,8 @@ struct MfccTables {           // device pointers into one scratch block
 
 struct MfccArgs {
     const void* pcm; int fmt;
-    const int64_t* s_off; const int64_t* f_off; const int32_t* f_utt;
+    const int64_t* s_beg; const int64_t* s_end;   // first sample of every utterance in `pcm`, one past its last
+    const int64_t* f_off; const int32_t* f_utt;
     int64_t U, N;
     int flen, fstep, pad_left;
     MfccTables t;
@@ -84,8 +85,8 @@ __global__ __launch_bounds__(256) void mfcc_kernel(MfccArgs a) {
         live[h] = n < a.N;
         if (live[h]) {
             const int u = a.f_utt[n];          // utterance of this frame (host-built table)
-            sbase[h] = a.s_off[u];
-            slen[h] = a.s_off[u + 1] - sbase[h];
+            sbase[h] = a.s_beg[u];
+            slen[h] = a.s_end[u] - sbase[h];
             s0[h] = (n - a.f_off[u]) * a.fstep;
         }
     }
@@ -323,14 +324,17 @@ int check_inputs(const char* who, int fmt, int64_t U, const void* samples, const
 }
 
 // carve the inputs + tables out of one block, upload, return the kernel arguments
-size_t table_bytes(int fmt, int64_t n_samples, int64_t U, int64_t N) {
+// (resident: the samples are on the device already and the utterances are ranges of them -- the endpointed entry)
+size_t table_bytes(int fmt, int64_t n_samples, int64_t U, int64_t N, bool resident = false) {
     auto al = [](size_t b) { return (b + 255) & ~size_t(255); };
-    return al((size_t)n_samples * fmt_size(fmt)) + 2 * al((size_t)(U + 1) * 8) + al((size_t)N * 4) + al(NFFT * 8) + al(2 * NFFT * 8) +
-           2 * al(NBIN * 8) + al((NFILT + 2) * 4) + al((size_t)NCEPS * NFILT * 8);
+    return (resident ? 0 : al((size_t)n_samples * fmt_size(fmt))) + 2 * al((size_t)(U + 1) * 8) + (resident ? al((size_t)(U + 1) * 8) : 0) +
+           al((size_t)N * 4) + al(NFFT * 8) + al(2 * NFFT * 8) + 2 * al(NBIN * 8) + al((NFILT + 2) * 4) + al((size_t)NCEPS * NFILT * 8);
 }
 
+// samples + s_off [U+1]: utterances back to back, uploaded here; or d_pcm + s_off / s_end [U]: ranges of resident samples
 hipError_t upload_inputs(char* base, hipStream_t st, int fmt, int64_t U, const void* samples, const int64_t* s_off,
-                         const int64_t* f_off, const HostTables& h, MfccArgs& a) {
+                         const int64_t* f_off, const HostTables& h, MfccArgs& a, const void* d_pcm = nullptr,
+                         const int64_t* s_end = nullptr) {
     auto al = [](size_t b) { return (b + 255) & ~size_t(255); };
     char* p = base;
     hipError_t e = hipSuccess;
@@ -340,8 +344,15 @@ hipError_t upload_inputs(char* base, hipStream_t st, int fmt, int64_t U, const v
         p += al(bytes);
         return dst;
     };
-    a.pcm = put(samples, (size_t)s_off[U] * fmt_size(fmt));
-    a.s_off = (const int64_t*)put(s_off, (size_t)(U + 1) * 8);
+    if (d_pcm) {
+        a.pcm = d_pcm;
+        a.s_beg = (const int64_t*)put(s_off, (size_t)(U + 1) * 8);
+        a.s_end = (const int64_t*)put(s_end, (size_t)(U + 1) * 8);
+    } else {
+        a.pcm = put(samples, (size_t)s_off[U] * fmt_size(fmt));
+        a.s_beg = (const int64_t*)put(s_off, (size_t)(U + 1) * 8);
+        a.s_end = a.s_beg + 1;
+    }
     a.f_off = (const int64_t*)put(f_off, (size_t)(U + 1) * 8);
     a.f_utt = (const int32_t*)put(h.f_utt.data(), h.f_utt.size() * 4);
     a.t.window = (const double*)put(h.window.data(), NFFT * 8);
@@ -417,4 +428,71 @@ extern "C" int gh_batch_create_from_pcm(gh_ctx* ctx, gh_dtype dtype, int mode, i
             return hipGetLastError();
         },
         "gh_batch_create_from_pcm", out);
+}
+
+extern "C" int gh_batch_create_from_pcm_endpointed(gh_ctx* ctx, gh_dtype dtype, int mode, int sample_fmt, int sample_rate,
+                                                   double frame_size, double frame_stride, double low_freq, double high_freq,
+                                                   int64_t U, const void* samples, const int64_t* sample_off,
+                                                   const gh_endpoint_params* prm, int start_boundary, int max_segments,
+                                                   int64_t* start, int64_t* end, int32_t* n_segments, uint8_t* open,
+                                                   int64_t* utt_frame_off, int64_t* n_utt, gh_batch** out) {
+    const char* who = "gh_batch_create_from_pcm_endpointed";
+    GH_REQUIRE(ctx && out && prm && sample_off && start && end && n_segments && open && utt_frame_off && n_utt, "%s: NULL argument", who);
+    GH_REQUIRE(sample_fmt == 0, "%s: sample_fmt=%d (endpoint detection reads int16)", who, sample_fmt);
+    GH_REQUIRE(U >= 0 && sample_off[0] == 0 && start_boundary >= 0 && max_segments >= 1, "%s: U=%lld start_boundary=%d max_segments=%d",
+               who, (long long)U, start_boundary, max_segments);
+    HostTables h;
+    int rc = build_tables(sample_rate, frame_size, frame_stride, low_freq, high_freq, h);
+    if (rc) return rc;
+    for (int64_t u = 0; u < U; ++u)
+        GH_REQUIRE(sample_off[u + 1] >= sample_off[u], "%s: sample_off decreases at recording %lld", who, (long long)u);
+    GH_REQUIRE(samples || sample_off[U] == 0, "%s: samples is NULL", who);
+    GH_HIP(hipSetDevice(ctx->device));
+    // the samples stay in an allocation of their own: the context's scratch is carved anew by both halves
+    void* d_pcm = nullptr;
+    GH_HIP(hipMalloc(&d_pcm, (size_t)sample_off[U] * 2 + 256));
+    struct guard { void* p; ~guard() { (void)hipFree(p); } } free_pcm{d_pcm};
+    if (sample_off[U]) GH_HIP(hipMemcpyAsync(d_pcm, samples, (size_t)sample_off[U] * 2, hipMemcpyHostToDevice, ctx->stream));
+    rc = gh_endpoints_run(ctx, static_cast<const int16_t*>(d_pcm), nullptr, U, sample_off, prm, max_segments, start, end, n_segments,
+                          open, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
+    if (rc) return rc;
+    if (U == 0) GH_HIP(hipStreamSynchronize(ctx->stream));
+    // one utterance per segment, the slice of get_samples (record.py:243-248); a recording without a segment stays whole
+    std::vector<int64_t> s_beg, s_end, f_off{0};
+    for (int64_t u = 0; u < U; ++u) {
+        const int64_t len = sample_off[u + 1] - sample_off[u];
+        const int k = n_segments[u];
+        GH_REQUIRE(k >= 0 && k <= max_segments, "%s: recording %lld came back with %d segments", who, (long long)u, k);
+        for (int s = 0; s < (k > 0 ? k : 1); ++s) {
+            int64_t b = 0, e = len;
+            if (k > 0) {
+                b = std::max<int64_t>(start[u * max_segments + s] - start_boundary, 0);
+                e = std::min<int64_t>(end[u * max_segments + s] + 1, len);
+            }
+            GH_REQUIRE(e - b >= 1, "%s: recording %lld is empty (the reference reads signal[0])", who, (long long)u);
+            s_beg.push_back(sample_off[u] + b);
+            s_end.push_back(sample_off[u] + e);
+            f_off.push_back(f_off.back() + (e - b + h.fstep - 1) / h.fstep);
+        }
+    }
+    const int64_t U2 = (int64_t)s_beg.size(), N = f_off.back();
+    *n_utt = U2;                                   // (U2 <= U * max_segments: the caller's table has room)
+    memcpy(utt_frame_off, f_off.data(), (size_t)(U2 + 1) * 8);
+    s_beg.push_back(0);       // (both tables travel with U2 + 1 entries)
+    s_end.push_back(0);
+    h.f_utt.resize((size_t)N);
+    for (int64_t u = 0; u < U2; ++u) std::fill(h.f_utt.begin() + f_off[u], h.f_utt.begin() + f_off[u + 1], (int32_t)u);
+    void* extra = nullptr;
+    return gh_batch_from_device_cepstra(
+        ctx, dtype, mode, NCEPS, N, U2, f_off.data(), table_bytes(0, 0, U2, N, true), &extra,
+        [&](double* d_ceps, hipStream_t st) {
+            MfccArgs a;
+            hipError_t e = upload_inputs(static_cast<char*>(extra), st, 0, U2, nullptr, s_beg.data(), f_off.data(), h, a, d_pcm, s_end.data());
+            if (e != hipSuccess) return e;
+            a.out_fb = nullptr;
+            a.out_mfcc = d_ceps;
+            launch_mfcc(a, N, st);
+            return hipGetLastError();
+        },
+        who, out);
 }

@@ -1,0 +1,4 @@
+# -*- coding: utf-8 -*-
+"""`sr.audio_capture` -- the reference's recorder (sr/audio_capture/record.py) with its endpoint detection on the GPU,
+for whole batches of recordings.  Imports without `pyaudio`; only the live microphone loop needs it."""
+from .record import *  # noqa: F401,F403

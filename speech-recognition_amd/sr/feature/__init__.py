@@ -39,9 +39,26 @@ def mfcc_features(path_file, frame_size=0.025, frame_stride=0.01, low_freq=80, h
     return fb[0], mf[0]
 
 
-def features_from_signals(signals, sample_rate=16000, dtype=np.float64, device=None, **mfcc_kw):
+def features_from_signals(signals, sample_rate=16000, dtype=np.float64, device=None, endpoints=None, max_segments=1, **mfcc_kw):
     """Audio in, resident 39-dimensional batch out: MFCC -> [ceps | delta | delta-delta] -> standardize,
-    all on the device; returns the `_hip.Batch` ready for `loglik` / decoding."""
+    all on the device; returns the `_hip.Batch` ready for `loglik` / decoding.
+
+    endpoints: an AudioRecorder config (sr.audio_capture; True: the reference's default config at `sample_rate`) -- the
+    1-D int16 recordings are first cut down to their speech on the device (`detect_endpoints`, up to `max_segments`
+    segments each, every one trimmed like `get_samples`; a recording without a segment stays whole) and the batch holds
+    one utterance per segment in recording order.  `batch.endpoints` is the result of `detect_endpoints` plus
+    `recording` [batch.U], the recording of every utterance.  The samples are uploaded once and do not come back; only
+    the per-recording indices do.  A dict whose 'sample rate' differs from `sample_rate` is a ValueError."""
     prm = (mfcc_kw.get("frame_size", 0.025), mfcc_kw.get("frame_stride", 0.01), mfcc_kw.get("low_freq", 80),
            mfcc_kw.get("high_freq"))
-    return _hip.Batch(_hip.default_context(device), pcm=signals, sample_rate=sample_rate, mfcc_params=prm, dtype=dtype)
+    if endpoints is None or endpoints is False:
+        return _hip.Batch(_hip.default_context(device), pcm=signals, sample_rate=sample_rate, mfcc_params=prm, dtype=dtype)
+    from ..audio_capture.record import _check_signals, _derived      # (`sr.audio_capture.record` the name is the function)
+    cfg = _derived(None if endpoints is True else endpoints, sample_rate)
+    if cfg['sample rate'] != sample_rate:
+        raise ValueError("the endpoint config is for %r Hz, the signals are at %r Hz" % (cfg['sample rate'], sample_rate))
+    if int(max_segments) < 1:
+        raise ValueError("max_segments = %r" % (max_segments,))
+    sigs = _check_signals(signals)
+    return _hip.Batch(_hip.default_context(device), pcm=sigs, sample_rate=sample_rate, mfcc_params=prm, dtype=dtype,
+                      endpoints=cfg, max_segments=int(max_segments))

@@ -23,6 +23,14 @@ GH_ERR_COMM = -7
 _c_i32p = C.POINTER(C.c_int32)
 _c_i64p = C.POINTER(C.c_int64)
 _c_f64p = C.POINTER(C.c_double)
+_c_u8p = C.POINTER(C.c_uint8)
+
+
+class EndpointParams(C.Structure):
+    """gh_endpoint_params: the derived config of AudioRecorder.__init__ (record.py:78-88)."""
+    _fields_ = [("width", C.c_int32), ("stride", C.c_int32), ("speech_frames", C.c_int32), ("silence_frames", C.c_int32),
+                ("forget", C.c_double), ("adjustment", C.c_double), ("onset", C.c_double), ("offset", C.c_double)]
+
 
 # name -> (restype, argtypes); mirrors include/gmmhmm.h one to one
 SIGNATURES = {
@@ -66,6 +74,13 @@ SIGNATURES = {
     "gh_batch_create_from_pcm": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double,
                                            C.c_double, C.c_double, C.c_int64, C.c_void_p, _c_i64p, _c_i64p,
                                            C.POINTER(C.c_void_p)]),
+    "gh_endpoint_frames": (C.c_int64, [C.c_int64, C.c_int, C.c_int]),
+    "gh_endpoints": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, _c_i64p, C.POINTER(EndpointParams), C.c_int, _c_i64p, _c_i64p,
+                               _c_i32p, _c_u8p, _c_i64p, _c_i64p, _c_u8p, _c_f64p, _c_f64p, _c_f64p]),
+    "gh_batch_create_from_pcm_endpointed": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double,
+                                                      C.c_double, C.c_double, C.c_int64, C.c_void_p, _c_i64p,
+                                                      C.POINTER(EndpointParams), C.c_int, C.c_int, _c_i64p, _c_i64p, _c_i32p,
+                                                      _c_u8p, _c_i64p, _c_i64p, C.POINTER(C.c_void_p)]),
     "gh_loglik": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "gh_loglik_sets": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, _c_i64p, _c_i32p, _c_i32p]),
     "gh_loglik_subset": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, _c_i32p, _c_i32p]),
@@ -637,6 +652,80 @@ def mfcc(ctx, signals, sample_rate=16000, mfcc_params=None):
     return ([fb[f_off[u]:f_off[u + 1]] for u in range(U)], [mf[f_off[u]:f_off[u + 1]] for u in range(U)])
 
 
+def endpoint_params(cfg):
+    """EndpointParams from a DERIVED AudioRecorder config (record.py:78-88: widths and thresholds in samples / frames)."""
+    return EndpointParams(int(cfg['samples per frame']), int(cfg['frame stride']), int(cfg['speech threshold']),
+                          int(cfg['silence threshold']), float(cfg['forget factor']), float(cfg['adjustment']),
+                          float(cfg['onset threshold']), float(cfg['offset threshold']))
+
+
+def pack_recordings(signals):
+    """int16 recordings back to back for gh_endpoints: (samples, sample_off)."""
+    s_off = np.zeros(len(signals) + 1, dtype=np.int64)
+    np.cumsum([len(x) for x in signals], out=s_off[1:])
+    samples = np.ascontiguousarray(np.concatenate(signals)) if len(signals) else np.zeros(0, dtype=np.int16)
+    assert samples.dtype == np.int16
+    return samples, s_off
+
+
+def _endpoint_outputs(U, max_segments):
+    return (np.zeros((U, max_segments), dtype=np.int64), np.zeros((U, max_segments), dtype=np.int64),
+            np.zeros(U, dtype=np.int32), np.zeros(U, dtype=np.uint8))
+
+
+def _endpoint_result(start, end, nseg, is_open):
+    return dict(start=start, end=end, n_segments=nseg.astype(np.int64), open=is_open.astype(bool))
+
+
+def endpoints(ctx, signals, cfg, max_segments=1, want_frames=False):
+    """gh_endpoints for a list of 1-D int16 arrays and a DERIVED config: the batched record_callback (record.py:116-174).
+    Returns a dict: start / end [U, max_segments], n_segments [U], open [U], frames_done [U] and, with want_frames, the
+    ragged per-frame is_speech / level / background / energy (lists of arrays) with their frame_off."""
+    samples, s_off = pack_recordings(signals)
+    U = len(signals)
+    prm = endpoint_params(cfg)
+    start, end, nseg, is_open = _endpoint_outputs(U, max_segments)
+    done = np.zeros(U, dtype=np.int64)
+    f_off = attr = level = bg = energy = None
+    if want_frames:
+        f_off = np.zeros(U + 1, dtype=np.int64)
+        np.cumsum([ctx.lib.gh_endpoint_frames(len(x), prm.width, prm.stride) for x in signals], out=f_off[1:])
+        N = int(f_off[-1])
+        attr, level, bg, energy = np.zeros(N, dtype=np.uint8), np.zeros(N), np.zeros(N), np.zeros(N)
+    _check(ctx.lib, ctx.lib.gh_endpoints(ctx.h, U, samples.ctypes.data_as(C.c_void_p), _ptr(s_off, _c_i64p), C.byref(prm),
+                                         int(max_segments), _ptr(start, _c_i64p), _ptr(end, _c_i64p), _ptr(nseg, _c_i32p),
+                                         _ptr(is_open, _c_u8p), _ptr(done, _c_i64p), _ptr(f_off, _c_i64p), _ptr(attr, _c_u8p),
+                                         _ptr(level, _c_f64p), _ptr(bg, _c_f64p), _ptr(energy, _c_f64p)))
+    r = _endpoint_result(start, end, nseg, is_open)
+    r["frames_done"] = done
+    if want_frames:
+        cut = lambda a: [a[f_off[u]:f_off[u + 1]] for u in range(U)]
+        r.update(frame_off=f_off, is_speech=cut(attr.astype(bool)), level=cut(level), background=cut(bg), energy=cut(energy))
+    return r
+
+
+def trim_ranges(result, lengths, start_boundary):
+    """(begin, stop, recording) of every utterance the endpointed front-end cuts: per segment the slice of get_samples
+    (record.py:243-248), [max(start - start_boundary, 0), end + 1) clipped to the recording; an open segment runs to the
+    end of the recording; a recording without a segment stays whole."""
+    lengths = np.asarray(lengths, dtype=np.int64)
+    nseg = np.asarray(result["n_segments"], dtype=np.int64)
+    U = len(lengths)
+    per = np.maximum(nseg, 1)
+    rec = np.repeat(np.arange(U, dtype=np.int64), per)
+    first = np.concatenate([[0], np.cumsum(per)[:-1]]) if U else np.zeros(0, dtype=np.int64)
+    seg = np.arange(len(rec), dtype=np.int64) - first[rec]
+    has = nseg[rec] > 0
+    cols = np.minimum(seg, np.asarray(result["start"]).shape[1] - 1)
+    start = np.asarray(result["start"], dtype=np.int64)[rec, cols]
+    end = np.asarray(result["end"], dtype=np.int64)[rec, cols]
+    begin = np.where(has, np.maximum(start - int(start_boundary), 0), 0)
+    stop = np.where(has, np.minimum(end + 1, lengths[rec]), lengths[rec])
+    is_open = np.asarray(result["open"], dtype=bool)[rec] & (seg == nseg[rec] - 1)
+    stop = np.where(is_open, lengths[rec], stop)
+    return begin, stop, rec
+
+
 def concat_rows(arrays, out):
     """np.concatenate(arrays, out=out) for the caller's templates: C-contiguous float64 arrays go through the threaded copy of
     `_hostcopy` (csrc/hostcopy.c: GMMHMM_HOST_THREADS threads, the GIL released; 62 MB in 2 000 pieces: 5.7 -> ~1.5 ms), anything
@@ -664,7 +753,8 @@ class Batch:
     """Ragged batch of utterances resident in HBM (gh_batch)."""
 
     def __init__(self, ctx, utterances=None, dtype=np.float64, feats=None, offsets=None, cepstra=None, frontend_mode=0,
-                 pcm=None, sample_rate=16000, mfcc_params=None, feats_dev=None, dim=None, wire=None, pin=False):
+                 pcm=None, sample_rate=16000, mfcc_params=None, feats_dev=None, dim=None, wire=None, pin=False,
+                 endpoints=None, max_segments=1):
         """wire=np.float32 with dtype float64: `feats` cross the host link as fp32 and are widened on the device
         (gh_batch_create_wire); pin=True page-locks the host buffer for the copy, pin="keep" leaves it page-locked for
         the next upload from the same array (`host_unpin(array)` ends that, before the array is freed)."""
@@ -680,6 +770,33 @@ class Batch:
                                                   _ptr(self.offsets, _c_i64p), C.byref(h)))
             self.h = h
             self.S = None
+            return
+        if pcm is not None and endpoints is not None:
+            # the same front-end on recordings cut down to their speech segments on the device (endpoints: a DERIVED
+            # AudioRecorder config; pcm: 1-D int16 arrays): one utterance per segment, self.endpoints = what was detected
+            samples, fmt, s_off, f_whole, prm = pack_pcm(ctx, pcm, sample_rate, mfcc_params)
+            assert fmt == 0
+            for n in np.diff(f_whole):       # (a recording this short has no segment and stays whole)
+                if n < 2 and frontend_mode != 2:
+                    raise IndexError("index 1 is out of bounds for axis 0 with size %d" % n)  # core.py:16
+            U = len(s_off) - 1
+            ep = endpoint_params(endpoints)
+            start, end, nseg, is_open = _endpoint_outputs(U, int(max_segments))
+            utt_off = np.zeros(U * int(max_segments) + 1, dtype=np.int64)    # the batch's own utterance table comes back
+            n_utt = np.zeros(1, dtype=np.int64)
+            h = C.c_void_p()
+            _check(ctx.lib, ctx.lib.gh_batch_create_from_pcm_endpointed(
+                ctx.h, GH_F64 if self.np_dtype == np.float64 else GH_F32, int(frontend_mode), fmt, int(sample_rate),
+                prm[0], prm[1], prm[2], prm[3], U, samples.ctypes.data_as(C.c_void_p), _ptr(s_off, _c_i64p), C.byref(ep),
+                int(endpoints['start boundary']), int(max_segments), _ptr(start, _c_i64p), _ptr(end, _c_i64p),
+                _ptr(nseg, _c_i32p), _ptr(is_open, _c_u8p), _ptr(utt_off, _c_i64p), _ptr(n_utt, _c_i64p), C.byref(h)))
+            self.h = h
+            self.S = None
+            self.endpoints = _endpoint_result(start, end, nseg, is_open)
+            self.endpoints["recording"] = np.repeat(np.arange(U, dtype=np.int64), np.maximum(self.endpoints["n_segments"], 1))
+            self.offsets = utt_off[:int(n_utt[0]) + 1].copy()
+            self.N, self.D, self.U = int(self.offsets[-1]), (13 if frontend_mode == 2 else 39), int(n_utt[0])
+            assert self.U == len(self.endpoints["recording"])
             return
         if pcm is not None:  # N3 front-end from audio samples: MFCC -> [ceps | delta | delta-delta] -> standardise
             samples, fmt, s_off, f_off, prm = pack_pcm(ctx, pcm, sample_rate, mfcc_params)

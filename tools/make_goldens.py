@@ -19,6 +19,7 @@ import argparse
 import ast
 import contextlib
 import importlib
+import importlib.util
 import io
 import os
 import sys
@@ -820,6 +821,105 @@ def g20(R):
 
 
 ALL["G20"] = g20
+
+
+def load_audio_capture():
+    """sr/audio_capture/record.py by path, with a stand-in for the `pyaudio` module it imports at the top (the constants
+    and the two methods the recorder touches outside the microphone loop)."""
+    stub = types.ModuleType("pyaudio")
+    stub.paInt16, stub.paContinue, stub.paComplete = 8, 0, 1
+
+    class PyAudio:
+        def terminate(self):
+            pass
+
+        def get_sample_size(self, fmt):
+            return 2
+
+    stub.PyAudio = PyAudio
+    sys.modules["pyaudio"] = stub
+    spec = importlib.util.spec_from_file_location("ref_audio_record", os.path.join(REF, "sr", "audio_capture", "record.py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod
+
+
+def burst_signal(rng, n, sigma, bursts, amp=4000.0, freq=440.0, rate=8000, am=0.0):
+    """int16 recording: Gaussian noise floor + a tone over each (first, last) sample range, amplitude modulated by
+    1 + am sin(2 pi 3 t)."""
+    t = np.arange(n) / rate
+    x = rng.normal(0.0, sigma, size=n) if sigma > 0 else np.zeros(n)
+    for a, b in bursts:
+        x[a:b] += amp * (1 + am * np.sin(2 * np.pi * 3 * t[a:b])) * np.sin(2 * np.pi * freq * t[a:b])
+    return np.clip(np.round(x), -32768, 32767).astype(np.int16)
+
+
+def g21(R):
+    """Endpoint detection by the reference's OWN AudioRecorder.record_callback (sr/audio_capture/record.py:116-217), fed
+    whole chunks of `samples per frame` samples (what start_recording asks PyAudio for) until it answers paComplete or the
+    recording is over.  Two configs (the default one; 16 kHz with 400-sample frames every 160, forget factor 100, other
+    thresholds and a non-zero end boundary), ten recordings: noise floor + amplitude-modulated tone burst, two bursts,
+    all zeros, speech that never ends, too short for frame 10, shorter than one chunk.  Stored: signals, the derived
+    config values, both indices, started_speech, per-frame is_speech / level / energy, the three debug lists,
+    len(get_samples())."""
+    A = load_audio_capture()
+    default = dict({      # the dict AudioRecorder() builds for config=None (record.py:58-74), format = the stub's paInt16
+        'sample rate': 8000, 'format': 8, 'chunk size': 1024, 'channel count': 1, 'forget factor': 1,
+        'max record time': 1000, 'frame time': 0.02, 'frame stride': 0.01, 'adjustment': 0.01, 'onset threshold': 3,
+        'offset threshold': 0.2, 'silence threshold': 500, 'speech threshold': 250, 'start boundary': 200,
+        'end boundary': 0})
+    other = dict(default, **{'sample rate': 16000, 'forget factor': 100, 'frame time': 0.025, 'frame stride': 0.01,
+                             'adjustment': 0.02, 'onset threshold': 4, 'offset threshold': 0.5, 'silence threshold': 300,
+                             'speech threshold': 100, 'start boundary': 100, 'end boundary': 50})
+    rng = np.random.default_rng(2100)
+    cases = [
+        (0, burst_signal(rng, 12000, 40, [(3000, 6500)], am=0.5)),
+        (0, burst_signal(rng, 12400, 60, [(1300, 5000)], amp=2500, am=0.3)),          # an early, weaker burst; trailing partial chunk
+        (0, burst_signal(rng, 16000, 30, [(2500, 5500), (11000, 14000)], am=0.4)),    # the reference stops at the first
+        (0, np.zeros(12000, dtype=np.int16)),
+        (0, burst_signal(rng, 12000, 50, [(4000, 12000)], am=0.2)),                   # speech never ends
+        (0, burst_signal(rng, 1500, 50, [])),                                         # never reaches frame 10
+        (0, burst_signal(rng, 100, 50, [])),                                          # shorter than one chunk
+        (1, burst_signal(rng, 24000, 80, [(6000, 13000)], amp=5000, rate=16000, am=0.5)),
+        (1, burst_signal(rng, 20000, 20, [(5000, 20000)], amp=3000, rate=16000, am=0.3)),
+        (1, burst_signal(rng, 20100, 300, [(4000, 9000)], amp=1500, rate=16000, am=0.6)),
+    ]
+    out = dict(n_signals=np.array(len(cases)), config_of=np.array([c for c, _ in cases]))
+    keys = sorted(k for k in default if k != 'format')
+    out["config_keys"] = np.array(keys)
+    for ci, cfg in enumerate((default, other)):
+        out["c%d_raw" % ci] = np.array([float(cfg[k]) for k in keys])
+    derived_keys = keys + ['samples per frame']
+    out["derived_keys"] = np.array(derived_keys)
+    for si, (ci, x) in enumerate(cases):
+        cfg = dict((default, other)[ci])
+        with quiet():
+            ar = A.AudioRecorder(cfg)
+            assert ar.config is cfg
+            w = cfg['samples per frame']
+            for c in range(len(x) // w):
+                chunk = x[c * w:(c + 1) * w]
+                _, flag = ar.record_callback(chunk.tobytes(), w, None, 0)
+                if flag == sys.modules["pyaudio"].paComplete:
+                    break
+            got = ar.get_samples()
+        out["c%d_derived" % ci] = np.array([float(cfg[k]) for k in derived_keys])
+        pp = "s%d_" % si
+        s0 = max(ar.speech_start_index - cfg['start boundary'], 0)
+        assert np.array_equal(got, x[s0:s0 + len(got)])
+        out.update({pp + "x": x, pp + "start": np.array(ar.speech_start_index), pp + "end": np.array(ar.speech_end_index),
+                    pp + "started": np.array(bool(ar.started_speech)), pp + "n_fed": np.array(len(ar.samples)),
+                    pp + "is_speech": np.array([bool(f.is_speech) for f in ar.frames], dtype=bool),
+                    pp + "level": np.array([float(f.level) for f in ar.frames]),
+                    pp + "energy": np.array([float(f.energy) for f in ar.frames]),
+                    pp + "levels": np.array(ar.levels, dtype=np.float64),
+                    pp + "backgrounds": np.array(ar.backgrounds, dtype=np.float64),
+                    pp + "final_levels": np.array(ar.final_levels, dtype=np.float64),
+                    pp + "n_get_samples": np.array(len(got))})
+    save("G21_endpoints", **out)
+
+
+ALL["G21"] = g21
 
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
