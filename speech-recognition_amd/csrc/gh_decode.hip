@@ -117,6 +117,12 @@ static int forced_kernel() {
     return !e ? 0 : !strcmp(e, "lean") ? 1 : !strcmp(e, "generic") ? 2 : 0;
 }
 
+// GMMHMM_CHAIN=rows (read at every call) keeps the lane = chain form of the chain sweep out: lane = row for every graph
+static bool chain_rows_forced() {
+    const char* e = getenv("GMMHMM_CHAIN");
+    return e && !strcmp(e, "rows");
+}
+
 static int viterbi_impl(gh_ctx* ctx, const gh_lattices* lat, const gh_batch* b, const int32_t* utt_lattice,
                         double* out_end_cost, int32_t* out_best_end, int32_t* out_path,
                         const int64_t* path_off, int32_t* out_path_len, double* out_costs,
@@ -140,6 +146,7 @@ static int viterbi_impl(gh_ctx* ctx, const gh_lattices* lat, const gh_batch* b, 
             snprintf(buf, sizeof buf, " %s %.0f us |", what, std::chrono::duration<double, std::micro>(now - last).count());
             line += buf; last = now;
         }
+        void note(const char* what) { if (on) { line += ' '; line += what; line += " |"; } }
         ~HostTrace() {
             if (on) fprintf(stderr, "[gh_viterbi host]%s total %.0f us\n", line.c_str(),
                             std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count());
@@ -365,11 +372,18 @@ static int viterbi_impl(gh_ctx* ctx, const gh_lattices* lat, const gh_batch* b, 
             fa.pw = c.n_groups == 1 ? gh_fused_window(c.R, lat->chain_unit, &fa.period) : 0;
         }
         ctx->last_fused = use_fused ? 1 : 0;
+        // lane = chain form (chains of 1 .. 8 rows each with consecutive states: the stacked word models) or lane = row
+        // (everything else; GMMHMM_CHAIN=rows forces it, read at every call: the parity tests switch it)
+        const bool use_lanes = !use_fused && gh_chain_lanes_ok(lat->chain_unit) && lat->chain_consecutive && !chain_rows_forced();
+        if (!use_fused) trace.note(use_lanes ? "chain=lanes" : "chain=rows");
         for (size_t k = 0; k + 1 < chunk_begin.size(); ++k) {
             const int64_t u0 = chunk_begin[k], nu = chunk_begin[k + 1] - u0;
+            bool selected = use_fused && fa.select_end;
             rc = use_fused ? gh_launch_viterbi_fused(ctx, fa, u0, nu, b->dtype == GH_F64, want_bp, out_costs != nullptr)
-                           : gh_launch_viterbi_chain(ctx, c, u0, nu, b->dtype == GH_F64, want_bp, out_costs != nullptr, lat->chain_skip);
-            if (!rc && !(use_fused && fa.select_end)) rc = gh_launch_chain_backtrace(ctx, c, u0, nu);  // end selection (+ path when requested)
+                 : use_lanes ? gh_launch_viterbi_chain_lanes(ctx, c, lat->chain_unit, u0, nu, b->dtype == GH_F64, want_bp, out_costs != nullptr,
+                                                             lat->chain_skip, &selected)
+                             : gh_launch_viterbi_chain(ctx, c, u0, nu, b->dtype == GH_F64, want_bp, out_costs != nullptr, lat->chain_skip);
+            if (!rc && !selected) rc = gh_launch_chain_backtrace(ctx, c, u0, nu);  // end selection (+ path when requested)
             if (rc) return rc;
         }
     }

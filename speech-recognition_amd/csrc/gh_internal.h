@@ -267,6 +267,7 @@ struct gh_lattices {
     bool chain_ok, chain_skip;
     int chain_groups;
     int chain_unit = 0;              // all chains of the chain form have this many rows (0: lengths differ)
+    bool chain_consecutive = false;  // ... and the states of every chain are consecutive (lane = chain form of the sweep)
     double *d_ch_cost0, *d_ch_cost1, *d_ch_cost2;
     uint8_t* d_ch_info;
     int32_t *d_ch_end_slot, *d_ch_group_row0;

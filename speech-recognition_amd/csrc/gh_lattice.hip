@@ -309,6 +309,10 @@ extern "C" int gh_lattices_create(gh_ctx* ctx, int L, const int64_t* row_off, co
             }
             chgroups.push_back(R);
             lt->chain_unit = (ok && uniform) ? unit : 0;
+            // lane = chain form of the sweep: a lane reads the states of its chain as one run of the matrix row
+            lt->chain_consecutive = lt->chain_unit > 0;
+            for (int r = 0; r < R && lt->chain_consecutive; ++r)
+                if (r % lt->chain_unit && h_state[r] != h_state[r - 1] + 1) lt->chain_consecutive = false;
         }
         if (ok) { lt->chain_ok = true; lt->chain_skip = skip; lt->chain_groups = (int)chgroups.size() - 1; }
     }

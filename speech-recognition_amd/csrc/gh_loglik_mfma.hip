@@ -84,21 +84,34 @@ template <> struct Dom<float> {
     static constexpr float inv_k = (float)(1.0 / GH_LSE_SCALE32), off = GH_LSE_OFF32, off_test = GH_LSE_OFF32 * 0.1f;
 };
 
+// The addends of the Horner steps of exp2s() and logs().  As literals the compiler copies each into the accumulator of a
+// v_fmac at every use (5 v_mov_b64 per tile); the kernel pins them in registers for the length of the tile loop instead
+// (pin(): fp64, one block per wave -- the multi-block instantiations have no registers to spare).  Same values, same
+// operations.
+struct LseK {
+    double e3 = 2.6466421444330968834e-08;                                   // exp2s: (ln2/128)^3 / 3!
+    double l4 = -46.166241308446829036, l3 = 61.554988411262438714;          // logs: -K/4, K/3
+    double l2 = -92.332482616893658071, l1 = 184.66496523378731614;          //       -K/2, K
+    __device__ __forceinline__ void pin() {
+        asm volatile("" : "+v"(e3), "+v"(l4), "+v"(l3), "+v"(l2), "+v"(l1));
+    }
+};
+
 // K ln s for s in [1, M] (or NaN)
-__device__ __forceinline__ double logs(double s, const double* __restrict__ tab) {
+__device__ __forceinline__ double logs(double s, const double* __restrict__ tab, const LseK& k) {
     const double* __restrict__ inv = tab + 128;
     const double* __restrict__ nlog = tab + 256;
     const double m = __builtin_amdgcn_frexp_mant(s);  // [0.5, 1)
     const int e = __builtin_amdgcn_frexp_exp(s);
     const int j = (__double2hiint(m) >> 13) & 127;
     const double rho = fma(m, inv[j], -1.0);
-    double p = fma(rho, 36.932993046757463228, -46.166241308446829036);  // K/5, -K/4
-    p = fma(p, rho, 61.554988411262438714);                              // K/3
-    p = fma(p, rho, -92.332482616893658071);                             // -K/2
-    p = fma(p, rho, 184.66496523378731614);                              // K
+    double p = fma(rho, 36.932993046757463228, k.l4);  // K/5, -K/4
+    p = fma(p, rho, k.l3);                             // K/3
+    p = fma(p, rho, k.l2);                             // -K/2
+    p = fma(p, rho, k.l1);                             // K
     return fma(p, rho, nlog[j]) + (double)(e << 7);
 }
-__device__ __forceinline__ float logs(float s, const double*) { return __builtin_amdgcn_logf(s); }  // v_log_f32 = log2
+__device__ __forceinline__ float logs(float s, const double*, const LseK&) { return __builtin_amdgcn_logf(s); }  // v_log_f32 = log2
 
 // Cross-lane pair exchange without LDS: gfx950's v_permlane16_swap / v_permlane32_swap swap
 // 16-lane rows (resp. 32-lane halves) between two registers; fed the same value twice they
@@ -126,25 +139,46 @@ template <int W> __device__ __forceinline__ void pair_of(double v, double& a, do
 }
 template <typename T, int W> __device__ __forceinline__ T pair_max(T v) { T a, b; pair_of<W>(v, a, b); return vmax(a, b); }
 template <typename T, int W> __device__ __forceinline__ T pair_sum(T v) { T a, b; pair_of<W>(v, a, b); return a + b; }
+// The xor-16 sums of TWO values for the price of one: v_permlane16_swap applied to the pair (v0, v1) leaves (v0 of the
+// even row, v0 of the odd row) in the even lane groups and (v1 of the even row, v1 of the odd row) in the odd ones, so one
+// addition gives pair_sum<16>(v0) in the even groups and pair_sum<16>(v1) in the odd groups -- the same two operands in
+// the same order as pair_sum adds them (and likewise for the maximum).  For a caller that needs the result for v0 only in
+// the even and for v1 only in the odd groups.
+__device__ __forceinline__ void pair_split(float v0, float v1, float& a, float& b) {
+    auto r = __builtin_amdgcn_permlane16_swap(__float_as_uint(v0), __float_as_uint(v1), false, false);
+    a = __uint_as_float(r[0]); b = __uint_as_float(r[1]);
+}
+__device__ __forceinline__ void pair_split(double v0, double v1, double& a, double& b) {
+    auto lo = __builtin_amdgcn_permlane16_swap((unsigned)__double2loint(v0), (unsigned)__double2loint(v1), false, false);
+    auto hi = __builtin_amdgcn_permlane16_swap((unsigned)__double2hiint(v0), (unsigned)__double2hiint(v1), false, false);
+    a = __hiloint2double((int)hi[0], (int)lo[0]); b = __hiloint2double((int)hi[1], (int)lo[1]);
+}
+template <typename T> __device__ __forceinline__ T pair_sum_split(T v0, T v1) { T a, b; pair_split(v0, v1, a, b); return a + b; }
+template <typename T> __device__ __forceinline__ T pair_max_split(T v0, T v1) { T a, b; pair_split(v0, v1, a, b); return vmax(a, b); }
 
 // scaled (max, sum of 2^..) -> negative log-likelihood; every component off -> +inf; NaN stays NaN
 // inf_below: the scaled log below which the largest term counts as "off".  Default Dom<T>::off_test (only switched-off
 // components); compat mode (gh_ctx_set_compat bit 0): K ln 2^-1075 -- the reference sums w pdf in the LINEAR domain
 // (hmm_state.py:114-120), where every term whose logarithm is below that rounds to 0 and the state costs -log 0 = +inf
-template <typename T> __device__ __forceinline__ T nll_of(T mx, T sm, const double* tab, T inf_below) {
-    const T v = (mx + logs(sm, tab)) * -Dom<T>::inv_k;
+template <typename T> __device__ __forceinline__ T nll_of(T mx, T sm, const double* tab, T inf_below, const LseK& k) {
+    const T v = (mx + logs(sm, tab, k)) * -Dom<T>::inv_k;
     return (mx < inf_below) ? T(INFINITY) : v;
 }
 
-// max and sum-of-exp over the 4 registers of one lane, then over `width` lane groups (1, 2 or 4)
-template <typename T, typename V>
-__device__ __forceinline__ void tile_lse(const V& a, int width, T& mx, T& sm, const double* tab) {
-    T m = vmax(vmax(a[0], a[1]), vmax(a[2], a[3]));
-    if (width >= 2) m = pair_max<T, 16>(m);
-    if (width >= 4) m = pair_max<T, 32>(m);
+// max over the 4 registers of one lane; the lane's own sum-of-exp against the state's max
+template <typename T, typename V> __device__ __forceinline__ T lane_max(const V& a) { return vmax(vmax(a[0], a[1]), vmax(a[2], a[3])); }
+template <typename T, typename V> __device__ __forceinline__ T lane_terms(const V& a, T m, const double* tab, const LseK& k) {
     // a NaN component makes its own term (and so the sum) NaN: the state is poisoned as in the
     // reference's linear-domain sum, although vmax() dropped the NaN
-    T e = (exp2s(a[0] - m, tab) + exp2s(a[1] - m, tab)) + (exp2s(a[2] - m, tab) + exp2s(a[3] - m, tab));
+    return (exp2s(a[0] - m, tab, k.e3) + exp2s(a[1] - m, tab, k.e3)) + (exp2s(a[2] - m, tab, k.e3) + exp2s(a[3] - m, tab, k.e3));
+}
+// max and sum-of-exp over the 4 registers of one lane, then over `width` lane groups (1, 2 or 4)
+template <typename T, typename V>
+__device__ __forceinline__ void tile_lse(const V& a, int width, T& mx, T& sm, const double* tab, const LseK& k) {
+    T m = lane_max<T, V>(a);
+    if (width >= 2) m = pair_max<T, 16>(m);
+    if (width >= 4) m = pair_max<T, 32>(m);
+    T e = lane_terms<T, V>(a, m, tab, k);
     if (width >= 2) e = pair_sum<T, 16>(e);
     if (width >= 4) e = pair_sum<T, 32>(e);
     mx = m;
@@ -180,6 +214,16 @@ __device__ __forceinline__ double nll_of_fe(double mx, float sm, double inf_belo
     return (mx < inf_below) ? (double)INFINITY : v;
 }
 
+// A wave-uniform pointer into global memory as an opaque pair of scalar registers: the compiler can no longer fold a
+// loop-invariant lane offset into it (which turns every use into 64-bit vector arithmetic) and addresses the loads as
+// scalar base + 32-bit lane offset.
+template <typename T> using global_ptr = const T __attribute__((address_space(1)))*;
+template <typename T> __device__ __forceinline__ global_ptr<T> uniform_ptr(const T* p) {
+    uint32_t lo = (uint32_t)reinterpret_cast<uintptr_t>(p), hi = (uint32_t)(reinterpret_cast<uintptr_t>(p) >> 32);
+    asm("" : "+s"(lo), "+s"(hi));
+    return (global_ptr<T>)reinterpret_cast<const T*>(((uintptr_t)hi << 32) | lo);
+}
+
 // One tile's epilogue: log-sum-exp over the mixture components held in the accumulators of
 // both column tiles, written into the LDS output tile.  MP = padded mixture size (compile
 // time); MP == 32 stands for "several tiles per state" (M_pad = 16 * tiles_per_state, run
@@ -190,7 +234,7 @@ __device__ __forceinline__ double nll_of_fe(double mx, float sm, double inf_belo
 template <typename T, typename V, int MP, bool FE = false>
 __device__ __forceinline__ void tile_epilogue(const V& acc0, const V& acc1, int t, int f, int q, int S, int RS,
                                               int chunk_s0, int tiles_per_state, T* lds, T* dummy,
-                                              const double* tab, T (&run_mx)[2], T (&run_sm)[2], T inf_below) {
+                                              const double* tab, T (&run_mx)[2], T (&run_sm)[2], T inf_below, const LseK& k) {
     T* orow0 = lds + f * RS - chunk_s0;
     T* orow1 = orow0 + 16 * RS;
     if (MP == 1) {
@@ -213,8 +257,8 @@ __device__ __forceinline__ void tile_epilogue(const V& acc0, const V& acc1, int 
             for (int h = 0; h < 2; ++h) {
                 const T x0 = acc[2 * h], x1 = acc[2 * h + 1];
                 const T m = vmax(x0, x1);
-                const T e = exp2s(x0 - m, tab) + exp2s(x1 - m, tab);
-                *((s + h < S) ? orow + s + h : dummy) = nll_of<T>(m, e, tab, inf_below);
+                const T e = exp2s(x0 - m, tab, k.e3) + exp2s(x1 - m, tab, k.e3);
+                *((s + h < S) ? orow + s + h : dummy) = nll_of<T>(m, e, tab, inf_below, k);
             }
         }
 #ifdef GH_MF_NOEPI  // diagnostic build: MFMAs + loads only (tools/variant_bench.sh)
@@ -269,18 +313,25 @@ __device__ __forceinline__ void tile_epilogue(const V& acc0, const V& acc1, int 
     } else if (MP == 4) {
         T mx, sm;
         const int s = 4 * t + q;
-        tile_lse<T, V>(acc0, 1, mx, sm, tab);
-        *((s < S) ? orow0 + s : dummy) = nll_of<T>(mx, sm, tab, inf_below);
-        tile_lse<T, V>(acc1, 1, mx, sm, tab);
-        *((s < S) ? orow1 + s : dummy) = nll_of<T>(mx, sm, tab, inf_below);
+        tile_lse<T, V>(acc0, 1, mx, sm, tab, k);
+        *((s < S) ? orow0 + s : dummy) = nll_of<T>(mx, sm, tab, inf_below, k);
+        tile_lse<T, V>(acc1, 1, mx, sm, tab, k);
+        *((s < S) ? orow1 + s : dummy) = nll_of<T>(mx, sm, tab, inf_below, k);
     } else if (MP <= 16) {
         constexpr int width = MP / 4;  // lane groups per state: 2 or 4
-        T mx0, sm0, mx1, sm1;
-        tile_lse<T, V>(acc0, width, mx0, sm0, tab);
-        tile_lse<T, V>(acc1, width, mx1, sm1, tab);
+        // The even group finishes column tile 0, the odd group column tile 1, so both butterflies run on the PAIR of
+        // column tiles (pair_*_split: one exchange instead of one per column tile, the xor-32 level follows on the
+        // result).  mxs is the max of "this group's" column tile -- what `odd ? mx1 : mx0` would select --, and one more
+        // exchange hands every lane both maxima for its exponents.  Same operands in the same order as tile_lse().
+        T mxs = pair_max_split(lane_max<T, V>(acc0), lane_max<T, V>(acc1));
+        if (width >= 4) mxs = pair_max<T, 32>(mxs);
+        T mx0, mx1;
+        pair_of<16>(mxs, mx0, mx1);
+        T sm = pair_sum_split(lane_terms<T, V>(acc0, mx0, tab, k), lane_terms<T, V>(acc1, mx1, tab, k));
+        if (width >= 4) sm = pair_sum<T, 32>(sm);
         const bool odd = q & 1;
         const int s = (16 / MP) * t + q / width;
-        const T v = nll_of<T>(odd ? mx1 : mx0, odd ? sm1 : sm0, tab, inf_below);
+        const T v = nll_of<T>(mxs, sm, tab, inf_below, k);
         *(((q & (width - 1)) < 2 && s < S) ? (odd ? orow1 : orow0) + s : dummy) = v;
     } else {
         const bool last = (t + 1) % tiles_per_state == 0;
@@ -288,15 +339,15 @@ __device__ __forceinline__ void tile_epilogue(const V& acc0, const V& acc1, int 
 #pragma unroll
         for (int c = 0; c < 2; ++c) {
             T mx, sm;
-            tile_lse<T, V>(c ? acc1 : acc0, 4, mx, sm, tab);
+            tile_lse<T, V>(c ? acc1 : acc0, 4, mx, sm, tab, k);
             // merge with the running pair: one of the two rescale factors is 2^0
             const T d = run_mx[c] - mx;
-            const T e = exp2s((d > T(0)) ? -d : d, tab);
+            const T e = exp2s((d > T(0)) ? -d : d, tab, k.e3);
             run_sm[c] = (d > T(0)) ? fma(sm, e, run_sm[c]) : fma(run_sm[c], e, sm);
             run_mx[c] = (d > T(0)) ? run_mx[c] : mx;
         }
         const bool odd = q & 1;
-        const T v = nll_of<T>(odd ? run_mx[1] : run_mx[0], odd ? run_sm[1] : run_sm[0], tab, inf_below);
+        const T v = nll_of<T>(odd ? run_mx[1] : run_mx[0], odd ? run_sm[1] : run_sm[0], tab, inf_below, k);
         *((last && q < 2 && s < S) ? (odd ? orow1 : orow0) + s : dummy) = v;
 #pragma unroll
         for (int c = 0; c < 2; ++c) {
@@ -407,6 +458,8 @@ __global__ __launch_bounds__(64, (sizeof(T) == 4 ? 3 : 1)) void loglik_mfma_kern
     const int RS = (S <= SC) ? S : SC;  // LDS row stride: whole matrix rows when they fit one chunk
     T* dummy = lds + 32 * RS + lane;    // per-lane slot behind the output tile
     T run_mx[2] = {Dom<T>::off, Dom<T>::off}, run_sm[2] = {T(0), T(0)};
+    LseK lse_k;
+    if (sizeof(T) == 8 && !MULTI && !FE && MP != 1) lse_k.pin();
     int chunk_s0 = 0;  // first state held in the LDS output tile
     int subset_cnt = 0;  // (block table) number of states the block's tile range covers
 
@@ -423,13 +476,21 @@ __global__ __launch_bounds__(64, (sizeof(T) == 4 ? 3 : 1)) void loglik_mfma_kern
     // initialisation copies --, the next tile's C travels into the other register set; ring refilled as it is consumed
     auto mfma_tile = [&](int t, V& acc0, V& acc1, const V& c_use, V& c_load) {
         const int tn = (!MULTI || t + 1 < t_hi) ? t + 1 : nxt_t0;   // one block per wave: run on into the zero pad tile
-        const T* cp = Cpk + tn * 16 + 4 * q;
+        const global_ptr<T> cp = uniform_ptr(Cpk + (unsigned)(tn * 16));
 #pragma unroll
-        for (int r = 0; r < 4; ++r) c_load[r] = cp[r];
+        for (int r = 0; r < 4; ++r) c_load[r] = cp[4 * q + r];
         // slot j serves k-step j [and j + R], refilled R k-steps ahead: from this tile while that stays inside it,
         // from the next tile (tile 0 after the last) otherwise
-        const T* a_cur = Apk + (int64_t)t * (KS * 64) + lane;
-        const T* a_nxt = Apk + (int64_t)tn * (KS * 64) + lane;
+        // (wave-uniform bases kept in scalar registers -- uniform_ptr -- plus the lane as a 32-bit offset: the address
+        //  arithmetic per tile is scalar, nothing of it on the vector pipe.  One base per 4 KB window of k-steps: what a
+        //  load's immediate offset reaches)
+        constexpr int WIN = 4096 / (64 * (int)sizeof(T)), NW = (KS + WIN - 1) / WIN;
+        global_ptr<T> a_cur[NW], a_nxt[NW];
+#pragma unroll
+        for (int w = 0; w < NW; ++w) {
+            a_cur[w] = uniform_ptr(Apk + (unsigned)(t * (KS * 64) + w * (WIN * 64)));
+            a_nxt[w] = uniform_ptr(Apk + (unsigned)(tn * (KS * 64) + w * (WIN * 64)));
+        }
 #pragma unroll
         for (int ks = 0; ks < KS; ++ks) {
             const T a = ring[ks % R];
@@ -442,7 +503,8 @@ __global__ __launch_bounds__(64, (sizeof(T) == 4 ? 3 : 1)) void loglik_mfma_kern
             acc1 = Acc<T>::mfma(a, b[1][ks], ks == 0 ? c_use : acc1);
 #endif
 #ifndef GH_MF_NOLOAD
-            ring[ks % R] = (ks + R < KS) ? a_cur[(ks + R) * 64] : a_nxt[(ks + R - KS) * 64];
+            ring[ks % R] = (ks + R < KS) ? a_cur[(ks + R) / WIN][((ks + R) % WIN) * 64 + lane]
+                                         : a_nxt[(ks + R - KS) / WIN][((ks + R - KS) % WIN) * 64 + lane];
 #endif
         }
     };
@@ -512,7 +574,7 @@ __global__ __launch_bounds__(64, (sizeof(T) == 4 ? 3 : 1)) void loglik_mfma_kern
         // Two tiles per iteration with the accumulator pairs swapping roles: the epilogue of tile t-1 is scheduled
         // with the MFMAs of tile t without copying accumulators (16 v_mov per tile otherwise).
         auto epi = [&](const V& e0, const V& e1, int t) {
-            tile_epilogue<T, V, MP, FE>(e0, e1, t, f, q, S, RS, chunk_s0, tiles_per_state, lds, dummy, tab, run_mx, run_sm, inf_below);
+            tile_epilogue<T, V, MP, FE>(e0, e1, t, f, q, S, RS, chunk_s0, tiles_per_state, lds, dummy, tab, run_mx, run_sm, inf_below, lse_k);
 #pragma unroll
             for (int i = 0; i < (GH_MF_SGB ? 2 * KS : 0); ++i) {   // (forced MFMA / VALU interleave: measured slower)
                 __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);

@@ -70,9 +70,16 @@ struct gh_chain_args {
     double* costs;
     const int64_t* costs_off;
     int* flag;
+    int unit_chains;          // lane = chain form: chains per utterance (R / rows per chain)
+    int64_t n_slots;          // lane = chain form: launch slots of this launch (slot0 .. slot0 + n_slots - 1)
 };
 int gh_launch_viterbi_chain(gh_ctx* ctx, const gh_chain_args& a, int64_t u_begin, int64_t n_utts, bool f64,
                             bool want_bp, bool want_costs, bool skip);
+// lane = chain form of the same sweep for graphs whose chains all have `unit` rows (gh_chain_lanes_ok: 1 .. 8) with
+// consecutive states; *selected: best_end is written, gh_launch_chain_backtrace is not needed for the end selection
+bool gh_chain_lanes_ok(int unit);
+int gh_launch_viterbi_chain_lanes(gh_ctx* ctx, const gh_chain_args& a, int unit, int64_t u_begin, int64_t n_utts, bool f64,
+                                  bool want_bp, bool want_costs, bool skip, bool* selected);
 int gh_launch_chain_backtrace(gh_ctx* ctx, const gh_chain_args& a, int64_t u_begin, int64_t n_utts);
 
 // Fused single-Gaussian decode (gh_viterbi_fused.hip): the chain kernel's graph and outputs, but every lane scores its

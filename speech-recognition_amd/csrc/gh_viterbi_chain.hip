@@ -97,6 +97,199 @@ __global__ __launch_bounds__(64) void viterbi_chain_kernel(gh_chain_args a) {
     }
 }
 
+// ---- lane = chain form: graphs whose chains all have N rows (gh_lattices::chain_unit; stacked word models) ----
+// ONE LANE walks one chain: its N previous costs, arc costs and row flags live in registers, the predecessors of a row
+// are the lane's own registers (no DPP shift, no idle lanes inside an utterance).  A wave holds floor(64 / chains per
+// utterance) whole utterances from consecutive launch slots (perm sorts by length: nearly equal); a lane whose utterance
+// has ended stops updating.  More than 64 chains per utterance: several waves per utterance.  The lane reads its N
+// consecutive emissions nll[t, state(row0) .. +N-1] of a column into the same prefetch ring as above.
+//
+// Same results bit for bit as viterbi_chain_kernel.  With back-pointers the candidates are tried in the same order with
+// the same strict '<'.  Without them the cell is min(min(c2+p2, c1+p1), c0+p0) + e in v_min_f64: the value of a minimum
+// does not depend on the order of equal candidates, minNum drops a NaN candidate exactly as `v < best` does, and the
+// `c != c -> +inf` rule is one more minimum against +inf.  A row without arcs has three +inf arc costs, so its cell is
+// +inf (or NaN -> +inf) without a test of its own; an arc that would cross a chain boundary has cost +inf by the
+// definition of a chain and is left out.  Column 0 (start rows take e, the others +inf) is peeled.
+// SELECT (no back-pointers and the whole utterance in one wave): the end selection of chain_end_select_kernel happens
+// here, on the end costs parked in LDS.
+template <typename ET, int N, bool WANT_BP, bool WANT_COSTS, bool SKIP>
+__global__ __launch_bounds__(64) void viterbi_chain_lanes_kernel(gh_chain_args a) {
+    constexpr bool SELECT = !WANT_BP;
+    __shared__ double s_end[SELECT ? 64 * N : 1];
+    const int lane = threadIdx.x;
+    const int C = a.unit_chains;               // chains per utterance
+    const bool one_wave = C <= 64;             // (then SELECT applies)
+    int ul = 0, chain;
+    int64_t slot;
+    bool act;
+    if (one_wave) {
+        const int upw = 64 / C;
+        ul = lane / C;
+        chain = lane - ul * C;
+        slot = a.slot0 + (int64_t)blockIdx.x * upw + ul;
+        act = ul < upw && slot < a.slot0 + a.n_slots;
+        if (!act) { ul = 0; chain = 0; slot = a.slot0 + (int64_t)blockIdx.x * upw; }   // an idle lane shadows lane 0: same loads, no stores
+    } else {
+        const int wpu = (C + 63) >> 6;
+        slot = a.slot0 + blockIdx.x / wpu;
+        chain = (blockIdx.x % wpu) * 64 + lane;
+        act = chain < C;
+        if (!act) chain = 0;
+    }
+    const int64_t u = a.perm ? a.perm[slot] : slot;
+    const int64_t f0 = a.utt_off[u];
+    const int T = (int)(a.utt_off[u + 1] - f0);
+    const int S = a.S, R = a.R;
+    const int row0 = chain * N;
+    const double INF = INFINITY;
+
+    // the lane's row constants
+    double c0[N], c1[N], c2[N];
+    uint32_t info = 0;      // 3 bits per row: bits 0-1 code of the first arc (3 = none), bit 2 start row
+#pragma unroll
+    for (int i = 0; i < N; ++i) {
+        c0[i] = a.cost0[row0 + i];
+        c1[i] = i >= 1 ? a.cost1[row0 + i] : INF;
+        c2[i] = (SKIP && i >= 2) ? a.cost2[row0 + i] : INF;
+        info |= (uint32_t)(a.row_info[row0 + i] & 7) << (3 * i);
+    }
+    const ET* ep = static_cast<const ET*>(a.nll) + f0 * S + a.row_state[row0];
+
+    // wave-uniform bounds of the lanes' lengths: the loop without guards runs while every lane is inside its utterance
+    int tmin = T, tmax = T;
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) {
+        tmin = min(tmin, __shfl_xor(tmin, m, 64));
+        tmax = max(tmax, __shfl_xor(tmax, m, 64));
+    }
+    tmin = __builtin_amdgcn_readfirstlane(tmin);
+    tmax = __builtin_amdgcn_readfirstlane(tmax);
+
+    double prev[N];
+    uint8_t* bp = WANT_BP ? a.bp + a.bp_off[slot] + row0 : nullptr;
+    double* co = WANT_COSTS ? a.costs + a.costs_off[u] + (int64_t)row0 * T : nullptr;
+
+    // column 0
+    if (T > 0) {
+#pragma unroll
+        for (int i = 0; i < N; ++i) {
+            const bool is_start = (info >> (3 * i + 2)) & 1;
+            prev[i] = is_start ? (double)ep[i] : INF;      // decode.py:99-101
+            if (WANT_BP && act) bp[i] = is_start ? 3 : (info >> (3 * i)) & 3;
+            if (WANT_COSTS && act) co[(int64_t)i * T] = prev[i];
+        }
+        if (WANT_BP) bp += R;
+        if (WANT_COSTS) co += 1;
+    } else {
+#pragma unroll
+        for (int i = 0; i < N; ++i) prev[i] = INF;
+    }
+
+    ET ring[PF][N];
+    const ET* lp = ep + S;
+
+    auto column = [&](const ET (&ev)[N]) {
+#pragma unroll
+        for (int i = N - 1; i >= 0; --i) {          // descending: prev[i-1], prev[i-2] are still the previous column's
+            const double e = (double)ev[i];
+            double c;
+            if (WANT_BP) {
+                double best = INF;
+                uint32_t code = (info >> (3 * i)) & 3;
+                if (SKIP && i >= 2) {
+                    const double v2 = c2[i] + prev[i - 2];
+                    if (v2 < best) { best = v2; code = 2; }
+                }
+                if (i >= 1) {
+                    const double v1 = c1[i] + prev[i - 1];
+                    if (v1 < best) { best = v1; code = 1; }
+                }
+                const double v0 = c0[i] + prev[i];
+                if (v0 < best) { best = v0; code = 0; }
+                c = best + e;
+                c = (c != c) ? INF : c;                  // min(inf, nan) keeps inf (decode.py:124)
+                if (act) bp[i] = (uint8_t)code;
+            } else {
+                double m = c0[i] + prev[i];
+                if (i >= 1) {
+                    double m1 = c1[i] + prev[i - 1];
+                    if (SKIP && i >= 2) m1 = vmin(c2[i] + prev[i - 2], m1);
+                    m = vmin(m1, m);
+                }
+                c = vmin(m + e, INF);
+            }
+            prev[i] = c;
+            if (WANT_COSTS && act) co[(int64_t)i * T] = c;
+        }
+        if (WANT_BP) bp += R;
+        if (WANT_COSTS) co += 1;
+    };
+
+    // The loop without guards has its own ring fill in front of it: reached over the guarded fill, the wait for a ring slot
+    // at the top of the loop becomes a wait for every load in flight (the compiler cannot count loads behind branches).
+    int t = 1;
+    if (1 + 2 * PF <= tmin) {
+#pragma unroll
+        for (int k = 0; k < PF; ++k) {
+#pragma unroll
+            for (int i = 0; i < N; ++i) ring[k][i] = lp[i];
+            lp += S;
+        }
+        do {                                        // every lane: columns t .. t+PF-1 exist, loads t+PF .. t+2PF-1 are inside
+#pragma unroll
+            for (int k = 0; k < PF; ++k) {
+                column(ring[k]);      // (consumed before the slot's refill is issued: the ring stays in its registers)
+#pragma unroll
+                for (int i = 0; i < N; ++i) ring[k][i] = lp[i];
+                lp += S;
+            }
+            t += PF;
+        } while (t + 2 * PF <= tmin);
+    } else {
+#pragma unroll
+        for (int k = 0; k < PF; ++k) {
+#pragma unroll
+            for (int i = 0; i < N; ++i) ring[k][i] = (1 + k < T) ? lp[i] : ET(0);
+            lp += S;
+        }
+    }
+    for (; t < tmax; t += PF) {
+#pragma unroll
+        for (int k = 0; k < PF; ++k) {
+            if (t + k < T) column(ring[k]);
+#pragma unroll
+            for (int i = 0; i < N; ++i) ring[k][i] = (t + k + PF < T) ? lp[i] : ET(0);
+            lp += S;
+        }
+    }
+
+    // end costs: every end row knows its slot in the graph's end list
+    if (T > 0) {
+#pragma unroll
+        for (int i = 0; i < N; ++i) {
+            const int es = a.end_slot[row0 + i];
+            if (act && es >= 0) {
+                a.end_cost[u * a.n_end + es] = prev[i];
+                if (SELECT && one_wave) s_end[ul * a.n_end + es] = prev[i];
+            }
+        }
+    }
+    if (SELECT && one_wave) {
+        __syncthreads();
+        if (act && chain == 0) {
+            double best = INF;
+            int bi = -1;
+            if (T > 0)
+                for (int k = 0; k < a.n_end; ++k) {
+                    const double c = s_end[ul * a.n_end + k];
+                    if (best >= c) { best = c; bi = k; }          // '>=': the last of equal minima (decode.py:129-134)
+                }
+            a.best_end[u] = bi;
+            if (a.path_len) a.path_len[u] = 0;
+        }
+    }
+}
+
 // End selection ('>=': the last of equal minima, decode.py:129-134) + back-trace of one utterance
 // per wave; lane 0 walks the 1-byte back-pointers, the pairs are parked in LDS and flushed by
 // the wave.
@@ -169,6 +362,38 @@ int gh_launch_viterbi_chain(gh_ctx* ctx, const gh_chain_args& a, int64_t u_begin
 #undef GH_VC_S
 #undef GH_VC
     GH_HIP(hipGetLastError());
+    return GH_OK;
+}
+
+// Lane = chain form for chains of `unit` rows each (1 .. 8).  *selected: the kernel has written best_end itself (no
+// back-pointers wanted and every utterance inside one wave), the end selection need not be launched.
+bool gh_chain_lanes_ok(int unit) { return unit >= 1 && unit <= 8; }
+int gh_launch_viterbi_chain_lanes(gh_ctx* ctx, const gh_chain_args& a, int unit, int64_t u_begin, int64_t n_utts, bool f64,
+                                  bool want_bp, bool want_costs, bool skip, bool* selected) {
+    if (selected) *selected = false;
+    if (n_utts <= 0) return GH_OK;
+    GH_REQUIRE(gh_chain_lanes_ok(unit) && a.R % unit == 0, "gh_viterbi: internal: chains of %d rows in the lane form", unit);
+    gh_chain_args b = a;
+    b.slot0 = u_begin;  // perm[] and bp_off[] are indexed by absolute launch slot
+    b.n_slots = n_utts;
+    b.unit_chains = a.R / unit;
+    const int C = b.unit_chains;
+    const int64_t n_waves = C <= 64 ? (n_utts + 64 / C - 1) / (64 / C) : n_utts * ((C + 63) / 64);
+    dim3 grid((unsigned)n_waves), blk(64);
+    if (unit < 3) skip = false;   // (no r-2 arc inside a chain of two rows)
+#define GH_VL(ET, NN, BP, CO, SK) hipLaunchKernelGGL((viterbi_chain_lanes_kernel<ET, NN, BP, CO, SK>), grid, blk, 0, ctx->stream, b)
+#define GH_VL_S(ET, NN, BP, CO) do { if (NN >= 3 && skip) GH_VL(ET, NN, BP, CO, (NN >= 3)); else GH_VL(ET, NN, BP, CO, false); } while (0)
+#define GH_VL_T(ET, NN) do { if (want_costs) GH_VL_S(ET, NN, true, true); else if (want_bp) GH_VL_S(ET, NN, true, false); else GH_VL_S(ET, NN, false, false); } while (0)
+#define GH_VL_N(ET) switch (unit) { case 1: GH_VL_T(ET, 1); break; case 2: GH_VL_T(ET, 2); break; case 3: GH_VL_T(ET, 3); break; \
+                                    case 4: GH_VL_T(ET, 4); break; case 5: GH_VL_T(ET, 5); break; case 6: GH_VL_T(ET, 6); break; \
+                                    case 7: GH_VL_T(ET, 7); break; default: GH_VL_T(ET, 8); break; }
+    if (f64) GH_VL_N(double) else GH_VL_N(float)
+#undef GH_VL_N
+#undef GH_VL_T
+#undef GH_VL_S
+#undef GH_VL
+    GH_HIP(hipGetLastError());
+    if (selected) *selected = !want_bp && !want_costs && C <= 64;
     return GH_OK;
 }
 

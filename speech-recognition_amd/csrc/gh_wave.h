@@ -73,19 +73,21 @@ __device__ __forceinline__ void push_bit(uint64_t& word, unsigned long long mask
 __device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
 // 2^(y/128) for finite y <= 0 (or NaN): table of 2^(j/128) (128 entries) + degree-4 polynomial
-__device__ __forceinline__ double exp2s(double y, const double* __restrict__ tab) {
+// (c3: the k = 3 coefficient, the addend of the first Horner step.  A caller that keeps it in a register across its loop
+//  saves the copy into the accumulator of a v_fmac per call; the arithmetic is the same)
+__device__ __forceinline__ double exp2s(double y, const double* __restrict__ tab, double c3 = 2.6466421444330968834e-08) {
     const double n = __builtin_rint(y);
     const double r = y - n;
     const int ni = (int)n;  // v_cvt_i32_f64 saturates
     const double t = tab[ni & 127];
-    double p = fma(r, 3.583032305400251285e-11, 2.6466421444330968834e-08);  // (ln2/128)^k / k!, k = 4, 3
+    double p = fma(r, 3.583032305400251285e-11, c3);  // (ln2/128)^k / k!, k = 4, 3
     p = fma(p, r, 1.4662262387640424337e-05);
     p = fma(p, r, 5.4152123481245727298e-03);
     p = p * r;  // 2^(r/128) - 1
     return __builtin_ldexp(fma(t, p, t), ni >> 7);
 }
 // (the float domain of gh_loglik_mfma.hip: the hardware's own exp2)
-__device__ __forceinline__ float exp2s(float y, const double*) { return __builtin_amdgcn_exp2f(y); }
+__device__ __forceinline__ float exp2s(float y, const double*, double = 0.0) { return __builtin_amdgcn_exp2f(y); }
 
 // np.isclose(a, b) with numpy's default tolerances
 __device__ __forceinline__ bool np_isclose(double a, double b) {
