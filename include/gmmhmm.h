@@ -654,6 +654,39 @@ int gh_text_viterbi(gh_ctx* ctx, const gh_lextree* tree, int64_t n_strings, cons
                     int64_t* best_cost /*[n_strings]*/, int32_t* path_len /*[n_strings]*/, int32_t* path_rows /*[path_cap]*/,
                     int64_t path_cap);
 
+/* ------------------------------------------------ online decode: A6 + A12 while the audio is still arriving
+ * decode_hmm_states (decode.py:80-146) over the word-loop grammar, carried across the chunks of n_streams live
+ * utterances: a column depends on the previous column only, so a stream keeps its previous column (16 N doubles), its
+ * open decision word and its decision history on the device, and gh_online_push advances it by the frames of one chunk.
+ * CONTRACT: after k frames of a stream, gh_online_result returns bitwise what gh_viterbi / gh_viterbi_labels return for
+ * a one-utterance decode of those k frames from the same likelihoods -- end costs, chosen end (last of equal minima,
+ * decode.py:129-134), path (end -> start, end cell excluded, :143-145) and label sequence (main.py:59-67).
+ * gh_online_create: `lat` must be ONE graph in the narrow loop form (gh_lattices_forms bit 2, up to 16 words of 2 .. 8,
+ * 12 or 16 states) without a beam and must outlive the session; a K-layer lattice, a bigram grammar, more than 16 words,
+ * several graphs or a beam are GH_ERR_UNSUPPORTED (there is no other path).  It allocates 128 N B of state, 64 B of open
+ * word and 64 ceil(max_frames / columns per decision word) B of history per stream (16 B per frame at N = 5).
+ * max_frames is a hard capacity: a push that would take ANY of its streams past it is refused as a whole
+ * (GH_ERR_INVALID) before anything is enqueued, and so is one with a stream named twice or out of range. */
+typedef struct gh_online gh_online;
+int gh_online_create(gh_ctx* ctx, const gh_lattices* lat, int64_t n_streams, int64_t max_frames, gh_online** out);
+void gh_online_destroy(gh_online* on);
+/* streams ids[0..n) (NULL: all) start again at column 0 */
+int gh_online_reset(gh_ctx* ctx, gh_online* on, int64_t n, const int64_t* ids /*[n] or NULL*/);
+/* Stream ids[u] takes the columns [first[u], first[u] + count[u]) of utterance u of the batch, whose likelihood matrix
+ * must be resident (gh_loglik); first NULL: 0, count NULL: up to the utterance's end.  count 0 is a stream that sits the
+ * tick out.  The call only enqueues work on the context's stream; the batch must stay alive until that work is done. */
+int gh_online_push(gh_ctx* ctx, gh_online* on, const gh_batch* b, const int64_t* ids /*[U], distinct*/,
+                   const int64_t* first /*[U] or NULL*/, const int64_t* count /*[U] or NULL*/);
+/* frames every stream has taken since its last reset */
+int gh_online_frames(const gh_online* on, int64_t* out /*[n_streams]*/);
+/* The decode of what streams ids[0..n) (NULL: all n_streams) have taken so far, in the conventions of gh_viterbi and
+ * gh_viterbi_labels: end_cost [n, n_end], best_end [n] (-1: no frames); labels of stream ids[i] at label_off[i]
+ * (capacity label_off[i+1] - label_off[i]) with row_label [R]; path [path_off[n], 2] with path_off[i+1] - path_off[i]
+ * >= gh_viterbi_path_cap for streams of more than one frame.  Any output may be NULL.  Synchronises. */
+int gh_online_result(gh_ctx* ctx, gh_online* on, int64_t n, const int64_t* ids /*[n] or NULL*/, double* end_cost,
+                     int32_t* best_end, const int32_t* row_label, int32_t* labels, const int64_t* label_off /*[n+1]*/,
+                     int32_t* n_labels, int32_t* path, const int64_t* path_off /*[n+1]*/, int32_t* path_len);
+
 #ifdef __cplusplus
 }
 #endif

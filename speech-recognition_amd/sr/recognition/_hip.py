@@ -162,6 +162,13 @@ SIGNATURES = {
     "gh_lextree_destroy": (None, [C.c_void_p]),
     "gh_text_viterbi": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, _c_i64p, _c_i32p, C.c_int, _c_i64p, _c_i64p, _c_i32p,
                                   _c_i32p, C.c_int64]),
+    "gh_online_create": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.POINTER(C.c_void_p)]),
+    "gh_online_destroy": (None, [C.c_void_p]),
+    "gh_online_reset": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, _c_i64p]),
+    "gh_online_push": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, _c_i64p, _c_i64p, _c_i64p]),
+    "gh_online_frames": (C.c_int, [C.c_void_p, _c_i64p]),
+    "gh_online_result": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, _c_i64p, _c_f64p, _c_i32p, _c_i32p, _c_i32p, _c_i64p, _c_i32p,
+                                   _c_i32p, _c_i64p, _c_i32p]),
 }
 
 
@@ -1364,6 +1371,95 @@ class Lattices:
         if getattr(self, "h", None):
             if getattr(self.ctx, "h", None):  # a handle must not outlive its context (interpreter shutdown order)
                 self.ctx.lib.gh_lattices_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class OnlineSession:
+    """Online decode over ONE word-loop graph (gh_online): `n_streams` live utterances whose previous column, open
+    decision word and decision history stay on the device; `push` advances streams by chunks of resident likelihoods,
+    `result` is the decode of what a stream has taken so far -- bitwise the one-shot decode of those frames.
+    `lat` (a `Lattices` with one graph in the narrow loop form) must outlive the session; any other graph form raises
+    `Unsupported`."""
+
+    def __init__(self, ctx, lat, n_streams, max_frames):
+        self.ctx, self.lat = ctx, lat
+        self.n_streams, self.max_frames = int(n_streams), int(max_frames)
+        h = C.c_void_p()
+        rc = ctx.lib.gh_online_create(ctx.h, lat.h, self.n_streams, self.max_frames, C.byref(h))
+        if rc == GH_ERR_UNSUPPORTED:
+            raise Unsupported(ctx.lib.gh_last_error().decode("utf-8", "replace"))
+        _check(ctx.lib, rc)
+        self.h = h
+        self.n_end, self.R = int(lat.n_end[0]), int(lat.R[0])
+        self._nlev = lat.path_cap(0, 1)
+
+    @staticmethod
+    def _i64(a):
+        return None if a is None else np.ascontiguousarray(a, dtype=np.int64)
+
+    def push(self, batch, ids, first=None, count=None):
+        """Stream ids[u] takes the columns [first[u], first[u] + count[u]) of utterance u of `batch` (likelihoods resident;
+        first None: 0, count None: to the utterance's end).  Only enqueues work: keep the batch alive until it is done."""
+        ids, first, count = self._i64(ids), self._i64(first), self._i64(count)
+        assert len(ids) == batch.U and (first is None or len(first) == batch.U) and (count is None or len(count) == batch.U)
+        _check(self.ctx.lib, self.ctx.lib.gh_online_push(self.ctx.h, self.h, batch.h, _ptr(ids, _c_i64p), _ptr(first, _c_i64p),
+                                                         _ptr(count, _c_i64p)))
+
+    def reset(self, ids=None):
+        ids = self._i64(ids)
+        _check(self.ctx.lib, self.ctx.lib.gh_online_reset(self.ctx.h, self.h, 0 if ids is None else len(ids), _ptr(ids, _c_i64p)))
+
+    def frames(self):
+        """Frames every stream has taken since its last reset: int64 [n_streams]."""
+        out = np.empty(self.n_streams, dtype=np.int64)
+        _check(self.ctx.lib, self.ctx.lib.gh_online_frames(self.h, _ptr(out, _c_i64p)))
+        return out
+
+    def result(self, ids=None, row_label=None, max_labels=None, want_path=False):
+        """dict(end_cost [n, n_end], best_end [n], frames [n][, labels: list of int32 arrays][, paths: list of int64 [K, 2]])
+        for the streams `ids` (None: all).  row_label [R]: the label sequences of gh_viterbi_labels (max_labels: scalar or
+        [n] bound per stream); want_path: the reference-style (row, column) paths."""
+        lib = self.ctx.lib
+        ids = np.arange(self.n_streams, dtype=np.int64) if ids is None else self._i64(ids)
+        n = len(ids)
+        ok = (ids >= 0) & (ids < self.n_streams)                          # an id out of range is the library's to refuse
+        T = np.where(ok, self.frames()[np.where(ok, ids, 0)], 0) if n else np.zeros(0, dtype=np.int64)
+        end_cost = np.empty((n, self.n_end), dtype=np.float64)
+        best_end = np.empty(n, dtype=np.int32)
+        rl = labels = label_off = n_labels = path = path_off = path_len = None
+        if row_label is not None:
+            rl = np.ascontiguousarray(np.asarray(row_label, dtype=np.int32).reshape(-1))
+            assert len(rl) == self.R, "row_label must give one label per graph row"
+            cap = np.where(T > 1, T * self._nlev // 2 + 1, 0)
+            if max_labels is not None:
+                cap = np.minimum(cap, np.asarray(max_labels, dtype=np.int64))
+            label_off = np.concatenate([[0], np.cumsum(cap)]).astype(np.int64)
+            labels = np.empty(int(label_off[-1]), dtype=np.int32)
+            n_labels = np.empty(n, dtype=np.int32)
+        if want_path:
+            path_off = np.concatenate([[0], np.cumsum(np.where(T > 1, T * self._nlev, 0))]).astype(np.int64)
+            path = np.empty((int(path_off[-1]), 2), dtype=np.int32)
+            path_len = np.empty(n, dtype=np.int32)
+        _check(lib, lib.gh_online_result(self.ctx.h, self.h, n, _ptr(ids, _c_i64p), _ptr(end_cost, _c_f64p), _ptr(best_end, _c_i32p),
+                                         _ptr(rl, _c_i32p), _ptr(labels, _c_i32p), _ptr(label_off, _c_i64p), _ptr(n_labels, _c_i32p),
+                                         _ptr(path, _c_i32p), _ptr(path_off, _c_i64p), _ptr(path_len, _c_i32p)))
+        out = dict(end_cost=end_cost, best_end=best_end, frames=T)
+        if rl is not None:
+            out["labels"] = [labels[label_off[i]:label_off[i] + n_labels[i]] for i in range(n)]
+        if want_path:
+            out["paths"] = [path[path_off[i]:path_off[i] + path_len[i]].astype(np.int64) for i in range(n)]
+        return out
+
+    def close(self):
+        if getattr(self, "h", None):
+            if getattr(self.ctx, "h", None):
+                self.ctx.lib.gh_online_destroy(self.h)
             self.h = None
 
     def __del__(self):

@@ -13,7 +13,7 @@ from . import _hip
 from . import _pack
 from .continuous_speech import packed_lattice, packed_loop_lattice, packed_bigram_lattice
 
-__all__ = ["IsolatedWordRecognizer", "ContinuousDecoder", "InFlight", "path_to_words", "sequence_report", "train_words"]
+__all__ = ["IsolatedWordRecognizer", "ContinuousDecoder", "OnlineDecoder", "InFlight", "path_to_words", "sequence_report", "train_words"]
 
 
 def _stack_models(ctx, models):
@@ -380,6 +380,137 @@ class ContinuousDecoder:
     def accuracy(self, xs, labels, verbose=False):
         """Decode `xs` and tally against the label strings like main.py:54-84 -- see `sequence_report`."""
         return sequence_report(self.decode(xs), labels, verbose=verbose)
+
+    def online(self, n_streams, max_frames):
+        """An `OnlineDecoder` of `n_streams` live utterances of up to `max_frames` frames each, sharing this decoder's
+        packed mixtures and graph (grammar="loop" only: anything else raises `_hip.Unsupported`)."""
+        return OnlineDecoder(self, n_streams, max_frames)
+
+
+class OnlineDecoder:
+    """Decode while the audio is still arriving: `n_streams` utterances take feature frames chunk by chunk, and
+    `result` gives at any time what `ContinuousDecoder.decode_batch` would give for the frames pushed so far -- the same
+    words, end costs, chosen ends and paths, without decoding the prefix again (the dynamic program of a stream is
+    carried on the device: its previous column and its decision history, gh_online).
+
+        dec = ContinuousDecoder(models, grammar="loop", word_penalty=p)
+        on = dec.online(n_streams=64, max_frames=3000)
+        on.push([3, 7], [frames_of_3, frames_of_7])          # [t_i, D] arrays, t_i >= 0
+        words, info = on.result([3])                          # running hypothesis of stream 3
+        words, info = on.finish([7])                          # ... of stream 7, whose id is free again
+
+    `max_frames` is a hard capacity per stream.  Bad arguments (an id twice in one push or out of range, a chunk of
+    another feature dimension, a push past `max_frames`) raise ValueError before the GPU is touched, and no stream moves."""
+
+    def __init__(self, decoder, n_streams, max_frames):
+        if decoder.grammar != "loop":
+            raise _hip.Unsupported("online decoding takes the word-loop grammar (grammar='loop'), not %r" % (decoder.grammar,))
+        if int(n_streams) < 1 or int(max_frames) < 1:
+            raise ValueError("n_streams and max_frames must be positive")
+        self.decoder = decoder
+        self.n_streams, self.max_frames = int(n_streams), int(max_frames)
+        self.session = _hip.OnlineSession(decoder.ctx, decoder.lat, self.n_streams, self.max_frames)
+        self._frames = np.zeros(self.n_streams, dtype=np.int64)       # what the session holds, for the checks below
+        self._row_word = np.where(decoder.row_state >= 0, decoder.row_state // decoder.n, -1).astype(np.int32)
+
+    @property
+    def frames(self):
+        """Frames every stream has taken since its last reset: int64 [n_streams]."""
+        return self._frames.copy()
+
+    def _ids(self, ids, distinct=True):
+        a = np.asarray(ids)
+        if a.ndim != 1 or (a.size and a.dtype.kind not in "iu"):
+            raise ValueError("ids must be a one-dimensional sequence of stream indices")
+        a = a.astype(np.int64)
+        if a.size and (a.min() < 0 or a.max() >= self.n_streams):
+            raise ValueError("stream ids must lie in [0, %d)" % self.n_streams)
+        if distinct and len(np.unique(a)) != len(a):
+            raise ValueError("a stream is named twice in one push")
+        return a
+
+    def _room(self, ids, counts):
+        over = self._frames[ids] + counts > self.max_frames
+        if np.any(over):
+            k = int(np.flatnonzero(over)[0])
+            raise ValueError("stream %d would hold %d frames, capacity %d" % (ids[k], self._frames[ids[k]] + counts[k], self.max_frames))
+
+    def push(self, ids, chunks):
+        """Stream ids[i] takes the frames chunks[i], a [t_i, D] array (t_i = 0: the stream sits this tick out)."""
+        ids = self._ids(ids)
+        if len(chunks) != len(ids):
+            raise ValueError("%d chunks for %d ids" % (len(chunks), len(ids)))
+        D = self.decoder.gmm.D
+        chunks = [np.asarray(c) for c in chunks]
+        for c in chunks:
+            if c.ndim != 2 or c.shape[1] != D:
+                raise ValueError("a chunk must be a [t, %d] array, not one of shape %r" % (D, c.shape))
+        counts = np.array([len(c) for c in chunks], dtype=np.int64)
+        self._room(ids, counts)
+        if not counts.sum():
+            return
+        batch = _hip.Batch(self.decoder.ctx, chunks, dtype=self.decoder.dtype)
+        try:
+            batch.loglik(self.decoder.gmm, fetch=False)
+            self.session.push(batch, ids)
+            self._frames[ids] += counts
+            self.decoder.ctx.sync()                       # (the batch's matrix is read until the sweep is done)
+        finally:
+            batch.close()
+
+    def push_batch(self, ids, batch, first=None, count=None):
+        """Stream ids[u] takes the columns [first[u], first[u] + count[u]) of utterance u of a resident `_hip.Batch`
+        (e.g. from `features_from_signals`; first None: 0, count None: to the utterance's end).  A batch without
+        likelihoods gets them here (once); one that holds a likelihood matrix is taken as it is, so that it can be fed
+        piecewise.  The work is only enqueued: keep the batch alive until the context is synchronised (`result` does)."""
+        ids = self._ids(ids)
+        if batch.U != len(ids):
+            raise ValueError("%d utterances for %d ids" % (batch.U, len(ids)))
+        if batch.D != self.decoder.gmm.D:
+            raise ValueError("the batch has %d feature dimensions, the model %d" % (batch.D, self.decoder.gmm.D))
+        T = np.asarray(batch.lengths, dtype=np.int64)
+        first = np.zeros(len(ids), dtype=np.int64) if first is None else np.asarray(first, dtype=np.int64)
+        count = T - first if count is None else np.asarray(count, dtype=np.int64)
+        if first.shape != T.shape or count.shape != T.shape or np.any(first < 0) or np.any(count < 0) or np.any(first + count > T):
+            raise ValueError("first / count must name column ranges inside the batch's utterances")
+        self._room(ids, count)
+        if not count.sum():
+            return
+        if batch.S is None:
+            batch.loglik(self.decoder.gmm, fetch=False)
+        elif batch.S != self.decoder.gmm.S:
+            raise ValueError("the batch holds likelihoods of %d states, the model has %d" % (batch.S, self.decoder.gmm.S))
+        self.session.push(batch, ids, first, count)
+        self._frames[ids] += count
+
+    def result(self, ids=None, want_path=False):
+        """(word-index lists, dict(end_cost [n, n_end], best_end [n], frames [n][, paths])) of the streams `ids` (None:
+        all) for the frames pushed so far: what `decode_batch` returns for those frames as whole utterances."""
+        ids = np.arange(self.n_streams, dtype=np.int64) if ids is None else self._ids(ids, distinct=False)
+        dec = self.decoder
+        if want_path:
+            r = self.session.result(ids, want_path=True)
+            return [path_to_words(p, dec.row_state, dec.n) for p in r["paths"]], r
+        r = self.session.result(ids, row_label=self._row_word, max_labels=dec._max_labels(self._frames[ids]))
+        return [[int(w) for w in l] for l in r.pop("labels")], r
+
+    def reset(self, ids=None):
+        """The streams `ids` (None: all) start again at frame 0."""
+        ids = None if ids is None else self._ids(ids, distinct=False)
+        self.session.reset(ids)
+        if ids is None:
+            self._frames[:] = 0
+        else:
+            self._frames[ids] = 0
+
+    def finish(self, ids, want_path=False):
+        """`result(ids)` followed by `reset(ids)`: the final decode of utterances that have ended; their ids are free."""
+        out = self.result(ids, want_path=want_path)
+        self.reset(ids)
+        return out
+
+    def close(self):
+        self.session.close()
 
 
 class InFlight:
