@@ -687,6 +687,40 @@ int gh_online_result(gh_ctx* ctx, gh_online* on, int64_t n, const int64_t* ids /
                      int32_t* best_end, const int32_t* row_label, int32_t* labels, const int64_t* label_off /*[n+1]*/,
                      int32_t* n_labels, int32_t* path, const int64_t* path_off /*[n+1]*/, int32_t* path_len);
 
+/* ------------------------------------------------ online decode: the settled prefix and a bounded history
+ * Trace back from EVERY cell of a stream's newest column that is alive (finite carried cost).  Where all those traces
+ * meet in one cell -- the ANCHOR -- everything at and before that cell is part of every result the stream can still
+ * have, whatever audio follows: its words are final and its decision history is dead.  gh_online_commit looks for the
+ * latest such cell in the columns <= frames - 2 (so the anchor is a cell of the current gh_online_result path as well,
+ * which excludes its own end cell) and keeps it per stream on the device; anchors only move forward.  The cell a trace
+ * occupies in a column is the one in which it arrives there from the column behind it (a first state entered through
+ * the loop row is followed to the last state that fed it before the step to the column below).
+ * CONTRACT: the labels of all commits of a stream so far are a prefix of the gh_viterbi_labels sequence of its first k
+ * frames for the current k and every later one.  OUTSIDE the contract: a stream whose end costs are all +inf -- the
+ * one-shot back-trace then starts from a dead cell and runs on its fallback arcs, which need not pass the anchor.
+ * gh_online_create_window: a session whose history holds `window_frames` UNSETTLED frames per stream (frames - settled
+ * frames), rounded up to whole decision words plus one word for the anchor's own: device memory per stream no longer
+ * depends on how long the stream runs, which is bounded by the 32-bit column only.  Same graph forms and refusals as
+ * gh_online_create.  A push that would take any of its streams past the window is refused as a whole (GH_ERR_INVALID,
+ * the message names the stream).  THERE IS NO FORCED COMMIT: a stream whose traces have not met within the window cannot
+ * take more frames; it can be read (gh_online_tail) and reset.  On such a session gh_online_result is
+ * GH_ERR_UNSUPPORTED (paths are not offered); gh_online_commit and gh_online_tail work on both kinds of session, and on
+ * one with full history a commit frees nothing and gh_online_result goes on covering the whole history. */
+int gh_online_create_window(gh_ctx* ctx, const gh_lattices* lat, int64_t n_streams, int64_t window_frames, gh_online** out);
+/* Advances the anchor of the streams ids[0..n) (NULL: all; distinct) and returns what THIS call settled: settled_frames
+ * [n] = anchor column + 1 (0: no anchor yet -- fewer than 2 frames, no live cell, or traces that do not meet), and with
+ * row_label [R] the labels (main.py:59-67) of the path between the previous anchor and the new one, stream ids[i] at
+ * label_off[i] (capacity label_off[i+1] - label_off[i]), n_new_labels [n].  labels may be NULL.  gh_online_reset
+ * clears a stream's anchor.  Synchronises. */
+int gh_online_commit(gh_ctx* ctx, gh_online* on, int64_t n, const int64_t* ids /*[n] or NULL*/, int64_t* settled_frames /*[n]*/,
+                     const int32_t* row_label, int32_t* labels, const int64_t* label_off /*[n+1]*/, int32_t* n_new_labels);
+/* The unsettled tail of the streams ids[0..n) (NULL: all): end_cost [n, n_end] and best_end [n] as gh_online_result, and
+ * the labels of the path from the chosen end down to the anchor -- the words that begin behind the anchor; the settled
+ * labels followed by these are the gh_online_result labels.  A stream without an anchor returns its whole label list.
+ * Any output may be NULL.  Synchronises. */
+int gh_online_tail(gh_ctx* ctx, gh_online* on, int64_t n, const int64_t* ids /*[n] or NULL*/, double* end_cost, int32_t* best_end,
+                   const int32_t* row_label, int32_t* labels, const int64_t* label_off /*[n+1]*/, int32_t* n_labels);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,40 @@
+// The online session (gh_online_*): what gh_viterbi_online.hip (push, result) and gh_online_settle.hip (commit, tail) share.
+#pragma once
+#include "gh_internal.h"
+#include "gh_host.h"
+
+// one stream of one push: `count` frames from row `row0` of the batch's [N, S] likelihood matrix continue stream `stream`
+// at absolute column `t0`
+struct gh_online_slot {
+    int64_t row0;
+    int32_t stream, count, t0, pad;
+};
+
+// the settled prefix of a stream ends in this cell (column < 0: nothing is settled yet)
+struct gh_online_anchor {
+    int32_t col, word, state, pad;
+};
+
+struct gh_online {
+    gh_ctx* ctx;
+    const gh_lattices* lat;        // must outlive the session
+    int64_t n_streams, max_frames, hist_stride;
+    int64_t window;                // > 0: the history is a ring that holds `window` unsettled frames (gh_online_create_window)
+    int32_t ring_words;            // decision words per lane in a stream's history: word index i lives at i % ring_words
+    void* d_arena;
+    double* d_prev;
+    uint32_t* d_open;
+    uint16_t* d_hist;
+    gh_online_anchor* d_anchor;    // [n_streams], valid where settled[stream] > 0
+    gh_online_slot* d_slots;       // [n_streams]: the table of the push in flight
+    gh_online_slot* h_slots;       // page-locked staging of the same size
+    hipEvent_t copied;             // behind the last upload of h_slots
+    bool copy_pending;
+    std::vector<int64_t> frames;   // [n_streams] frames taken so far
+    std::vector<int64_t> settled;  // [n_streams] anchor column + 1 (0: none): host mirror of d_anchor for the push check
+    std::vector<uint8_t> seen;     // [n_streams] scratch of the duplicate check
+};
+
+// End costs and end selection of n streams from their carried columns (gh_viterbi_online.hip)
+int gh_launch_online_end(gh_ctx* ctx, const gh_online* on, const int64_t* d_ids, const int64_t* d_utt_off, int64_t n, double* d_end_cost,
+                         int32_t* d_best_end);

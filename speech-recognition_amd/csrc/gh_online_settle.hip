@@ -1,0 +1,439 @@
+// The SETTLED PREFIX of an online stream (gh_online_commit, gh_online_tail): the part of the running hypothesis that no
+// later audio can change, and with it the part of the decision history that is dead.
+//
+// Every hypothesis a stream can still end in is the back-trace of some cell of its newest column that is alive (finite
+// carried cost).  Trace back from ALL of them at once: where the traces meet in one cell -- the ANCHOR -- everything at and
+// before that cell is common to every future result.  A trace is a function of the decision bits alone, so the set of cells
+// the traces occupy can only shrink going back, the first column (from the newest) in which it has one member is the latest
+// such column, and below it nothing has to be looked at.  The cell a trace occupies "in column c" is the one in which it
+// ARRIVES there from column c + 1: a first state that was entered from the loop row is followed through the loop row to the
+// last state that fed it (same column) before the step to the column below.
+//
+// online_settle_kernel -- the mapping of the loop kernels: FOUR STREAMS PER WAVE, DPP row = stream, lane = word.  A lane
+// holds the live states of its word as a bit mask and maps it through its OWN decision word (64 contiguous bytes per row and
+// CPW columns), so a column step is one load per lane and a few bit operations however many cells are alive; lane = stream
+// would walk every live cell's trace on its own, 16 N of them with scattered loads.  The loop-row hop is the only thing
+// that crosses lanes: a row ballot of the lanes that take it, and the lowest lane of the column's `cand == rm` bits gets
+// bit N - 1.  The size of the set is a DPP row sum of popcounts.  Cost: O(unsettled tail) per stream.
+// online_segment_kernel -- ONE path from a cell down to an anchor (or to column 0), lane = stream as in
+// lattice_backtrace_kernel, with the label rule of that kernel's MODE 1: the newly settled words (new anchor -> old anchor)
+// and the words of the unsettled tail (best end -> anchor).
+// Bit layout: gh_loop_hb / gh_loop_cpw (gh_viterbi.h); tie rules: the LOOP branch of lattice_backtrace_kernel.  A finite
+// cell has only finite predecessors, so the "+inf: first existing arc" fallback is never taken by the settle walk; the
+// segment walk keeps it, because the chosen end of a stream may be a +inf cell (the one-shot decode's rule for it).
+#include "gh_online.h"
+#include "gh_viterbi.h"
+#include "gh_wave.h"
+
+struct gh_settle_task {
+    int32_t stream, T, has_anchor, pad;
+};
+
+struct gh_settle_args {
+    const gh_layerform* lf;
+    const int32_t* end_rows;
+    const gh_settle_task* tasks;
+    int64_t n;
+    const double* prev;            // [n_streams][N][16]
+    const uint16_t* hist;          // stream k at k * hist_stride (uint16 units), word index i at i % ring_words
+    int64_t hist_stride;
+    int ring_words;
+    gh_online_anchor* anchor;      // [n_streams]
+    gh_online_anchor* cand;        // [n]: the settle walk's result (commit), null in tail mode
+    const int32_t* best_end;       // [n] (tail mode)
+    const int32_t* row_label;
+    int32_t* labels;
+    const int64_t* label_off;
+    int32_t* n_labels;
+    int64_t* settled_frames;       // [n] (commit)
+    int* flag;
+};
+
+namespace {
+
+__device__ __forceinline__ int row_sum16(int v) {
+    v += dpp_mov<0x121>(v);
+    v += dpp_mov<0x122>(v);
+    v += dpp_mov<0x124>(v);
+    v += dpp_mov<0x128>(v);
+    return v;
+}
+
+template <int N, bool SKIP>
+__global__ __launch_bounds__(64) void online_settle_kernel(gh_settle_args a) {
+    constexpr int HB = gh_loop_hb(N, SKIP), CPW = gh_loop_cpw(N, SKIP);
+    constexpr uint32_t HBM = (uint32_t)((1ull << HB) - 1ull);
+    static_assert(CPW >= 1 && N <= 16, "decision bits of a column must fit one word, the states of a word one mask");
+    const int lane = threadIdx.x, kk = lane >> 4, w = lane & 15;
+    const int W = a.lf->W;
+    const int64_t i = (int64_t)blockIdx.x * 4 + kk;
+    const bool has = i < a.n;
+    gh_settle_task tk;
+    tk.stream = 0; tk.T = 0; tk.has_anchor = 0; tk.pad = 0;
+    if (has) tk = a.tasks[i];
+    gh_online_anchor old;
+    old.col = -1; old.word = 0; old.state = 0; old.pad = 0;
+    if (has && tk.has_anchor) old = a.anchor[tk.stream];
+    const int lo = old.col >= 0 ? old.col : 0;                  // every trace passes the old anchor: the walk ends there
+    const int ring = a.ring_words;
+    const double INF = INFINITY;
+    // the start set: the emitting cells of the newest column that are alive
+    uint32_t mask = 0;
+    if (has && tk.T >= 2 && w < W) {
+        const double* st = a.prev + ((int64_t)tk.stream * N) * 16 + w;
+#pragma unroll
+        for (int s = 0; s < N; ++s) mask |= (uint32_t)(st[s * 16] < INF) << s;
+    }
+    int j = tk.T - 1;
+    bool active = row_sum16(__popc(mask)) > 0 && j > lo;        // row-uniform
+    const uint32_t* hp = reinterpret_cast<const uint32_t*>(a.hist + (int64_t)tk.stream * a.hist_stride) + w;
+    int ci = active ? j % CPW : 0, wr = active ? (j / CPW) % ring : 0, held = -1;
+    uint32_t word = 0;
+    int flag = 0;
+    bool mine = false;                                          // this lane holds the anchor: (j, w, lowest bit of mask)
+    while (__ballot(active)) {
+        // ---- one column step back, j -> j - 1, through the decisions of column j ----
+        if (active && wr != held) { word = hp[(int64_t)wr * 16]; held = wr; }
+        const uint32_t hb = (word >> ((CPW - 1 - ci) * HB)) & HBM;
+        // first states: self keeps the bit; the loop row hands it to the last state of the column's best word (same column)
+        const bool b0 = mask & 1u, b_l = (hb >> 1) & 1u, b_s = hb & 1u;
+        const uint32_t hops = (uint32_t)(__ballot(active && b0 && !b_s && b_l) >> (kk * 16)) & 0xffffu;
+        const uint32_t eq = (uint32_t)(__ballot(active && w < W && ((hb >> 2) & 1u)) >> (kk * 16)) & 0xffffu;
+        if (active && b0 && !b_s) {
+            mask &= ~1u;
+            if (!b_l) flag |= 2;                                // the start row, in a column > 0
+        }
+        if (hops) {
+            if (!eq) flag |= 2;
+            else if (w == __ffs(eq) - 1) mask |= 1u << (N - 1); // lowest word = lowest origin row (np.argmin)
+        }
+        uint32_t nm = mask & 1u;
+        int before = 0;
+#pragma unroll
+        for (int s = N - 1; s >= 1; --s) {
+            int code;
+            if (SKIP && s >= 2) {
+                const int b_a = (hb >> (HB - 1 - before)) & 1, b_b = (hb >> (HB - 2 - before)) & 1;
+                code = b_b ? 0 : (b_a ? 1 : 2);
+                before += 2;
+            } else {
+                code = ((hb >> (HB - 1 - before)) & 1) ? 0 : 1;
+                before += 1;
+            }
+            if ((mask >> s) & 1u) nm |= 1u << (s - code);
+        }
+        if (active) {
+            mask = nm;
+            --j;
+            if (ci == 0) { ci = CPW - 1; wr = wr == 0 ? ring - 1 : wr - 1; } else --ci;
+        }
+        const int size = row_sum16(__popc(mask));
+        if (active && size == 1) {
+            mine = mask != 0;
+            active = false;
+        } else if (active && j <= lo) {
+            if (old.col >= 0) flag |= 2;                        // the traces did not meet in the old anchor
+            active = false;
+        }
+    }
+    if (flag) atomicOr(a.flag, flag);
+    const uint32_t found = (uint32_t)(__ballot(mine) >> (kk * 16)) & 0xffffu;
+    if (has && (found ? mine : w == 0)) {
+        gh_online_anchor c = old;                               // nothing new: the anchor stays
+        if (mine) { c.col = j; c.word = w; c.state = __ffs(mask) - 1; c.pad = 0; }
+        a.cand[i] = c;
+    }
+}
+
+// One path, lane = stream.  Commit mode (a.cand): from the new anchor (visited) down to the old one; tail mode: from the
+// chosen end of the newest column (not visited, as in the one-shot back-trace) down to the anchor.  Without an anchor the
+// walk ends in column 0 like the one-shot back-trace.  Labels: MODE 1 of lattice_backtrace_kernel; the run of labelled rows
+// the anchor lies in belongs to the settled side, so the label pending on arrival is dropped.
+template <int N, bool SKIP>
+__global__ __launch_bounds__(64) void online_segment_kernel(gh_settle_args a) {
+    constexpr int HB = gh_loop_hb(N, SKIP), CPW = gh_loop_cpw(N, SKIP);
+    constexpr uint32_t HBM = (uint32_t)((1ull << HB) - 1ull);
+    __shared__ uint8_t s_arcs[GH_LAYERS_ROWW * GH_LAYERS_MAXN];
+    const gh_layerform* __restrict__ lf = a.lf;
+    for (int k = threadIdx.x; k < GH_LAYERS_ROWW * GH_LAYERS_MAXN; k += 64) s_arcs[k] = (&lf->arcs[0][0])[k];
+    __syncthreads();
+    const int W = lf->W, Lr = lf->loop_row;
+    const int64_t i = (int64_t)blockIdx.x * 64 + threadIdx.x;
+    if (i >= a.n) return;
+    const gh_settle_task tk = a.tasks[i];
+    const bool commit = a.cand != nullptr;
+    gh_online_anchor stop;
+    stop.col = -1; stop.word = 0; stop.state = 0; stop.pad = 0;
+    if (tk.has_anchor) stop = a.anchor[tk.stream];
+    auto row_of = [&](int ww, int ss) { return ss == 0 ? Lr + 1 + ww : 1 + ww * (N - 1) + (ss - 1); };
+    int j, bw, bs;
+    bool strict = true;                                         // a walk that misses the anchor is an internal error
+    if (commit) {
+        const gh_online_anchor c = a.cand[i];
+        a.settled_frames[i] = c.col + 1;
+        if (c.col < 0 || c.col == stop.col) { if (a.n_labels) a.n_labels[i] = 0; return; }
+        a.anchor[tk.stream] = c;
+        if (!a.labels) return;
+        j = c.col; bw = c.word; bs = c.state;
+    } else {
+        const int be = a.best_end[i];
+        if (tk.T <= 1 || be < 0) { a.n_labels[i] = 0; return; }
+        const int r = a.end_rows[be];
+        if (r > Lr) { bw = r - Lr - 1; bs = 0; } else { bw = (r - 1) / (N - 1); bs = (r - 1) % (N - 1) + 1; }
+        j = tk.T - 1;
+        // (a +inf end is traced on the fallback arcs, which need not lead to the anchor: outside the contract, not an error)
+        strict = a.prev[((int64_t)tk.stream * N + bs) * 16 + bw] < INFINITY;
+    }
+    const int lo = stop.col >= 0 ? stop.col : 0;
+    const uint32_t* bpu = reinterpret_cast<const uint32_t*>(a.hist + (int64_t)tk.stream * a.hist_stride);
+    int32_t* labs = a.labels + a.label_off[i];
+    const int64_t cap = a.label_off[i + 1] - a.label_off[i];
+    const int ring = a.ring_words;
+    int64_t len = 0;
+    int prev_label = -1, kind = 0, flag = 0;
+    int hwi = -1, hwr = 0;                                      // word index whose ring position is held
+    int64_t key = -1;
+    uint32_t cw = 0;
+    auto visit = [&](int row) {
+        const int l = a.row_label[row];
+        if (prev_label >= 0 && l < 0) {
+            if (len >= cap) { flag |= 8; return; }
+            labs[cap - 1 - len] = prev_label;
+            ++len;
+        }
+        prev_label = l;
+    };
+    if (commit) visit(row_of(bw, bs));
+    while (j > lo && !flag) {
+        const int wi = j / CPW;
+        const int shift = (CPW - 1 - j % CPW) * HB;
+        if (wi != hwi) { hwr = wi % ring; hwi = wi; }
+        if (kind == 0) {
+            const int64_t want = (int64_t)hwr * 16 + bw;
+            if (want != key) { cw = bpu[want]; key = want; }
+            const uint32_t hb = (cw >> shift) & HBM;
+            const int arcs = s_arcs[bw * GH_LAYERS_MAXN + bs];
+            if (bs >= 1) {
+                int before = 0;
+                for (int s2 = N - 1; s2 > bs; --s2) before += (SKIP && s2 >= 2) ? 2 : 1;
+                int code;
+                if (SKIP && bs >= 2) {
+                    const int b_a = (hb >> (HB - 1 - before)) & 1, b_b = (hb >> (HB - 2 - before)) & 1;
+                    code = b_b ? 0 : (b_a ? 1 : 2);
+                } else {
+                    code = ((hb >> (HB - 1 - before)) & 1) ? 0 : 1;
+                }
+                if (!((arcs >> code) & 1)) code = (arcs & 4) ? 2 : (arcs & 2) ? 1 : (arcs & 1) ? 0 : -1;
+                if (code < 0) { flag |= 2; break; }
+                bs -= code;
+                --j;
+                visit(row_of(bw, bs));
+            } else {
+                const int b_l = (hb >> 1) & 1, b_s = hb & 1;
+                int pick = b_s ? 0 : (b_l ? 3 : 4);
+                if (!((arcs >> pick) & 1)) pick = (arcs & 16) ? 4 : (arcs & 8) ? 3 : (arcs & 1) ? 0 : -1;
+                if (pick == 0) { --j; visit(row_of(bw, 0)); }
+                else if (pick == 3) { kind = 1; visit(Lr); }
+                else { flag |= 2; break; }                      // no origin, or the start row in a column > 0
+            }
+        } else {
+            const uint4* rowp = reinterpret_cast<const uint4*>(bpu + (int64_t)hwr * 16);
+            int found = -1;
+#pragma unroll
+            for (int q4 = 3; q4 >= 0; --q4) {
+                const uint4 v = rowp[q4];
+                if ((v.w >> (shift + 2)) & 1u) found = 4 * q4 + 3;
+                if ((v.z >> (shift + 2)) & 1u) found = 4 * q4 + 2;
+                if ((v.y >> (shift + 2)) & 1u) found = 4 * q4 + 1;
+                if ((v.x >> (shift + 2)) & 1u) found = 4 * q4;
+            }
+            if (found < 0 || found >= W) { flag |= 2; break; }
+            bw = found;
+            bs = N - 1;
+            kind = 0;
+            visit(row_of(bw, bs));
+        }
+    }
+    if (!flag && stop.col >= 0) {
+        if (bw != stop.word || bs != stop.state) { if (strict) flag |= 2; }
+        prev_label = -1;                                        // the anchor's own run is settled already
+    }
+    if (flag) atomicOr(a.flag, flag);
+    if (!flag && prev_label >= 0) {
+        if (len >= cap) atomicOr(a.flag, 8);
+        else { labs[cap - 1 - len] = prev_label; ++len; }
+    }
+    for (int64_t k = 0; k < len; ++k) labs[k] = labs[cap - len + k];
+    a.n_labels[i] = (int32_t)len;
+}
+
+int launch_settle(gh_ctx* ctx, const gh_settle_args& a, const gh_layerform& f, bool settle, const char* who) {
+    const dim3 blk(64);
+    const dim3 grid((unsigned)(settle ? (a.n + 3) / 4 : (a.n + 63) / 64));
+#define GH_ST(ET, NN, SK)                                                                                    \
+    do {                                                                                                     \
+        if (settle) hipLaunchKernelGGL((online_settle_kernel<NN, SK>), grid, blk, 0, ctx->stream, a);        \
+        else hipLaunchKernelGGL((online_segment_kernel<NN, SK>), grid, blk, 0, ctx->stream, a);              \
+    } while (0)
+    GH_NSKIP_SWITCH(f.N, f.skip, 16, GH_ST, , "%s: loop form with %d states per word", who, f.N)
+#undef GH_ST
+    GH_HIP(hipGetLastError());
+    return GH_OK;
+}
+
+// the streams a call names (NULL: all), checked; `distinct`: a stream may be named once
+int tasks_of(gh_online* on, const char* who, int64_t& n, const int64_t* ids, bool distinct, std::vector<gh_settle_task>& tasks) {
+    if (!ids) n = on->n_streams;
+    tasks.resize((size_t)std::max<int64_t>(n, 0));
+    for (int64_t i = 0; i < n; ++i) {
+        const int64_t id = ids ? ids[i] : i;
+        GH_REQUIRE(id >= 0 && id < on->n_streams, "%s: stream %lld out of range [0, %lld)", who, (long long)id, (long long)on->n_streams);
+        gh_settle_task& t = tasks[(size_t)i];
+        t.stream = (int32_t)id; t.T = (int32_t)on->frames[(size_t)id]; t.has_anchor = on->settled[(size_t)id] > 0; t.pad = 0;
+    }
+    if (distinct && ids) {
+        int64_t twice = -1, k = 0;
+        for (; k < n && twice < 0; ++k) {
+            if (on->seen[(size_t)ids[k]]) twice = ids[k];
+            on->seen[(size_t)ids[k]] = 1;
+        }
+        for (int64_t q = 0; q < k; ++q) on->seen[(size_t)ids[q]] = 0;
+        GH_REQUIRE(twice < 0, "%s: stream %lld is named twice", who, (long long)twice);
+    }
+    return GH_OK;
+}
+
+}  // namespace
+
+// --------------------------------------------------------------------------------------------------------------- C ABI
+extern "C" int gh_online_commit(gh_ctx* ctx, gh_online* on, int64_t n, const int64_t* ids, int64_t* settled_frames,
+                                const int32_t* row_label, int32_t* labels, const int64_t* label_off, int32_t* n_new_labels) {
+    GH_REQUIRE(ctx && on, "gh_online_commit: NULL argument");
+    GH_REQUIRE(ctx == on->ctx, "gh_online_commit: the session belongs to another context");
+    GH_REQUIRE(!labels || (row_label && label_off && n_new_labels), "gh_online_commit: labels need row_label, label_off and n_new_labels");
+    std::vector<gh_settle_task> tasks;
+    int rc = tasks_of(on, "gh_online_commit", n, ids, true, tasks);
+    if (rc) return rc;
+    if (n <= 0) return GH_OK;
+    const gh_lattices* lat = on->lat;
+    const gh_layerform& f = lat->h_layers;
+    const int R = lat->lat[0].R;
+    GH_HIP(hipSetDevice(ctx->device));
+    int* d_flag;
+    gh_settle_task* d_tasks;
+    gh_online_anchor* d_cand;
+    int64_t *d_settled, *d_labeloff = nullptr;
+    int32_t *d_rowlabel = nullptr, *d_nlabels = nullptr, *d_labels = nullptr;
+    Carver cv;
+    cv.add(&d_flag, 64); cv.add(&d_tasks, (size_t)n); cv.add(&d_cand, (size_t)n); cv.add(&d_settled, (size_t)n);
+    if (labels) { cv.add(&d_rowlabel, (size_t)R); cv.add(&d_labeloff, (size_t)n + 1); cv.add(&d_nlabels, (size_t)n); cv.add(&d_labels, (size_t)label_off[n] + 1); }
+    rc = cv.commit(ctx);
+    if (rc) return rc;
+    hipStream_t st = ctx->stream;
+    GH_HIP(hipMemsetAsync(d_flag, 0, sizeof(int), st));
+    GH_HIP(hipMemcpyAsync(d_tasks, tasks.data(), (size_t)n * sizeof(gh_settle_task), hipMemcpyHostToDevice, st));
+    if (labels) {
+        GH_HIP(hipMemcpyAsync(d_rowlabel, row_label, (size_t)R * 4, hipMemcpyHostToDevice, st));
+        GH_HIP(hipMemcpyAsync(d_labeloff, label_off, (size_t)(n + 1) * 8, hipMemcpyHostToDevice, st));
+    }
+    gh_settle_args a;
+    memset(&a, 0, sizeof a);
+    a.lf = lat->d_layers; a.end_rows = lat->d_end_rows; a.tasks = d_tasks; a.n = n; a.prev = on->d_prev; a.hist = on->d_hist;
+    a.hist_stride = on->hist_stride; a.ring_words = on->ring_words; a.anchor = on->d_anchor; a.cand = d_cand;
+    a.row_label = d_rowlabel; a.labels = d_labels; a.label_off = d_labeloff; a.n_labels = d_nlabels; a.settled_frames = d_settled;
+    a.flag = d_flag;
+    rc = launch_settle(ctx, a, f, true, "gh_online_commit");
+    if (rc) return rc;
+    rc = launch_settle(ctx, a, f, false, "gh_online_commit");
+    if (rc) return rc;
+    int flag = 0;
+    std::vector<int64_t> h_settled((size_t)n);
+    GH_HIP(hipMemcpyAsync(&flag, d_flag, sizeof(int), hipMemcpyDeviceToHost, st));
+    GH_HIP(hipMemcpyAsync(h_settled.data(), d_settled, (size_t)n * 8, hipMemcpyDeviceToHost, st));
+    if (labels) {
+        GH_HIP(hipMemcpyAsync(n_new_labels, d_nlabels, (size_t)n * 4, hipMemcpyDeviceToHost, st));
+        if (label_off[n] > 0) GH_HIP(hipMemcpyAsync(labels, d_labels, (size_t)label_off[n] * 4, hipMemcpyDeviceToHost, st));
+    }
+    GH_HIP(hipStreamSynchronize(st));
+    // (the anchors on the device have moved whatever the flag says: the mirror follows them)
+    for (int64_t i = 0; i < n; ++i) on->settled[(size_t)tasks[(size_t)i].stream] = h_settled[(size_t)i];
+    if (settled_frames) memcpy(settled_frames, h_settled.data(), (size_t)n * 8);
+    if (flag & 2) {
+        gh_set_error("gh_online_commit: a trace reached a cell without predecessor or missed the anchor");
+        return GH_ERR_INVALID;
+    }
+    if (flag & 8) {
+        gh_set_error("gh_online_commit: label capacity of a stream too small");
+        return GH_ERR_INVALID;
+    }
+    return GH_OK;
+}
+
+extern "C" int gh_online_tail(gh_ctx* ctx, gh_online* on, int64_t n, const int64_t* ids, double* end_cost, int32_t* best_end,
+                              const int32_t* row_label, int32_t* labels, const int64_t* label_off, int32_t* n_labels) {
+    GH_REQUIRE(ctx && on, "gh_online_tail: NULL argument");
+    GH_REQUIRE(ctx == on->ctx, "gh_online_tail: the session belongs to another context");
+    GH_REQUIRE(!labels || (row_label && label_off && n_labels), "gh_online_tail: labels need row_label, label_off and n_labels");
+    std::vector<gh_settle_task> tasks;
+    int rc = tasks_of(on, "gh_online_tail", n, ids, false, tasks);
+    if (rc) return rc;
+    if (n <= 0) return GH_OK;
+    const gh_lattices* lat = on->lat;
+    const gh_layerform& f = lat->h_layers;
+    const int n_end = lat->lat[0].n_end, R = lat->lat[0].R;
+    std::vector<int64_t> h_ids((size_t)n), utt_off((size_t)n + 1, 0);
+    for (int64_t i = 0; i < n; ++i) {
+        h_ids[(size_t)i] = tasks[(size_t)i].stream;
+        utt_off[(size_t)i + 1] = utt_off[(size_t)i] + tasks[(size_t)i].T;
+    }
+    GH_HIP(hipSetDevice(ctx->device));
+    int* d_flag;
+    gh_settle_task* d_tasks;
+    double* d_endcost;
+    int64_t *d_ids, *d_uttoff, *d_labeloff = nullptr;
+    int32_t *d_best, *d_rowlabel = nullptr, *d_nlabels = nullptr, *d_labels = nullptr;
+    Carver cv;
+    cv.add(&d_flag, 64); cv.add(&d_tasks, (size_t)n); cv.add(&d_best, (size_t)n); cv.add(&d_endcost, (size_t)n * n_end);
+    cv.add(&d_ids, (size_t)n); cv.add(&d_uttoff, (size_t)n + 1);
+    if (labels) { cv.add(&d_rowlabel, (size_t)R); cv.add(&d_labeloff, (size_t)n + 1); cv.add(&d_nlabels, (size_t)n); cv.add(&d_labels, (size_t)label_off[n] + 1); }
+    rc = cv.commit(ctx);
+    if (rc) return rc;
+    hipStream_t st = ctx->stream;
+    GH_HIP(hipMemsetAsync(d_flag, 0, sizeof(int), st));
+    GH_HIP(hipMemcpyAsync(d_tasks, tasks.data(), (size_t)n * sizeof(gh_settle_task), hipMemcpyHostToDevice, st));
+    GH_HIP(hipMemcpyAsync(d_ids, h_ids.data(), (size_t)n * 8, hipMemcpyHostToDevice, st));
+    GH_HIP(hipMemcpyAsync(d_uttoff, utt_off.data(), (size_t)(n + 1) * 8, hipMemcpyHostToDevice, st));
+    if (labels) {
+        GH_HIP(hipMemcpyAsync(d_rowlabel, row_label, (size_t)R * 4, hipMemcpyHostToDevice, st));
+        GH_HIP(hipMemcpyAsync(d_labeloff, label_off, (size_t)(n + 1) * 8, hipMemcpyHostToDevice, st));
+    }
+    rc = gh_launch_online_end(ctx, on, d_ids, d_uttoff, n, d_endcost, d_best);
+    if (rc) return rc;
+    if (labels) {
+        gh_settle_args a;
+        memset(&a, 0, sizeof a);
+        a.lf = lat->d_layers; a.end_rows = lat->d_end_rows; a.tasks = d_tasks; a.n = n; a.prev = on->d_prev; a.hist = on->d_hist;
+        a.hist_stride = on->hist_stride; a.ring_words = on->ring_words; a.anchor = on->d_anchor; a.best_end = d_best;
+        a.row_label = d_rowlabel; a.labels = d_labels; a.label_off = d_labeloff; a.n_labels = d_nlabels; a.flag = d_flag;
+        rc = launch_settle(ctx, a, f, false, "gh_online_tail");
+        if (rc) return rc;
+    }
+    int flag = 0;
+    GH_HIP(hipMemcpyAsync(&flag, d_flag, sizeof(int), hipMemcpyDeviceToHost, st));
+    if (best_end) GH_HIP(hipMemcpyAsync(best_end, d_best, (size_t)n * 4, hipMemcpyDeviceToHost, st));
+    if (end_cost) GH_HIP(hipMemcpyAsync(end_cost, d_endcost, (size_t)n * n_end * 8, hipMemcpyDeviceToHost, st));
+    if (labels) {
+        GH_HIP(hipMemcpyAsync(n_labels, d_nlabels, (size_t)n * 4, hipMemcpyDeviceToHost, st));
+        if (label_off[n] > 0) GH_HIP(hipMemcpyAsync(labels, d_labels, (size_t)label_off[n] * 4, hipMemcpyDeviceToHost, st));
+    }
+    GH_HIP(hipStreamSynchronize(st));
+    if (flag & 2) {
+        gh_set_error("gh_online_tail: back-trace reached a cell without predecessor or missed the anchor");
+        return GH_ERR_INVALID;
+    }
+    if (flag & 8) {
+        gh_set_error("gh_online_tail: label capacity of a stream too small");
+        return GH_ERR_INVALID;
+    }
+    return GH_OK;
+}

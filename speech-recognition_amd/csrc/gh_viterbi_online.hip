@@ -15,17 +15,14 @@
 // candidate order, same strict '<', same decision bits); what differs is where `prev` and `word` come from and go to,
 // and that the start-row term and the decision-word index use the absolute column.  A chunk moves 16 N 8 B of state in
 // and out and 64 B of open word per stream beside its emissions and decisions.
-#include "gh_internal.h"
-#include "gh_host.h"
+//
+// The history is addressed as a RING: decision word index i of a stream lives at i % ring_words.  A session created with a
+// capacity (gh_online_create) has a ring as long as its last word index, so nothing ever wraps and it writes the bytes it
+// always wrote; one created with a window (gh_online_create_window) holds `window` unsettled frames and one word of slack
+// for the word the anchor lies in (gh_online_settle.hip: what is settled, and why the frames before it are dead).
+#include "gh_online.h"
 #include "gh_viterbi.h"
 #include "gh_wave.h"
-
-// one stream of one push: `count` frames from row `row0` of the batch's [N, S] likelihood matrix continue stream `stream`
-// at absolute column `t0`
-struct gh_online_slot {
-    int64_t row0;
-    int32_t stream, count, t0, pad;
-};
 
 struct gh_online_args {
     const gh_layerform* lf;
@@ -37,22 +34,7 @@ struct gh_online_args {
     uint32_t* open;        // [n_streams][16]
     uint16_t* hist;        // decision words, stream k at k * hist_stride (uint16 units, as gh_layers_args::bp)
     int64_t hist_stride;
-};
-
-struct gh_online {
-    gh_ctx* ctx;
-    const gh_lattices* lat;        // must outlive the session
-    int64_t n_streams, max_frames, hist_stride;
-    void* d_arena;
-    double* d_prev;
-    uint32_t* d_open;
-    uint16_t* d_hist;
-    gh_online_slot* d_slots;       // [n_streams]: the table of the push in flight
-    gh_online_slot* h_slots;       // page-locked staging of the same size
-    hipEvent_t copied;             // behind the last upload of h_slots
-    bool copy_pending;
-    std::vector<int64_t> frames;   // [n_streams] frames taken so far
-    std::vector<uint8_t> seen;     // [n_streams] scratch of the duplicate check
+    int ring_words;        // word index i of a stream lives at i % ring_words
 };
 
 namespace {
@@ -112,6 +94,8 @@ __global__ __launch_bounds__(64) void viterbi_online_kernel(gh_online_args a) {
     for (int s = 0; s < N; ++s) prev[s] = carried ? st[s * 16] : INF;
     uint32_t word = (carried && tb % CPW != 0) ? *op : 0u;
     uint32_t* bp = reinterpret_cast<uint32_t*>(a.hist + (int64_t)sl.stream * a.hist_stride) + w;
+    const int n_ring = a.ring_words;
+    int wr = (tb / CPW) % n_ring;                               // ring position of the open word; it moves on as words fill
 
     for (int t0 = 0; t0 < Tmax; t0 += PF) {
 #pragma unroll
@@ -156,12 +140,13 @@ __global__ __launch_bounds__(64) void viterbi_online_kernel(gh_online_args a) {
                 prev[0] = vmin(vmin(base0, m2) + e[0], INF);
                 const int ci = ta % CPW;
                 if (ci == CPW - 1) {
-                    bp[(int64_t)(ta / CPW) * 16] = word;
+                    bp[(int64_t)wr * 16] = word;
                     word = 0;
+                    wr = wr + 1 == n_ring ? 0 : wr + 1;
                 } else if (t == T - 1) {
                     // the chunk ends inside a word: the history shows it left aligned (what the one-shot sweep leaves behind
                     // its last column), the state keeps the pushed bits for the next chunk
-                    bp[(int64_t)(ta / CPW) * 16] = word << (HB * (CPW - 1 - ci));
+                    bp[(int64_t)wr * 16] = word << (HB * (CPW - 1 - ci));
                 }
             }
             {   // the slot's refill: unconditional, from a clamped column, outside the divergent region (viterbi_loop_kernel)
@@ -222,14 +207,13 @@ int launch_online(gh_ctx* ctx, const gh_online_args& a, const gh_layerform& f, b
     return GH_OK;
 }
 
-}  // namespace
-
-// --------------------------------------------------------------------------------------------------------------- C ABI
-extern "C" int gh_online_create(gh_ctx* ctx, const gh_lattices* lat, int64_t n_streams, int64_t max_frames, gh_online** out) {
-    GH_REQUIRE(ctx && lat && out, "gh_online_create: NULL argument");
+// a session with history for `frames` frames per stream: all a stream will ever take, or (window) its unsettled tail
+int online_create(gh_ctx* ctx, const gh_lattices* lat, int64_t n_streams, int64_t frames, bool window, gh_online** out) {
+    const char* const who = window ? "gh_online_create_window" : "gh_online_create";
+    GH_REQUIRE(ctx && lat && out, "%s: NULL argument", who);
     *out = nullptr;
-    GH_REQUIRE(n_streams >= 1 && n_streams <= 0x7fffffff, "gh_online_create: n_streams=%lld", (long long)n_streams);
-    GH_REQUIRE(max_frames >= 1 && max_frames <= 0x7fffffff, "gh_online_create: max_frames=%lld", (long long)max_frames);
+    GH_REQUIRE(n_streams >= 1 && n_streams <= 0x7fffffff, "%s: n_streams=%lld", who, (long long)n_streams);
+    GH_REQUIRE(frames >= 1 && frames <= 0x7fffffff, "%s: %s=%lld", who, window ? "window_frames" : "max_frames", (long long)frames);
     const char* why = nullptr;
     if (lat->L != 1 || lat->deferred_src) why = "several graphs (one word-loop graph serves all streams)";
     else if (lat->beam > 0) why = "a rank beam is set on the graph";
@@ -238,26 +222,33 @@ extern "C" int gh_online_create(gh_ctx* ctx, const gh_lattices* lat, int64_t n_s
     else if (!lat->layers_ok || lat->h_layers.loop != 1) why = "a graph that is not in loop form";
     else if (lat->h_layers.W > GH_LAYERS_ROWW) why = "more than 16 words";
     if (why) {
-        gh_set_error("gh_online_create: online decoding takes the word-loop grammar with up to %d words, not %s", GH_LAYERS_ROWW, why);
+        gh_set_error("%s: online decoding takes the word-loop grammar with up to %d words, not %s", who, GH_LAYERS_ROWW, why);
         return GH_ERR_UNSUPPORTED;
     }
     GH_HIP(hipSetDevice(ctx->device));
     const gh_layerform& f = lat->h_layers;
     gh_online* on = new gh_online();
-    on->ctx = ctx; on->lat = lat; on->n_streams = n_streams; on->max_frames = max_frames;
-    on->hist_stride = (int64_t)gh_bp_entries(max_frames, gh_loop_cpw(f.N, f.skip != 0), 16, 32);
+    on->ctx = ctx; on->lat = lat; on->n_streams = n_streams;
+    // a window: whole decision words, one more for the word the anchor lies in; the stream itself ends with the 32-bit column
+    const int cpw = gh_loop_cpw(f.N, f.skip != 0);
+    on->max_frames = window ? 0x7fffffff : frames;
+    on->window = window ? frames : 0;
+    on->ring_words = (int32_t)((frames + cpw - 1) / cpw + (window ? 1 : 0));
+    on->hist_stride = (int64_t)on->ring_words * 16 * 2;
     on->d_arena = nullptr; on->h_slots = nullptr; on->copied = nullptr; on->copy_pending = false;
     on->frames.assign((size_t)n_streams, 0);
+    on->settled.assign((size_t)n_streams, 0);
     on->seen.assign((size_t)n_streams, 0);
     auto pad = [](size_t b) { return (b + 255) & ~size_t(255); };
     const size_t b_prev = pad((size_t)n_streams * f.N * 16 * sizeof(double)), b_open = pad((size_t)n_streams * 16 * 4);
     const size_t b_hist = pad((size_t)n_streams * (size_t)on->hist_stride * 2), b_slots = pad((size_t)n_streams * sizeof(gh_online_slot));
-    hipError_t e = hipMalloc(&on->d_arena, b_prev + b_open + b_hist + b_slots);
+    const size_t b_anchor = pad((size_t)n_streams * sizeof(gh_online_anchor));
+    hipError_t e = hipMalloc(&on->d_arena, b_prev + b_open + b_hist + b_slots + b_anchor);
     if (e == hipSuccess) e = hipHostMalloc((void**)&on->h_slots, b_slots, hipHostMallocDefault);
     if (e == hipSuccess) e = hipEventCreateWithFlags(&on->copied, hipEventDisableTiming);
     if (e != hipSuccess) {
-        gh_set_error("gh_online_create: %lld streams x %lld frames (%zu bytes): %s", (long long)n_streams, (long long)max_frames,
-                     b_prev + b_open + b_hist + b_slots, hipGetErrorString(e));
+        gh_set_error("%s: %lld streams x %lld frames (%zu bytes): %s", who, (long long)n_streams, (long long)frames,
+                     b_prev + b_open + b_hist + b_slots + b_anchor, hipGetErrorString(e));
         gh_online_destroy(on);
         return e == hipErrorOutOfMemory ? GH_ERR_NOMEM : GH_ERR_HIP;
     }
@@ -265,9 +256,29 @@ extern "C" int gh_online_create(gh_ctx* ctx, const gh_lattices* lat, int64_t n_s
     on->d_prev = reinterpret_cast<double*>(p); p += b_prev;
     on->d_open = reinterpret_cast<uint32_t*>(p); p += b_open;
     on->d_hist = reinterpret_cast<uint16_t*>(p); p += b_hist;
-    on->d_slots = reinterpret_cast<gh_online_slot*>(p);
+    on->d_slots = reinterpret_cast<gh_online_slot*>(p); p += b_slots;
+    on->d_anchor = reinterpret_cast<gh_online_anchor*>(p);   // (read only where `settled` says a stream has one)
     *out = on;
     return GH_OK;
+}
+
+}  // namespace
+
+int gh_launch_online_end(gh_ctx* ctx, const gh_online* on, const int64_t* d_ids, const int64_t* d_utt_off, int64_t n, double* d_end_cost,
+                         int32_t* d_best_end) {
+    hipLaunchKernelGGL(online_end_kernel, dim3((unsigned)((n + 3) / 4)), dim3(64), 0, ctx->stream, on->lat->d_layers, on->lat->d_lf_end_slot,
+                       on->lat->lat[0].n_end, on->d_prev, d_ids, d_utt_off, n, d_end_cost, d_best_end);
+    GH_HIP(hipGetLastError());
+    return GH_OK;
+}
+
+// --------------------------------------------------------------------------------------------------------------- C ABI
+extern "C" int gh_online_create(gh_ctx* ctx, const gh_lattices* lat, int64_t n_streams, int64_t max_frames, gh_online** out) {
+    return online_create(ctx, lat, n_streams, max_frames, false, out);
+}
+
+extern "C" int gh_online_create_window(gh_ctx* ctx, const gh_lattices* lat, int64_t n_streams, int64_t window_frames, gh_online** out) {
+    return online_create(ctx, lat, n_streams, window_frames, true, out);
 }
 
 extern "C" void gh_online_destroy(gh_online* on) {
@@ -284,13 +295,15 @@ extern "C" int gh_online_reset(gh_ctx* ctx, gh_online* on, int64_t n, const int6
     GH_REQUIRE(ctx && on, "gh_online_reset: NULL argument");
     if (!ids) {
         std::fill(on->frames.begin(), on->frames.end(), 0);
+        std::fill(on->settled.begin(), on->settled.end(), 0);
         return GH_OK;
     }
     for (int64_t k = 0; k < n; ++k)
         GH_REQUIRE(ids[k] >= 0 && ids[k] < on->n_streams, "gh_online_reset: stream %lld out of range [0, %lld)", (long long)ids[k],
                    (long long)on->n_streams);
-    // (a stream at column 0 starts from +inf and an empty word: nothing on the device has to be cleared)
-    for (int64_t k = 0; k < n; ++k) on->frames[(size_t)ids[k]] = 0;
+    // (a stream at column 0 starts from +inf and an empty word, and its anchor is read only once `settled` says it has one:
+    //  nothing on the device has to be cleared)
+    for (int64_t k = 0; k < n; ++k) on->frames[(size_t)ids[k]] = on->settled[(size_t)ids[k]] = 0;
     return GH_OK;
 }
 
@@ -328,6 +341,10 @@ extern "C" int gh_online_push(gh_ctx* ctx, gh_online* on, const gh_batch* b, con
                    (long long)(fr + cn), (long long)u, (long long)Tu);
         GH_REQUIRE(on->frames[(size_t)id] + cn <= on->max_frames, "gh_online_push: stream %lld would hold %lld frames, capacity %lld",
                    (long long)id, (long long)(on->frames[(size_t)id] + cn), (long long)on->max_frames);
+        GH_REQUIRE(!on->window || on->frames[(size_t)id] + cn - on->settled[(size_t)id] <= on->window,
+                   "gh_online_push: stream %lld would hold %lld unsettled frames, window %lld (gh_online_commit moves the window on; a "
+                   "stream whose traces have not met within it can only be finished)", (long long)id,
+                   (long long)(on->frames[(size_t)id] + cn - on->settled[(size_t)id]), (long long)on->window);
         if (cn == 0) continue;
         gh_online_slot s;
         s.row0 = b->offsets[u] + fr; s.stream = (int32_t)id; s.count = (int32_t)cn; s.t0 = (int32_t)on->frames[(size_t)id]; s.pad = 0;
@@ -349,7 +366,7 @@ extern "C" int gh_online_push(gh_ctx* ctx, gh_online* on, const gh_batch* b, con
     gh_online_args a;
     memset(&a, 0, sizeof a);
     a.lf = on->lat->d_layers; a.nll = b->nll; a.S = b->nll_S; a.slots = on->d_slots; a.n_slots = (int64_t)slots.size();
-    a.prev = on->d_prev; a.open = on->d_open; a.hist = on->d_hist; a.hist_stride = on->hist_stride;
+    a.prev = on->d_prev; a.open = on->d_open; a.hist = on->d_hist; a.hist_stride = on->hist_stride; a.ring_words = on->ring_words;
     const int rc = launch_online(ctx, a, f, b->dtype == GH_F64);
     if (rc) return rc;
     for (const gh_online_slot& s : slots) on->frames[(size_t)s.stream] += s.count;
@@ -363,6 +380,11 @@ extern "C" int gh_online_result(gh_ctx* ctx, gh_online* on, int64_t n, const int
     GH_REQUIRE(ctx == on->ctx, "gh_online_result: the session belongs to another context");
     GH_REQUIRE(!labels || (row_label && label_off && n_labels), "gh_online_result: labels need row_label, label_off and n_labels");
     GH_REQUIRE(!path || (path_off && path_len), "gh_online_result: path needs path_off and path_len");
+    if (on->window) {
+        gh_set_error("gh_online_result: a session with a window keeps the unsettled tail of the history only; gh_online_commit gives the "
+                     "settled words and gh_online_tail the rest (paths are not offered)");
+        return GH_ERR_UNSUPPORTED;
+    }
     if (!ids) n = on->n_streams;
     if (n <= 0) return GH_OK;
     const gh_lattices* lat = on->lat;
@@ -400,9 +422,8 @@ extern "C" int gh_online_result(gh_ctx* ctx, gh_online* on, int64_t n, const int
         GH_HIP(hipMemcpyAsync(d_labeloff, label_off, (size_t)(n + 1) * 8, hipMemcpyHostToDevice, st));
     }
     if (path) GH_HIP(hipMemcpyAsync(d_pathoff, path_off, (size_t)(n + 1) * 8, hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(online_end_kernel, dim3((unsigned)((n + 3) / 4)), dim3(64), 0, st, lat->d_layers, lat->d_lf_end_slot, n_end,
-                       on->d_prev, d_ids, d_uttoff, n, d_endcost, d_best);
-    GH_HIP(hipGetLastError());
+    rc = gh_launch_online_end(ctx, on, d_ids, d_uttoff, n, d_endcost, d_best);
+    if (rc) return rc;
     // the one-shot decode's own back-trace on the history: utterance i = stream ids[i], its decision words at bp_off[i]
     gh_layers_args c;
     memset(&c, 0, sizeof c);

@@ -169,6 +169,9 @@ SIGNATURES = {
     "gh_online_frames": (C.c_int, [C.c_void_p, _c_i64p]),
     "gh_online_result": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, _c_i64p, _c_f64p, _c_i32p, _c_i32p, _c_i32p, _c_i64p, _c_i32p,
                                    _c_i32p, _c_i64p, _c_i32p]),
+    "gh_online_create_window": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.POINTER(C.c_void_p)]),
+    "gh_online_commit": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, _c_i64p, _c_i64p, _c_i32p, _c_i32p, _c_i64p, _c_i32p]),
+    "gh_online_tail": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, _c_i64p, _c_f64p, _c_i32p, _c_i32p, _c_i32p, _c_i64p, _c_i32p]),
 }
 
 
@@ -1385,13 +1388,23 @@ class OnlineSession:
     decision word and decision history stay on the device; `push` advances streams by chunks of resident likelihoods,
     `result` is the decode of what a stream has taken so far -- bitwise the one-shot decode of those frames.
     `lat` (a `Lattices` with one graph in the narrow loop form) must outlive the session; any other graph form raises
-    `Unsupported`."""
+    `Unsupported`.
+    Exactly one of `max_frames` (history for whole streams) and `window` (gh_online_create_window: history for that many
+    UNSETTLED frames per stream) is given.  `commit` advances the settled prefix of streams and returns what it settled,
+    `tail` is the rest of the running hypothesis; with a window, `result` is `Unsupported` (no paths, use `tail`)."""
 
-    def __init__(self, ctx, lat, n_streams, max_frames):
+    def __init__(self, ctx, lat, n_streams, max_frames=None, window=None):
+        if (max_frames is None) == (window is None):
+            raise ValueError("exactly one of max_frames and window must be given")
         self.ctx, self.lat = ctx, lat
-        self.n_streams, self.max_frames = int(n_streams), int(max_frames)
+        self.n_streams = int(n_streams)
+        self.max_frames = None if max_frames is None else int(max_frames)
+        self.window = None if window is None else int(window)
         h = C.c_void_p()
-        rc = ctx.lib.gh_online_create(ctx.h, lat.h, self.n_streams, self.max_frames, C.byref(h))
+        if window is None:
+            rc = ctx.lib.gh_online_create(ctx.h, lat.h, self.n_streams, self.max_frames, C.byref(h))
+        else:
+            rc = ctx.lib.gh_online_create_window(ctx.h, lat.h, self.n_streams, self.window, C.byref(h))
         if rc == GH_ERR_UNSUPPORTED:
             raise Unsupported(ctx.lib.gh_last_error().decode("utf-8", "replace"))
         _check(ctx.lib, rc)
@@ -1446,14 +1459,63 @@ class OnlineSession:
             path_off = np.concatenate([[0], np.cumsum(np.where(T > 1, T * self._nlev, 0))]).astype(np.int64)
             path = np.empty((int(path_off[-1]), 2), dtype=np.int32)
             path_len = np.empty(n, dtype=np.int32)
-        _check(lib, lib.gh_online_result(self.ctx.h, self.h, n, _ptr(ids, _c_i64p), _ptr(end_cost, _c_f64p), _ptr(best_end, _c_i32p),
-                                         _ptr(rl, _c_i32p), _ptr(labels, _c_i32p), _ptr(label_off, _c_i64p), _ptr(n_labels, _c_i32p),
-                                         _ptr(path, _c_i32p), _ptr(path_off, _c_i64p), _ptr(path_len, _c_i32p)))
+        rc = lib.gh_online_result(self.ctx.h, self.h, n, _ptr(ids, _c_i64p), _ptr(end_cost, _c_f64p), _ptr(best_end, _c_i32p),
+                                  _ptr(rl, _c_i32p), _ptr(labels, _c_i32p), _ptr(label_off, _c_i64p), _ptr(n_labels, _c_i32p),
+                                  _ptr(path, _c_i32p), _ptr(path_off, _c_i64p), _ptr(path_len, _c_i32p))
+        if rc == GH_ERR_UNSUPPORTED:                                      # a session with a window: commit() and tail()
+            raise Unsupported(lib.gh_last_error().decode("utf-8", "replace"))
+        _check(lib, rc)
         out = dict(end_cost=end_cost, best_end=best_end, frames=T)
         if rl is not None:
             out["labels"] = [labels[label_off[i]:label_off[i] + n_labels[i]] for i in range(n)]
         if want_path:
             out["paths"] = [path[path_off[i]:path_off[i] + path_len[i]].astype(np.int64) for i in range(n)]
+        return out
+
+    def _label_room(self, ids, row_label, max_labels):
+        """(row_label, labels, label_off, n_labels) for a call that returns up to max_labels [n] labels per stream."""
+        rl = np.ascontiguousarray(np.asarray(row_label, dtype=np.int32).reshape(-1))
+        assert len(rl) == self.R, "row_label must give one label per graph row"
+        cap = np.broadcast_to(np.asarray(max_labels, dtype=np.int64), (len(ids),))
+        label_off = np.concatenate([[0], np.cumsum(cap)]).astype(np.int64)
+        return rl, np.empty(int(label_off[-1]), dtype=np.int32), label_off, np.empty(len(ids), dtype=np.int32)
+
+    def commit(self, ids=None, row_label=None, max_labels=None):
+        """Advances the anchor of the streams `ids` (None: all; distinct): dict(settled_frames [n]: anchor column + 1, 0 =
+        nothing settled yet[, labels: list of int32 arrays -- what THIS call settled]).  max_labels: scalar or [n] bound
+        per stream (default: one label per frame of the session's longest stream)."""
+        lib = self.ctx.lib
+        ids = np.arange(self.n_streams, dtype=np.int64) if ids is None else self._i64(ids)
+        n = len(ids)
+        settled = np.zeros(n, dtype=np.int64)
+        rl = labels = label_off = n_labels = None
+        if row_label is not None:
+            rl, labels, label_off, n_labels = self._label_room(ids, row_label, int(self.frames().max()) + 1 if max_labels is None else max_labels)
+        _check(lib, lib.gh_online_commit(self.ctx.h, self.h, n, _ptr(ids, _c_i64p), _ptr(settled, _c_i64p), _ptr(rl, _c_i32p),
+                                         _ptr(labels, _c_i32p), _ptr(label_off, _c_i64p), _ptr(n_labels, _c_i32p)))
+        out = dict(settled_frames=settled)
+        if rl is not None:
+            out["labels"] = [labels[label_off[i]:label_off[i] + n_labels[i]] for i in range(n)]
+        return out
+
+    def tail(self, ids=None, row_label=None, max_labels=None):
+        """dict(end_cost [n, n_end], best_end [n], frames [n][, labels: the labels behind the anchor, list of int32 arrays])
+        for the streams `ids` (None: all); a stream without an anchor gives its whole label sequence."""
+        lib = self.ctx.lib
+        ids = np.arange(self.n_streams, dtype=np.int64) if ids is None else self._i64(ids)
+        n = len(ids)
+        ok = (ids >= 0) & (ids < self.n_streams)
+        T = np.where(ok, self.frames()[np.where(ok, ids, 0)], 0) if n else np.zeros(0, dtype=np.int64)
+        end_cost = np.empty((n, self.n_end), dtype=np.float64)
+        best_end = np.empty(n, dtype=np.int32)
+        rl = labels = label_off = n_labels = None
+        if row_label is not None:
+            rl, labels, label_off, n_labels = self._label_room(ids, row_label, T + 1 if max_labels is None else max_labels)
+        _check(lib, lib.gh_online_tail(self.ctx.h, self.h, n, _ptr(ids, _c_i64p), _ptr(end_cost, _c_f64p), _ptr(best_end, _c_i32p),
+                                       _ptr(rl, _c_i32p), _ptr(labels, _c_i32p), _ptr(label_off, _c_i64p), _ptr(n_labels, _c_i32p)))
+        out = dict(end_cost=end_cost, best_end=best_end, frames=T)
+        if rl is not None:
+            out["labels"] = [labels[label_off[i]:label_off[i] + n_labels[i]] for i in range(n)]
         return out
 
     def close(self):

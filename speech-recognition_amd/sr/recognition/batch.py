@@ -381,10 +381,12 @@ class ContinuousDecoder:
         """Decode `xs` and tally against the label strings like main.py:54-84 -- see `sequence_report`."""
         return sequence_report(self.decode(xs), labels, verbose=verbose)
 
-    def online(self, n_streams, max_frames):
-        """An `OnlineDecoder` of `n_streams` live utterances of up to `max_frames` frames each, sharing this decoder's
-        packed mixtures and graph (grammar="loop" only: anything else raises `_hip.Unsupported`)."""
-        return OnlineDecoder(self, n_streams, max_frames)
+    def online(self, n_streams, max_frames=None, window=None):
+        """An `OnlineDecoder` of `n_streams` live utterances sharing this decoder's packed mixtures and graph
+        (grammar="loop" only: anything else raises `_hip.Unsupported`).  Exactly one of `max_frames` (utterances of up to
+        that many frames, whole history kept) and `window` (utterances of any length, history for that many unsettled
+        frames) must be given."""
+        return OnlineDecoder(self, n_streams, max_frames, window)
 
 
 class OnlineDecoder:
@@ -400,17 +402,39 @@ class OnlineDecoder:
         words, info = on.finish([7])                          # ... of stream 7, whose id is free again
 
     `max_frames` is a hard capacity per stream.  Bad arguments (an id twice in one push or out of range, a chunk of
-    another feature dimension, a push past `max_frames`) raise ValueError before the GPU is touched, and no stream moves."""
+    another feature dimension, a push past `max_frames`) raise ValueError before the GPU is touched, and no stream moves.
 
-    def __init__(self, decoder, n_streams, max_frames):
+    THE SETTLED PREFIX.  `commit` traces back from every cell of a stream's newest column that is still alive; where all
+    those traces meet, everything before is final whatever audio follows.  It returns the words that became final with
+    this call, `settled` all of them so far, and they are a prefix of every later `result`:
+
+        on = dec.online(n_streams=64, window=400)             # history for 400 UNSETTLED frames per stream
+        on.push(ids, chunks); new_words = on.commit(ids)      # per stream: words that can no longer change
+        words, info = on.result([3])                          # settled words + the words of the unsettled tail
+
+    With `window=` instead of `max_frames=` a stream may run for any length: the history is a ring that holds the frames
+    behind the settled prefix, and a push that would take a stream's unsettled frames (frames - settled_frames) past the
+    window raises ValueError like one past `max_frames`.  There is NO forced commit: a stream whose traces have not met
+    within the window cannot take more frames and can only be finished.  A windowed decoder offers no paths."""
+
+    def __init__(self, decoder, n_streams, max_frames=None, window=None):
         if decoder.grammar != "loop":
             raise _hip.Unsupported("online decoding takes the word-loop grammar (grammar='loop'), not %r" % (decoder.grammar,))
-        if int(n_streams) < 1 or int(max_frames) < 1:
-            raise ValueError("n_streams and max_frames must be positive")
+        if (max_frames is None) == (window is None):
+            raise ValueError("exactly one of max_frames and window must be given")
+        if int(n_streams) < 1 or int(window if max_frames is None else max_frames) < 1:
+            raise ValueError("n_streams and max_frames / window must be positive")
         self.decoder = decoder
-        self.n_streams, self.max_frames = int(n_streams), int(max_frames)
-        self.session = _hip.OnlineSession(decoder.ctx, decoder.lat, self.n_streams, self.max_frames)
+        self.n_streams = int(n_streams)
+        self.max_frames = None if max_frames is None else int(max_frames)
+        self.window = None if window is None else int(window)
+        if window is None:
+            self.session = _hip.OnlineSession(decoder.ctx, decoder.lat, self.n_streams, self.max_frames)
+        else:
+            self.session = _hip.OnlineSession(decoder.ctx, decoder.lat, self.n_streams, window=self.window)
         self._frames = np.zeros(self.n_streams, dtype=np.int64)       # what the session holds, for the checks below
+        self._settled = np.zeros(self.n_streams, dtype=np.int64)      # settled frames (anchor column + 1) of every stream
+        self._words = [[] for _ in range(self.n_streams)]             # ... and its settled words
         self._row_word = np.where(decoder.row_state >= 0, decoder.row_state // decoder.n, -1).astype(np.int32)
 
     @property
@@ -430,6 +454,12 @@ class OnlineDecoder:
         return a
 
     def _room(self, ids, counts):
+        if self.window is not None:
+            tail = self._frames[ids] + counts - self._settled[ids]
+            if np.any(tail > self.window):
+                k = int(np.flatnonzero(tail > self.window)[0])
+                raise ValueError("stream %d would hold %d unsettled frames, window %d" % (ids[k], tail[k], self.window))
+            return
         over = self._frames[ids] + counts > self.max_frames
         if np.any(over):
             k = int(np.flatnonzero(over)[0])
@@ -488,20 +518,48 @@ class OnlineDecoder:
         all) for the frames pushed so far: what `decode_batch` returns for those frames as whole utterances."""
         ids = np.arange(self.n_streams, dtype=np.int64) if ids is None else self._ids(ids, distinct=False)
         dec = self.decoder
+        if self.window is not None:
+            if want_path:
+                raise ValueError("a decoder with a window offers no paths")
+            r = self.session.tail(ids, row_label=self._row_word, max_labels=self._frames[ids] - self._settled[ids] + 2)
+            return [self._words[k] + [int(w) for w in l] for k, l in zip(ids, r.pop("labels"))], r
         if want_path:
             r = self.session.result(ids, want_path=True)
             return [path_to_words(p, dec.row_state, dec.n) for p in r["paths"]], r
         r = self.session.result(ids, row_label=self._row_word, max_labels=dec._max_labels(self._frames[ids]))
         return [[int(w) for w in l] for l in r.pop("labels")], r
 
+    def commit(self, ids=None):
+        """Settles what can no longer change of the streams `ids` (None: all; distinct): the list of the words that became
+        final with THIS call, per stream.  Nothing is settled while a stream has fewer than two frames or no live cell, or
+        while its traces do not meet."""
+        ids = np.arange(self.n_streams, dtype=np.int64) if ids is None else self._ids(ids)
+        # (room for a word per unsettled frame: with skip arcs a word can pass in fewer than n - 1 column steps)
+        r = self.session.commit(ids, row_label=self._row_word, max_labels=self._frames[ids] - self._settled[ids] + 2)
+        new = [[int(w) for w in l] for l in r["labels"]]
+        for k, s, ws in zip(ids, r["settled_frames"], new):
+            self._settled[k] = s
+            self._words[k] = self._words[k] + ws
+        return new
+
+    def settled(self, ids=None):
+        """(all settled words so far, settled_frames [n]) of the streams `ids` (None: all): stream k's first
+        settled_frames[k] frames can no longer change its words."""
+        ids = np.arange(self.n_streams, dtype=np.int64) if ids is None else self._ids(ids, distinct=False)
+        return [list(self._words[k]) for k in ids], self._settled[ids].copy()
+
     def reset(self, ids=None):
-        """The streams `ids` (None: all) start again at frame 0."""
+        """The streams `ids` (None: all) start again at frame 0, with nothing settled."""
         ids = None if ids is None else self._ids(ids, distinct=False)
         self.session.reset(ids)
         if ids is None:
             self._frames[:] = 0
+            self._settled[:] = 0
         else:
             self._frames[ids] = 0
+            self._settled[ids] = 0
+        for k in (range(self.n_streams) if ids is None else ids):
+            self._words[int(k)] = []
 
     def finish(self, ids, want_path=False):
         """`result(ids)` followed by `reset(ids)`: the final decode of utterances that have ended; their ids are free."""
