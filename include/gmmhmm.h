@@ -721,6 +721,43 @@ int gh_online_commit(gh_ctx* ctx, gh_online* on, int64_t n, const int64_t* ids /
 int gh_online_tail(gh_ctx* ctx, gh_online* on, int64_t n, const int64_t* ids /*[n] or NULL*/, double* end_cost, int32_t* best_end,
                    const int32_t* row_label, int32_t* labels, const int64_t* label_off /*[n+1]*/, int32_t* n_labels);
 
+/* ------------------------------------------------ streaming front-end: audio chunks in, final feature frames out
+ * gh_batch_create_from_pcm(mode 1) for n_streams live utterances whose int16 audio arrives in pieces of any size: a push
+ * returns exactly the frames [cepstra | delta | delta-delta] (39 columns) that have become final.
+ * CONTRACT: the concatenated output of a stream is bitwise the mode-1 batch of that utterance ALONE, however the audio was
+ * cut.  With flen / step = the frame length / stride in samples and n = the stream's samples so far: cepstral frame t is
+ * complete when t step + flen <= n; frames are paired (2m, 2m + 1) by absolute index (the MFCC kernel sends a pair through
+ * one FFT) and a pair is computed when both frames are complete; feature frame t is final when cepstra t + 2 exist.  So
+ * an open stream has C = (n < flen ? 0 : (n - flen) / step + 1) complete frames, P = C & ~1 computed ones and
+ * max(0, P - 2) final ones; a stream that has ended has all ceil(n / step) frames, zero-extended like `segment`, with
+ * delta_feature's one-sided rules at the last frame.  Carried on the device per stream: fewer than flen + 2 step + 1
+ * samples (two buffers written in turn) and the last 4 cepstral rows.
+ * NORMALISATION: per-utterance standardize is not causal; a front-end created with mean / std [39] applies the fixed map
+ * "round the raw value to the batch dtype, evaluate (x - mean) / std in fp64, round to the dtype" (NULL, NULL: raw
+ * features).  gh_batch_affine is that map in place on any resident batch (mean / std [D]; likelihoods the batch holds
+ * are forgotten), e.g. on a mode-1 batch of whole utterances for training.
+ * gh_stream_push: stream ids[u] takes samples [sample_off[u], sample_off[u+1]) of `samples` (any length from 0 to
+ * max_chunk_samples); end[u] != 0 (end may be NULL) ends its utterance with this chunk.  *out is a resident batch of n
+ * utterances in the order of ids with ragged frame counts, 0 allowed.  Everything is checked before anything is enqueued
+ * and a refused push (GH_ERR_INVALID) moves no stream: an id twice or out of range, a chunk over max_chunk_samples, a
+ * stream that has ended and was not reset, an end with no samples or fewer than 2 frames.  Synchronises.
+ * gh_stream_reset: streams ids[0..n) (NULL: all) start a new utterance at sample 0; nothing happens on the device.
+ * gh_stream_samples: samples every stream has taken since its last reset.
+ * gh_stream_profile(on): HIP events around the phases of every push from now on; gh_stream_phase_ms: the last push's
+ * upload, MFCC kernel, stack kernel and carry kernel in ms (measurement plumbing, as gh_em_profile). */
+typedef struct gh_stream gh_stream;
+int gh_stream_create(gh_ctx* ctx, int64_t n_streams, int sample_rate, double frame_size, double frame_stride, double low_freq,
+                     double high_freq, int64_t max_chunk_samples, gh_dtype dtype, const double* mean /*[39] or NULL*/,
+                     const double* std_ /*[39] or NULL*/, gh_stream** out);
+void gh_stream_destroy(gh_stream* fe);
+int gh_stream_reset(gh_stream* fe, int64_t n, const int64_t* ids /*[n] or NULL*/);
+int gh_stream_samples(const gh_stream* fe, int64_t* out /*[n_streams]*/);
+int gh_stream_profile(gh_stream* fe, int on);
+int gh_stream_phase_ms(const gh_stream* fe, double* out /*[4]*/);
+int gh_stream_push(gh_ctx* ctx, gh_stream* fe, int64_t n, const int64_t* ids /*[n], distinct*/, const int16_t* samples,
+                   const int64_t* sample_off /*[n+1]*/, const uint8_t* end /*[n] or NULL*/, gh_batch** out);
+int gh_batch_affine(gh_ctx* ctx, gh_batch* b, const double* mean /*[D]*/, const double* std_ /*[D]*/);
+
 #ifdef __cplusplus
 }
 #endif

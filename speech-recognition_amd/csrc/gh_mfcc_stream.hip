@@ -1,0 +1,642 @@
+// Streaming MFCC / delta front-end: int16 PCM arrives per stream in chunks of any size, and every push returns exactly
+// the feature frames [ceps | delta | delta-delta] that have become final, as a resident batch.  CONTRACT: a stream's
+// concatenated output is bitwise gh_batch_create_from_pcm(mode 1) of that utterance ALONE, however the audio was cut.
+//   * cepstral frame t is complete when t * step + flen <= n (n = samples so far); mfcc_kernel sends two frames through one
+//     complex FFT, so a frame's bits depend on its partner: frames are paired (2m, 2m + 1) by ABSOLUTE index and a pair is
+//     computed when both frames are complete; a trailing odd frame at the end pairs with a dead slot (live[1] == false);
+//   * feature frame t is final when cepstra t + 2 exist (delta needs t + 1, delta-delta t + 2); at the end of the
+//     utterance all ceil(n / step) frames come out, zero-extended like `segment`, with delta_feature's one-sided rules;
+//   * carried per stream on the device: the samples from one before the first uncomputed pair (pre-emphasis) to the
+//     newest, fewer than flen + 2 step + 1 of them, in two buffers written in turn; the last 4 cepstral rows (416 B).
+//     A stream at sample 0 reads no carry: a reset touches nothing on the device.
+// Normalisation is a FIXED affine map (per-utterance `standardize` is not causal): the raw value is rounded to the batch
+// dtype, (x - mean) / std is evaluated in fp64 on that and rounded to the dtype; gh_batch_affine is the same map on any
+// resident batch.
+// The kernel body from the FFT to the DCT, the tables and build_tables are COPIES of gh_mfcc.hip's (a unit of their own:
+// the machine code of the one-shot kernels stays what it was); same source, same flags, same rounding.
+#include "gh_internal.h"
+#include "gh_host.h"
+#include <climits>
+
+namespace {
+
+constexpr int NFFT = 512, NBIN = NFFT / 2 + 1, NFILT = 40, NCEPS = 13;
+constexpr int MFCC_S1 = 72, MFCC_S2 = 9;     // padded strides of the two transposes (elements)
+
+struct MfccTables {           // device pointers into one scratch block
+    const double* window;     // [NFFT]   hamming(pad_w) in [0, pad_w), 0 behind
+    const double* tw;         // [NFFT][2] cos / -sin of 2 pi k / NFFT
+    const double* wup;        // [NBIN] weight of bin k in the ASCENDING half of the filter that peaks right of it
+    const double* wdn;        // [NBIN] weight of bin k in the DESCENDING half of the filter that peaks at / left of it
+    const int* seg;           // [NFILT + 2] the mel bin points: segment s = bins [seg[s], seg[s+1])
+    const double* dct;        // [NCEPS][NFILT]
+};
+
+typedef double c2 __attribute__((ext_vector_type(2)));   // (re, im)
+
+__device__ __forceinline__ c2 mul_negi(c2 v) { return (c2){v.y, -v.x}; }                       // v * (-i)
+__device__ __forceinline__ c2 cmul(c2 a, c2 w) { return (c2){a.x * w.x - a.y * w.y, a.x * w.y + a.y * w.x}; }
+
+// in-place 8-point forward DFT (decimation in frequency), natural output order
+__device__ __forceinline__ void dft8(c2 (&v)[8]) {
+    constexpr double R = 0.70710678118654752440;
+    c2 t[4], u[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) { t[j] = v[j] + v[j + 4]; u[j] = v[j] - v[j + 4]; }
+    u[1] = (c2){(u[1].x + u[1].y) * R, (u[1].y - u[1].x) * R};      // * W8^1
+    u[2] = mul_negi(u[2]);                                          // * W8^2
+    u[3] = (c2){(u[3].y - u[3].x) * R, -(u[3].x + u[3].y) * R};     // * W8^3
+    auto dft4 = [](const c2 (&x)[4], c2& o0, c2& o1, c2& o2, c2& o3) {
+        const c2 s0 = x[0] + x[2], s1 = x[0] - x[2], s2 = x[1] + x[3], s3 = mul_negi(x[1] - x[3]);
+        o0 = s0 + s2; o2 = s0 - s2; o1 = s1 + s3; o3 = s1 - s3;
+    };
+    dft4(t, v[0], v[2], v[4], v[6]);
+    dft4(u, v[1], v[3], v[5], v[7]);
+}
+
+// One wave, one PAIR of frames (A, B): z = a + i b (lane l holds z[l + 64 j] in v[j], windowed and zero padded) goes
+// through ONE 512-point complex FFT and the two real spectra are separated afterwards.  512 = 8 x 8 x 8: three radix-8
+// passes in registers (each lane holds 8 points), two transposes through LDS (padded, 16-byte accesses) -- instead of
+// 9 radix-2 stages with a barrier and 8 LDS accesses per butterfly each.  ex: the wave's 8 * MFCC_S1 doubles of LDS,
+// lfb: its [2][NFILT] log filterbank row, s_wup / s_wdn: the block's copy of the per-bin weights.
+// store_ceps(acc0, acc1): lane c < NCEPS holds cepstrum c of A and B.
+template <typename StoreCeps>
+__device__ __forceinline__ void mfcc_pair_tail(const MfccTables& t, c2 (&v)[8], double* ex, double (&lfb)[2][NFILT],
+                                               const double* s_wup, const double* s_wdn, int lane, StoreCeps store_ceps) {
+    constexpr int S1 = MFCC_S1, S2 = MFCC_S2;
+    // ---- pass 1: DFT over j, twiddle W512^(l q); transpose so that lane (l1 + 8 q) holds l2 = 0..7 ----
+    dft8(v);
+#pragma unroll
+    for (int q = 1; q < 8; ++q) v[q] = cmul(v[q], *reinterpret_cast<const c2*>(t.tw + 2 * (lane * q)));
+    // component-wise transpose through LDS: v[i] goes to slot wr(i), comes back from slot rd(i)
+    auto transpose = [&](auto wr, auto rd) {
+        double tx[8];
+#pragma unroll
+        for (int i = 0; i < 8; ++i) ex[wr(i)] = v[i].x;
+        __syncthreads();
+#pragma unroll
+        for (int i = 0; i < 8; ++i) tx[i] = ex[rd(i)];
+        __syncthreads();
+#pragma unroll
+        for (int i = 0; i < 8; ++i) ex[wr(i)] = v[i].y;
+        __syncthreads();
+#pragma unroll
+        for (int i = 0; i < 8; ++i) v[i] = (c2){tx[i], ex[rd(i)]};
+        __syncthreads();
+    };
+    const int l1 = lane & 7, qq = lane >> 3;
+    transpose([&](int q) { return q * S1 + lane; }, [&](int l2) { return qq * S1 + l1 + 8 * l2; });
+    // ---- pass 2: DFT over l2, twiddle W64^(l1 q'); transpose so that lane (q + 8 q') holds l1 = 0..7 ----
+    dft8(v);
+#pragma unroll
+    for (int q2 = 1; q2 < 8; ++q2) v[q2] = cmul(v[q2], *reinterpret_cast<const c2*>(t.tw + 2 * (8 * l1 * q2)));
+    transpose([&](int q2) { return (qq + 8 * q2) * S2 + l1; }, [&](int i) { return lane * S2 + i; });
+    // ---- pass 3: DFT over l1: register p holds Z[lane + 64 p] ----
+    dft8(v);
+    // ---- separate the two real spectra, power / NFFT for bins 0..256: the partner Z[N - k] comes through LDS ----
+    double wx[5], wy[5];
+#pragma unroll
+    for (int p = 0; p < 8; ++p) ex[lane + 64 * p] = v[p].x;
+    __syncthreads();
+#pragma unroll
+    for (int i = 0; i < 5; ++i) wx[i] = ex[(NFFT - (lane + 64 * i)) & (NFFT - 1)];
+    __syncthreads();
+#pragma unroll
+    for (int p = 0; p < 8; ++p) ex[lane + 64 * p] = v[p].y;
+    __syncthreads();
+#pragma unroll
+    for (int i = 0; i < 5; ++i) wy[i] = ex[(NFFT - (lane + 64 * i)) & (NFFT - 1)];
+    __syncthreads();
+    double* pw = ex;                                         // [2][NBIN + pad]
+#pragma unroll
+    for (int i = 0; i < 5; ++i) {
+        const int k = lane + 64 * i;
+        const c2 z = (i < 4) ? v[i] : v[4];                  // k = 256 sits in lane 0, register 4
+        const double ar = z.x + wx[i], ai = z.y - wy[i], br = z.x - wx[i], bi = z.y + wy[i];
+        if (k < NBIN) {
+            pw[k] = (ar * ar + ai * ai) * (0.25 / NFFT);
+            pw[264 + k] = (br * br + bi * bi) * (0.25 / NFFT);
+        }
+    }
+    __syncthreads();
+    // ---- mel filterbank: lane s sums segment s = [seg[s], seg[s+1]) once with the ascending weights (filter
+    // s + 1) and once with the descending ones (filter s); filter m = up(segment m - 1) + down(segment m) ----
+    {
+        double up0 = 0.0, up1 = 0.0, dn0 = 0.0, dn1 = 0.0;
+        if (lane <= NFILT) {
+            const int kb = t.seg[lane], ke = t.seg[lane + 1];
+            for (int k = kb; k < ke; ++k) {
+                const double gu = s_wup[k], gd = s_wdn[k], x0 = pw[k], x1 = pw[264 + k];
+                up0 = fma(x0, gu, up0); dn0 = fma(x0, gd, dn0);
+                up1 = fma(x1, gu, up1); dn1 = fma(x1, gd, dn1);
+            }
+        }
+        const double pu0 = __shfl_up(up0, 1), pu1 = __shfl_up(up1, 1);   // ascending half lives one segment to the left
+        if (lane >= 1 && lane <= NFILT) {
+            double acc0 = pu0 + dn0, acc1 = pu1 + dn1;
+            if (acc0 == 0.0) acc0 = 2.220446049250313e-16;  // np.finfo(float).eps
+            if (acc1 == 0.0) acc1 = 2.220446049250313e-16;
+            const double f0 = log10(acc0), f1 = log10(acc1);
+            lfb[0][lane - 1] = f0;
+            lfb[1][lane - 1] = f1;
+        }
+    }
+    __syncthreads();
+    // ---- DCT-II (ortho), coefficients 1..13: lane = coefficient + 16 * quarter of the 40 filters ----
+    {
+        const int c = lane & 15, part = lane >> 4;
+        double acc0 = 0.0, acc1 = 0.0;
+        if (c < NCEPS) {
+            const double* row = t.dct + c * NFILT + part * (NFILT / 4);
+            const double* l0 = lfb[0] + part * (NFILT / 4);
+            const double* l1f = lfb[1] + part * (NFILT / 4);
+#pragma unroll
+            for (int m = 0; m < NFILT / 4; ++m) { acc0 = fma(row[m], l0[m], acc0); acc1 = fma(row[m], l1f[m], acc1); }
+        }
+        acc0 += __shfl_xor(acc0, 16); acc0 += __shfl_xor(acc0, 32);
+        acc1 += __shfl_xor(acc1, 16); acc1 += __shfl_xor(acc1, 32);
+        store_ceps(acc0, acc1);
+    }
+}
+
+struct HostTables {
+    std::vector<double> window, tw, wup, wdn, dct;
+    std::vector<int> seg;
+    int flen, fstep, pad_left;
+};
+
+// tables built the way the reference builds them (feature.py:25-40,52,58-75,80)
+int build_tables(int sample_rate, double frame_size, double frame_stride, double low_freq, double high_freq,
+                 HostTables& h) {
+    h.flen = (int)(frame_size * sample_rate);
+    h.fstep = (int)(frame_stride * sample_rate);
+    GH_REQUIRE(sample_rate > 0 && h.flen >= 1 && h.fstep >= 1, "gh_stream: sample_rate=%d frame=%d step=%d samples",
+               sample_rate, h.flen, h.fstep);
+    int pad_w = 1;
+    while (pad_w < h.flen) pad_w <<= 1;  // 1 << (width - 1).bit_length()
+    if (pad_w > NFFT) {
+        gh_set_error("gh_stream: frames of %d samples exceed the reference's NFFT = %d", h.flen, NFFT);
+        return GH_ERR_UNSUPPORTED;
+    }
+    h.pad_left = (pad_w - h.flen) / 2;
+    h.window.assign(NFFT, 0.0);
+    for (int k = 0; k < pad_w; ++k)
+        h.window[k] = pad_w == 1 ? 1.0 : 0.54 - 0.46 * std::cos(2.0 * M_PI * k / (pad_w - 1));
+    h.tw.resize(2 * NFFT);
+    for (int k = 0; k < NFFT; ++k) {
+        const long double ang = -2.0L * 3.14159265358979323846264338327950288L * k / NFFT;
+        h.tw[2 * k] = (double)cosl(ang);
+        h.tw[2 * k + 1] = (double)sinl(ang);
+    }
+    if (!(high_freq > 0)) high_freq = sample_rate / 2.0;
+    const double low_mel = 2595 * std::log10(1 + low_freq / 700), high_mel = 2595 * std::log10(1 + high_freq / 700);
+    std::vector<double> bin(NFILT + 2);
+    const double step = (high_mel - low_mel) / (NFILT + 1);   // np.linspace(start, stop, NFILT + 2)
+    for (int i = 0; i < NFILT + 2; ++i) {
+        const double mel = (i == NFILT + 1) ? high_mel : low_mel + step * i;
+        const double hz = 700 * (std::pow(10.0, mel / 2595) - 1);
+        bin[i] = std::floor((NFFT + 1) * hz / sample_rate);
+    }
+    // the triangles (feature.py:66-75) as per-bin weights: bin k in [bin[m-1], bin[m]) rises towards filter m,
+    // bin k in [bin[m], bin[m+1]) falls away from filter m
+    h.wup.assign(NBIN, 0.0);
+    h.wdn.assign(NBIN, 0.0);
+    h.seg.assign(NFILT + 2, 0);
+    for (int i = 0; i < NFILT + 2; ++i) {
+        GH_REQUIRE(bin[i] >= 0 && bin[i] <= NBIN && (i == 0 || bin[i] >= bin[i - 1]),
+                   "gh_stream: mel point %d falls on bin %g outside the spectrum", i, bin[i]);
+        h.seg[i] = (int)bin[i];
+    }
+    for (int m = 1; m <= NFILT; ++m) {
+        const int lo = (int)bin[m - 1], ce = (int)bin[m], hi = (int)bin[m + 1];
+        for (int k = lo; k < ce; ++k) h.wup[k] = (k - bin[m - 1]) / (bin[m] - bin[m - 1]);
+        for (int k = ce; k < hi; ++k) h.wdn[k] = (bin[m + 1] - k) / (bin[m + 1] - bin[m]);
+    }
+    h.dct.resize((size_t)NCEPS * NFILT);
+    for (int c = 1; c <= NCEPS; ++c)
+        for (int m = 0; m < NFILT; ++m)
+            h.dct[(size_t)(c - 1) * NFILT + m] = std::sqrt(2.0 / NFILT) * std::cos(M_PI * c * (2 * m + 1) / (2.0 * NFILT));
+    return GH_OK;
+}
+
+
+// one stream of one push (host-built, uploaded with the chunk)
+struct StreamSlot {
+    int64_t chunk_off;            // first sample of its chunk in the uploaded samples
+    int64_t n_before, n_after;    // samples it held before the push / holds now
+    int64_t cbase, cnew;          // absolute index of sample 0 of the carry it reads / of the carry this push leaves behind
+    int64_t c_first, c_end;       // cepstral frames [c_first, c_end) are computed by this push (c_first is even)
+    int64_t f_first, f_end;       // feature frames [f_first, f_end) become final
+    int64_t T;                    // frames of the whole utterance when it ends here, INT64_MAX while it is open
+    int64_t out_off, ceps_off;    // first row in the output batch / in the scratch cepstra
+    int64_t pair_off;             // first frame pair in the launch
+    int32_t id, rd;               // stream; carry buffer to read (the other one is written)
+};
+
+struct StreamMfccArgs {
+    const int16_t* chunk;         // the chunks of this push, back to back
+    const int16_t* carry;         // [2][n_streams][cap]
+    const StreamSlot* slot;
+    const int32_t* pair_slot;     // slot of every frame pair (host-built table)
+    int64_t n_pairs, n_streams;
+    int cap, flen, fstep, pad_left;
+    MfccTables t;
+    double* ceps;                 // [new cepstral rows][NCEPS]
+};
+
+// One wave per frame pair, four pairs per workgroup: mfcc_kernel with samples addressed by ABSOLUTE index in the stream
+// -- below n_before they sit in the carry, from there on in the chunk -- and the carried previous sample in front of a
+// frame's first one (only absolute sample 0 is taken as it is).  A frame that is computed before the end is complete, so
+// the zero extension (s0 + js < n_after) only ever acts at the end.
+__global__ __launch_bounds__(256) void stream_mfcc_kernel(StreamMfccArgs a) {
+    constexpr int S1 = MFCC_S1;
+    __shared__ double s_x[4][8 * S1];
+    __shared__ double s_lfb[4][2][NFILT];
+    __shared__ double s_wup[NBIN], s_wdn[NBIN];          // per-bin filter weights, shared by the block
+    for (int k = threadIdx.x; k < NBIN; k += 256) { s_wup[k] = a.t.wup[k]; s_wdn[k] = a.t.wdn[k]; }
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    double* ex = s_x[wv];
+    const int64_t pr = (int64_t)blockIdx.x * 4 + wv;
+    const bool have = pr < a.n_pairs;                    // a wave past the last pair walks the last pair's addresses, stores nothing
+    const int64_t prc = have ? pr : a.n_pairs - 1;
+    const StreamSlot s = a.slot[a.pair_slot[prc]];
+    const int64_t fA = s.c_first + 2 * (prc - s.pair_off);   // frames fA (A) and fA + 1 (B) of the stream
+    const int16_t* carry = a.carry + ((int64_t)s.rd * a.n_streams + s.id) * a.cap;
+    const int16_t* chunk = a.chunk + s.chunk_off;
+    int64_t s0[2];
+    bool live[2];
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+        live[h] = have && fA + h < s.c_end;
+        s0[h] = (fA + h) * a.fstep;
+    }
+    auto sample_at = [&](int64_t i) {                    // cbase <= i < n_after
+        const int16_t* p = i < s.n_before ? carry + (i - s.cbase) : chunk + (i - s.n_before);
+        return (double)*p;
+    };
+    // ---- windowed, zero padded frames: lane l holds z[l + 64 j], j = 0..7 (loads unconditional on clamped addresses) ----
+    c2 v[8];
+    double cur[2][8], prv[2][8];
+    const int64_t last = s.n_after - 1;                  // (a slot with a pair has n_after > c_first * step > cbase)
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            int64_t p = s0[h] + (lane + 64 * j - a.pad_left);
+            p = p < s.cbase ? s.cbase : (p > last ? last : p);
+            cur[h][j] = sample_at(p);
+            prv[h][j] = sample_at(p > s.cbase ? p - 1 : p);
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        const int js = lane + 64 * j - a.pad_left;
+        const double w = a.t.window[lane + 64 * j];
+        double xs[2];
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            const bool in = live[h] && js >= 0 && js < a.flen && s0[h] + js < s.n_after;
+            const double x = (s0[h] + js == 0) ? cur[h][j] : __dsub_rn(cur[h][j], __dmul_rn(0.97, prv[h][j]));
+            xs[h] = in ? x * w : 0.0;
+        }
+        v[j] = (c2){xs[0], xs[1]};
+    }
+    double* o = a.ceps + (s.ceps_off + (fA - s.c_first)) * NCEPS;
+    mfcc_pair_tail(a.t, v, ex, s_lfb[wv], s_wup, s_wdn, lane, [&](double acc0, double acc1) {
+        if (lane < NCEPS) {
+            if (live[0]) o[lane] = acc0;
+            if (live[1]) o[NCEPS + lane] = acc1;
+        }
+    });
+}
+
+// the affine map of the header comment
+template <typename OT> __device__ __forceinline__ OT affine(double raw, const double* mean, const double* sd, int k) {
+    const OT r = (OT)raw;
+    return mean ? (OT)(((double)r - mean[k]) / sd[k]) : r;
+}
+
+// One workgroup per stream of the push: stack_kernel's formulas and edge rules (t == 0; t == T - 1 only at the end) on
+// cepstral rows t - 2 .. t + 2, of which those below c_first are carried (row r at r & 3) and the rest are new; then the
+// affine map, straight into the output batch.
+template <typename OT>
+__global__ __launch_bounds__(256) void stream_stack_kernel(const StreamSlot* __restrict__ slot, const double* __restrict__ ceps,
+                                                           const double* __restrict__ cc /*[n_streams][4][NCEPS]*/,
+                                                           const double* __restrict__ mean, const double* __restrict__ sd,
+                                                           OT* __restrict__ out) {
+    const StreamSlot s = slot[blockIdx.x];
+    const int nf = (int)(s.f_end - s.f_first);
+    const double* old = cc + (int64_t)s.id * 4 * NCEPS;
+    const double* fresh = ceps + s.ceps_off * NCEPS;
+    auto f = [&](int64_t r, int c) { return r >= s.c_first ? fresh[(r - s.c_first) * NCEPS + c] : old[(r & 3) * NCEPS + c]; };
+    auto delta_at = [&](int64_t t, int c) {
+        if (t == 0) return f(1, c) - f(0, c);
+        if (t == s.T - 1) return f(t, c) - f(t - 1, c);
+        return f(t + 1, c) - f(t - 1, c);
+    };
+    for (int i = threadIdx.x; i < nf * NCEPS; i += blockDim.x) {
+        const int64_t t = s.f_first + i / NCEPS;
+        const int c = i % NCEPS;
+        const double d = delta_at(t, c);
+        double dd;  // delta of the delta track, same edge rules
+        if (t == 0) dd = delta_at(1, c) - d;
+        else if (t == s.T - 1) dd = d - delta_at(t - 1, c);
+        else dd = delta_at(t + 1, c) - delta_at(t - 1, c);
+        OT* o = out + (s.out_off + i / NCEPS) * (3 * NCEPS);
+        o[c] = affine<OT>(f(t, c), mean, sd, c);
+        o[NCEPS + c] = affine<OT>(d, mean, sd, NCEPS + c);
+        o[2 * NCEPS + c] = affine<OT>(dd, mean, sd, 2 * NCEPS + c);
+    }
+}
+
+// One wave per stream of the push, after the two kernels above: the samples from cnew on go to the stream's other carry
+// buffer (never the one being read), the newest of the last 4 cepstral rows to their places r & 3.
+__global__ __launch_bounds__(64) void stream_carry_kernel(const StreamSlot* __restrict__ slot, const int16_t* __restrict__ chunk,
+                                                          int16_t* carry, int64_t n_streams, int cap,
+                                                          const double* __restrict__ ceps, double* __restrict__ cc) {
+    const StreamSlot s = slot[blockIdx.x];
+    const int16_t* rd = carry + ((int64_t)s.rd * n_streams + s.id) * cap;
+    int16_t* wr = carry + ((int64_t)(s.rd ^ 1) * n_streams + s.id) * cap;
+    const int len = (int)(s.n_after - s.cnew);           // <= cap (checked on the host); 0 for a stream that ended
+    for (int k = threadIdx.x; k < len; k += 64) {
+        const int64_t i = s.cnew + k;
+        wr[k] = i < s.n_before ? rd[i - s.cbase] : chunk[s.chunk_off + (i - s.n_before)];
+    }
+    const int64_t r0 = s.c_end - 4 > s.c_first ? s.c_end - 4 : s.c_first;
+    double* keep = cc + (int64_t)s.id * 4 * NCEPS;
+    for (int k = threadIdx.x; k < (int)(s.c_end - r0) * NCEPS; k += 64) {
+        const int64_t r = r0 + k / NCEPS;
+        keep[(r & 3) * NCEPS + k % NCEPS] = ceps[(s.ceps_off + (r - s.c_first)) * NCEPS + k % NCEPS];
+    }
+}
+
+template <typename OT>
+__global__ __launch_bounds__(256) void affine_kernel(OT* __restrict__ x, int64_t n, int D, const double* __restrict__ mean,
+                                                     const double* __restrict__ sd) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) x[i] = affine<OT>((double)x[i], mean, sd, (int)(i % D));
+}
+
+int check_affine(const char* who, const double* mean, const double* sd, int D) {
+    for (int k = 0; k < D; ++k)
+        GH_REQUIRE(std::isfinite(mean[k]) && std::isfinite(sd[k]) && sd[k] != 0.0, "%s: mean[%d]=%g std[%d]=%g", who, k, mean[k], k, sd[k]);
+    return GH_OK;
+}
+
+}  // namespace
+
+struct gh_stream {
+    gh_ctx* ctx;
+    gh_dtype dtype;
+    int64_t n_streams, max_chunk;
+    int flen, fstep, pad_left, cap;
+    bool normalise;
+    void* d_arena;                 // the one device allocation the pointers below point into
+    MfccTables t;
+    double *d_mean, *d_sd;         // [3 NCEPS] (unused without a map)
+    int16_t* d_carry;              // [2][n_streams][cap]
+    double* d_cc;                  // [n_streams][4][NCEPS]
+    std::vector<int64_t> samples;  // per stream: samples taken since its last reset
+    std::vector<uint8_t> ended, rd;    // ... whether it has ended; which carry buffer holds its samples
+    hipEvent_t ev[5] = {};         // gh_stream_profile: around upload, MFCC, stack, carry of a push
+    bool profile = false;
+    double phase_ms[4] = {0, 0, 0, 0};
+    // first cepstral frame that is not computed after n samples of an open stream, and where its carry begins
+    int64_t pairs_done(int64_t n) const { return n < flen ? 0 : (((n - flen) / fstep + 1) & ~int64_t(1)); }
+    int64_t carry_base(int64_t n) const { return std::min(std::max<int64_t>(pairs_done(n) * fstep - 1, 0), n); }
+};
+
+extern "C" int gh_stream_create(gh_ctx* ctx, int64_t n_streams, int sample_rate, double frame_size, double frame_stride,
+                                double low_freq, double high_freq, int64_t max_chunk_samples, gh_dtype dtype,
+                                const double* mean, const double* std_, gh_stream** out) {
+    GH_REQUIRE(ctx && out, "gh_stream_create: NULL argument");
+    GH_REQUIRE(dtype == GH_F32 || dtype == GH_F64, "gh_stream_create: bad dtype %d", (int)dtype);
+    GH_REQUIRE(n_streams >= 1 && max_chunk_samples >= 1, "gh_stream_create: n_streams=%lld max_chunk_samples=%lld",
+               (long long)n_streams, (long long)max_chunk_samples);
+    GH_REQUIRE((mean == nullptr) == (std_ == nullptr), "gh_stream_create: mean and std come together");
+    HostTables h;
+    int rc = build_tables(sample_rate, frame_size, frame_stride, low_freq, high_freq, h);
+    if (rc) return rc;
+    if (mean && (rc = check_affine("gh_stream_create", mean, std_, 3 * NCEPS))) return rc;
+    GH_HIP(hipSetDevice(ctx->device));
+    gh_stream* fe = new gh_stream();
+    fe->ctx = ctx; fe->dtype = dtype; fe->n_streams = n_streams; fe->max_chunk = max_chunk_samples;
+    fe->flen = h.flen; fe->fstep = h.fstep; fe->pad_left = h.pad_left;
+    fe->cap = h.flen + 2 * h.fstep + 2;
+    fe->normalise = mean != nullptr;
+    fe->samples.assign((size_t)n_streams, 0);
+    fe->ended.assign((size_t)n_streams, 0);
+    fe->rd.assign((size_t)n_streams, 0);
+    UploadArena ar;
+    std::vector<double> vm(mean ? mean : h.window.data(), (mean ? mean : h.window.data()) + 3 * NCEPS);
+    std::vector<double> vs(std_ ? std_ : h.window.data(), (std_ ? std_ : h.window.data()) + 3 * NCEPS);
+    std::vector<int16_t> carry((size_t)2 * n_streams * fe->cap, 0);
+    std::vector<double> cc((size_t)n_streams * 4 * NCEPS, 0.0);
+    double *d_window, *d_tw, *d_wup, *d_wdn, *d_dct;
+    int* d_seg;
+    ar.add(&d_window, h.window); ar.add(&d_tw, h.tw); ar.add(&d_wup, h.wup); ar.add(&d_wdn, h.wdn);
+    ar.add(&d_seg, h.seg); ar.add(&d_dct, h.dct);
+    ar.add(&fe->d_mean, vm); ar.add(&fe->d_sd, vs);
+    ar.add(&fe->d_carry, carry); ar.add(&fe->d_cc, cc);
+    rc = ar.commit(&fe->d_arena);
+    if (rc) { if (fe->d_arena) (void)hipFree(fe->d_arena); delete fe; return rc; }
+    fe->t.window = d_window; fe->t.tw = d_tw; fe->t.wup = d_wup; fe->t.wdn = d_wdn; fe->t.seg = d_seg; fe->t.dct = d_dct;
+    *out = fe;
+    return GH_OK;
+}
+
+extern "C" void gh_stream_destroy(gh_stream* fe) {
+    if (!fe) return;
+    if (fe->d_arena) (void)hipFree(fe->d_arena);
+    for (hipEvent_t e : fe->ev) if (e) (void)hipEventDestroy(e);
+    delete fe;
+}
+
+extern "C" int gh_stream_profile(gh_stream* fe, int on) {
+    GH_REQUIRE(fe, "gh_stream_profile: NULL argument");
+    if (on) {
+        GH_HIP(hipSetDevice(fe->ctx->device));
+        for (hipEvent_t& e : fe->ev) if (!e) GH_HIP(hipEventCreate(&e));
+    }
+    fe->profile = on != 0;
+    return GH_OK;
+}
+
+extern "C" int gh_stream_phase_ms(const gh_stream* fe, double* out) {
+    GH_REQUIRE(fe && out, "gh_stream_phase_ms: NULL argument");
+    memcpy(out, fe->phase_ms, sizeof(fe->phase_ms));
+    return GH_OK;
+}
+
+extern "C" int gh_stream_reset(gh_stream* fe, int64_t n, const int64_t* ids) {
+    GH_REQUIRE(fe && n >= 0, "gh_stream_reset: NULL argument");
+    if (!ids) {
+        std::fill(fe->samples.begin(), fe->samples.end(), 0);
+        std::fill(fe->ended.begin(), fe->ended.end(), 0);
+        return GH_OK;
+    }
+    for (int64_t i = 0; i < n; ++i)
+        GH_REQUIRE(ids[i] >= 0 && ids[i] < fe->n_streams, "gh_stream_reset: stream %lld of %lld", (long long)ids[i], (long long)fe->n_streams);
+    for (int64_t i = 0; i < n; ++i) { fe->samples[(size_t)ids[i]] = 0; fe->ended[(size_t)ids[i]] = 0; }
+    return GH_OK;
+}
+
+extern "C" int gh_stream_samples(const gh_stream* fe, int64_t* out) {
+    GH_REQUIRE(fe && out, "gh_stream_samples: NULL argument");
+    memcpy(out, fe->samples.data(), (size_t)fe->n_streams * 8);
+    return GH_OK;
+}
+
+extern "C" int gh_stream_push(gh_ctx* ctx, gh_stream* fe, int64_t n, const int64_t* ids, const int16_t* samples,
+                              const int64_t* sample_off, const uint8_t* end, gh_batch** out) {
+    const char* who = "gh_stream_push";
+    GH_REQUIRE(ctx && fe && out && n >= 0 && (n == 0 || (ids && sample_off)), "%s: NULL argument", who);
+    GH_REQUIRE(ctx == fe->ctx, "%s: the front-end belongs to another context", who);
+    // ---- every check before anything is enqueued: a refused push moves no stream ----
+    static const int64_t zero = 0;
+    if (n == 0) sample_off = &zero;
+    GH_REQUIRE(sample_off[0] == 0, "%s: sample_off must start at 0", who);
+    std::vector<uint8_t> seen((size_t)fe->n_streams, 0);
+    std::vector<StreamSlot> slot((size_t)n);
+    std::vector<int64_t> f_off((size_t)n + 1, 0);
+    std::vector<int32_t> pair_slot;
+    int64_t n_ceps = 0;
+    for (int64_t u = 0; u < n; ++u) {
+        const int64_t id = ids[u], len = sample_off[u + 1] - sample_off[u];
+        GH_REQUIRE(id >= 0 && id < fe->n_streams, "%s: stream %lld of %lld", who, (long long)id, (long long)fe->n_streams);
+        GH_REQUIRE(!seen[(size_t)id], "%s: stream %lld is named twice", who, (long long)id);
+        seen[(size_t)id] = 1;
+        GH_REQUIRE(len >= 0 && len <= fe->max_chunk, "%s: stream %lld gets %lld samples, max_chunk_samples %lld", who, (long long)id,
+                   (long long)len, (long long)fe->max_chunk);
+        GH_REQUIRE(!fe->ended[(size_t)id], "%s: stream %lld has ended (reset it first)", who, (long long)id);
+        StreamSlot& s = slot[(size_t)u];
+        s.id = (int32_t)id;
+        s.rd = fe->rd[(size_t)id];
+        s.chunk_off = sample_off[u];
+        s.n_before = fe->samples[(size_t)id];
+        s.n_after = s.n_before + len;
+        s.cbase = fe->carry_base(s.n_before);
+        s.c_first = fe->pairs_done(s.n_before);
+        s.f_first = std::max<int64_t>(s.c_first - 2, 0);
+        if (end && end[u]) {
+            const int64_t T = (s.n_after + fe->fstep - 1) / fe->fstep;
+            GH_REQUIRE(s.n_after >= 1 && T >= 2, "%s: stream %lld ends with %lld samples, fewer than 2 frames (delta_feature indexes feat[i + 1])",
+                       who, (long long)id, (long long)s.n_after);
+            s.T = s.c_end = s.f_end = T;
+            s.cnew = s.n_after;
+        } else {
+            s.T = INT64_MAX;
+            s.c_end = fe->pairs_done(s.n_after);
+            s.f_end = std::max<int64_t>(s.c_end - 2, 0);
+            s.cnew = fe->carry_base(s.n_after);
+        }
+        GH_REQUIRE(s.cnew >= s.cbase && s.n_after - s.cnew <= fe->cap && s.n_before - s.cbase <= fe->cap,
+                   "%s: internal: stream %lld would carry %lld samples, room for %d", who, (long long)id, (long long)(s.n_after - s.cnew), fe->cap);
+        s.out_off = f_off[(size_t)u];
+        f_off[(size_t)u + 1] = s.out_off + (s.f_end - s.f_first);
+        s.ceps_off = n_ceps;
+        n_ceps += s.c_end - s.c_first;
+        s.pair_off = (int64_t)pair_slot.size();
+        pair_slot.insert(pair_slot.end(), (size_t)((s.c_end - s.c_first + 1) / 2), (int32_t)u);
+    }
+    const int64_t total = sample_off[n], N = f_off[(size_t)n], n_pairs = (int64_t)pair_slot.size();
+    GH_REQUIRE(samples || total == 0, "%s: samples is NULL", who);
+    GH_HIP(hipSetDevice(ctx->device));
+    const size_t esz = fe->dtype == GH_F64 ? 8 : 4;
+    void* feats = nullptr;
+    if (N > 0) GH_HIP(hipMalloc(&feats, (size_t)N * 3 * NCEPS * esz));
+    gh_batch* b = nullptr;
+    int rc = gh_batch_wrap(ctx, fe->dtype, 3 * NCEPS, N, n, feats, f_off.data(), &b);
+    if (rc) { if (feats) (void)hipFree(feats); return rc; }
+    b->feats = feats;
+    b->owns_feats = true;
+    if (n > 0) {
+        int16_t* d_chunk;
+        StreamSlot* d_slot;
+        int32_t* d_pair;
+        double* d_ceps;
+        Carver cv;
+        cv.add(&d_chunk, (size_t)total + 1);
+        cv.add(&d_slot, (size_t)n);
+        cv.add(&d_pair, (size_t)n_pairs + 1);
+        cv.add(&d_ceps, (size_t)(n_ceps + 1) * NCEPS);
+        if ((rc = cv.commit(ctx))) { gh_batch_destroy(b); return rc; }
+        hipStream_t st = ctx->stream;
+        hipError_t e = hipSuccess;
+        int mark = 0;
+        auto tick = [&] { if (fe->profile && e == hipSuccess) e = hipEventRecord(fe->ev[mark++], st); };
+        tick();
+        if (total && e == hipSuccess) e = hipMemcpyAsync(d_chunk, samples, (size_t)total * 2, hipMemcpyHostToDevice, st);
+        if (e == hipSuccess) e = hipMemcpyAsync(d_slot, slot.data(), (size_t)n * sizeof(StreamSlot), hipMemcpyHostToDevice, st);
+        if (e == hipSuccess && n_pairs) e = hipMemcpyAsync(d_pair, pair_slot.data(), (size_t)n_pairs * 4, hipMemcpyHostToDevice, st);
+        tick();
+        if (e == hipSuccess && n_pairs) {
+            StreamMfccArgs a;
+            a.chunk = d_chunk; a.carry = fe->d_carry; a.slot = d_slot; a.pair_slot = d_pair;
+            a.n_pairs = n_pairs; a.n_streams = fe->n_streams;
+            a.cap = fe->cap; a.flen = fe->flen; a.fstep = fe->fstep; a.pad_left = fe->pad_left;
+            a.t = fe->t; a.ceps = d_ceps;
+            hipLaunchKernelGGL(stream_mfcc_kernel, dim3((unsigned)((n_pairs + 3) / 4)), dim3(256), 0, st, a);
+            e = hipGetLastError();
+        }
+        tick();
+        if (e == hipSuccess && N > 0) {
+            const double* m = fe->normalise ? fe->d_mean : nullptr;
+            if (fe->dtype == GH_F64)
+                hipLaunchKernelGGL((stream_stack_kernel<double>), dim3((unsigned)n), dim3(256), 0, st, d_slot, d_ceps, fe->d_cc, m, fe->d_sd, (double*)feats);
+            else
+                hipLaunchKernelGGL((stream_stack_kernel<float>), dim3((unsigned)n), dim3(256), 0, st, d_slot, d_ceps, fe->d_cc, m, fe->d_sd, (float*)feats);
+            e = hipGetLastError();
+        }
+        tick();
+        if (e == hipSuccess) {
+            hipLaunchKernelGGL(stream_carry_kernel, dim3((unsigned)n), dim3(64), 0, st, d_slot, d_chunk, fe->d_carry, fe->n_streams, fe->cap,
+                               d_ceps, fe->d_cc);
+            e = hipGetLastError();
+        }
+        tick();
+        if (e == hipSuccess) e = hipStreamSynchronize(st);   // (the uploads come from the caller's and this call's host memory)
+        for (int k = 0; k < 4 && fe->profile && e == hipSuccess; ++k) {
+            float ms = 0;
+            e = hipEventElapsedTime(&ms, fe->ev[k], fe->ev[k + 1]);
+            fe->phase_ms[k] = ms;
+        }
+        if (e != hipSuccess) {
+            gh_set_error("%s: %s", who, hipGetErrorString(e));
+            gh_batch_destroy(b);
+            return e == hipErrorOutOfMemory ? GH_ERR_NOMEM : GH_ERR_HIP;
+        }
+    }
+    for (int64_t u = 0; u < n; ++u) {
+        const size_t id = (size_t)ids[u];
+        fe->samples[id] = slot[(size_t)u].n_after;
+        fe->rd[id] ^= 1;
+        if (end && end[u]) fe->ended[id] = 1;
+    }
+    *out = b;
+    return GH_OK;
+}
+
+extern "C" int gh_batch_affine(gh_ctx* ctx, gh_batch* b, const double* mean, const double* std_) {
+    GH_REQUIRE(ctx && b && mean && std_, "gh_batch_affine: NULL argument");
+    int rc = check_affine("gh_batch_affine", mean, std_, b->D);
+    if (rc) return rc;
+    const int64_t n = b->N * b->D;
+    if (n == 0) return GH_OK;
+    GH_HIP(hipSetDevice(ctx->device));
+    double *d_mean, *d_sd;
+    Carver cv;
+    cv.add(&d_mean, (size_t)b->D);
+    cv.add(&d_sd, (size_t)b->D);
+    if ((rc = cv.commit(ctx))) return rc;
+    hipStream_t st = ctx->stream;
+    GH_HIP(hipMemcpyAsync(d_mean, mean, (size_t)b->D * 8, hipMemcpyHostToDevice, st));
+    GH_HIP(hipMemcpyAsync(d_sd, std_, (size_t)b->D * 8, hipMemcpyHostToDevice, st));
+    const dim3 grid((unsigned)((n + 255) / 256)), block(256);
+    if (b->dtype == GH_F64) hipLaunchKernelGGL((affine_kernel<double>), grid, block, 0, st, (double*)b->feats, n, b->D, d_mean, d_sd);
+    else hipLaunchKernelGGL((affine_kernel<float>), grid, block, 0, st, (float*)b->feats, n, b->D, d_mean, d_sd);
+    GH_HIP(hipGetLastError());
+    GH_HIP(hipStreamSynchronize(st));
+    b->nll_serial = 0;             // likelihoods the batch may hold belong to the features it had
+    return GH_OK;
+}

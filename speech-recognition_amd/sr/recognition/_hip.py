@@ -172,6 +172,15 @@ SIGNATURES = {
     "gh_online_create_window": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.POINTER(C.c_void_p)]),
     "gh_online_commit": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, _c_i64p, _c_i64p, _c_i32p, _c_i32p, _c_i64p, _c_i32p]),
     "gh_online_tail": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, _c_i64p, _c_f64p, _c_i32p, _c_i32p, _c_i32p, _c_i64p, _c_i32p]),
+    "gh_stream_create": (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_double, C.c_double, C.c_double, C.c_double, C.c_int64, C.c_int,
+                                   _c_f64p, _c_f64p, C.POINTER(C.c_void_p)]),
+    "gh_stream_destroy": (None, [C.c_void_p]),
+    "gh_stream_reset": (C.c_int, [C.c_void_p, C.c_int64, _c_i64p]),
+    "gh_stream_samples": (C.c_int, [C.c_void_p, _c_i64p]),
+    "gh_stream_profile": (C.c_int, [C.c_void_p, C.c_int]),
+    "gh_stream_phase_ms": (C.c_int, [C.c_void_p, _c_f64p]),
+    "gh_stream_push": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, _c_i64p, C.c_void_p, _c_i64p, _c_u8p, C.POINTER(C.c_void_p)]),
+    "gh_batch_affine": (C.c_int, [C.c_void_p, C.c_void_p, _c_f64p, _c_f64p]),
 }
 
 
@@ -870,9 +879,28 @@ class Batch:
         self.h = h
         self.S = None
 
+    @classmethod
+    def _adopt(cls, ctx, handle, offsets, dim, dtype):
+        """A handle the library returned (gh_stream_push) as a Batch that owns it."""
+        b = cls.__new__(cls)
+        b.ctx, b.np_dtype, b.h, b.S = ctx, np.dtype(dtype), handle, None
+        b.offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+        b.N, b.D, b.U = int(b.offsets[-1]), int(dim), len(b.offsets) - 1
+        return b
+
     @property
     def lengths(self):
         return np.diff(self.offsets)
+
+    def affine(self, mean, std):
+        """x -> (x - mean) / std in place (gh_batch_affine: evaluated in fp64 on the resident value, rounded to the batch
+        dtype); mean / std [D].  Likelihoods the batch holds are forgotten."""
+        mean, std = _f64(mean).reshape(-1), _f64(std).reshape(-1)
+        if len(mean) != self.D or len(std) != self.D:
+            raise ValueError("mean and std must have %d entries" % self.D)
+        _check(self.ctx.lib, self.ctx.lib.gh_batch_affine(self.ctx.h, self.h, _ptr(mean, _c_f64p), _ptr(std, _c_f64p)))
+        self.S = None
+        return self
 
     def features(self):
         """The resident feature matrix, copied back: list of [T_u, D] arrays."""
@@ -1522,6 +1550,93 @@ class OnlineSession:
         if getattr(self, "h", None):
             if getattr(self.ctx, "h", None):
                 self.ctx.lib.gh_online_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def stream_frames_ready(n_samples, flen, step, ended=False):
+    """Feature frames of a stream that are final after `n_samples` samples (scalars or arrays), for frames of `flen`
+    samples every `step`: cepstral frame t is complete when t * step + flen <= n, frames are computed in pairs (2m, 2m + 1)
+    and delta-delta looks 2 frames ahead -- max(0, (C & ~1) - 2) with C complete frames; all ceil(n / step) once ended."""
+    n = np.asarray(n_samples, dtype=np.int64)
+    c = np.where(n < flen, 0, (n - flen) // step + 1)
+    out = np.where(np.asarray(ended, dtype=bool), -(-n // step), np.maximum((c & ~np.int64(1)) - 2, 0))
+    return out if out.ndim else int(out)
+
+
+class StreamFrontend:
+    """Streaming MFCC / delta front-end (gh_stream): `n_streams` live utterances take int16 audio in chunks, `push`
+    returns the feature frames that became final as a resident `Batch` (39 columns, ragged, 0 frames allowed).  The raw
+    binding: arguments are checked by the library, which refuses with `BackendError`; `sr.feature.StreamingFrontend`
+    is the checked front."""
+
+    def __init__(self, ctx, n_streams, sample_rate=16000, mfcc_params=None, max_chunk=16000, dtype=np.float64, normalize=None):
+        fs, st, lo, hi = mfcc_params if mfcc_params is not None else (0.025, 0.01, 80, None)
+        self.ctx, self.n_streams, self.np_dtype = ctx, int(n_streams), np.dtype(dtype)
+        assert self.np_dtype in (np.dtype(np.float32), np.dtype(np.float64))
+        mean = std = None
+        if normalize is not None:
+            mean, std = _f64(normalize[0]).reshape(-1), _f64(normalize[1]).reshape(-1)
+            if len(mean) != 39 or len(std) != 39:
+                raise ValueError("normalize = (mean [39], std [39])")
+        h = C.c_void_p()
+        rc = ctx.lib.gh_stream_create(ctx.h, self.n_streams, int(sample_rate), float(fs), float(st), float(lo),
+                                      0.0 if hi is None else float(hi), int(max_chunk),
+                                      GH_F64 if self.np_dtype == np.float64 else GH_F32, _ptr(mean, _c_f64p), _ptr(std, _c_f64p),
+                                      C.byref(h))
+        if rc == GH_ERR_UNSUPPORTED:
+            raise Unsupported(ctx.lib.gh_last_error().decode("utf-8", "replace"))
+        _check(ctx.lib, rc)
+        self.h = h
+        self.flen, self.step = int(float(fs) * int(sample_rate)), int(float(st) * int(sample_rate))   # as build_tables truncates
+
+    def push(self, ids, samples, sample_off, end=None):
+        """Stream ids[u] takes samples[sample_off[u]:sample_off[u + 1]] (int16); end [n] (uint8 / bool) ends utterances."""
+        ids = np.ascontiguousarray(ids, dtype=np.int64)
+        samples = np.ascontiguousarray(samples)
+        assert samples.dtype == np.int16
+        sample_off = np.ascontiguousarray(sample_off, dtype=np.int64)
+        end = None if end is None else np.ascontiguousarray(end, dtype=np.uint8)
+        assert len(sample_off) == len(ids) + 1 and (end is None or len(end) == len(ids))
+        before = self.samples()[ids] if len(ids) else np.zeros(0, dtype=np.int64)
+        h = C.c_void_p()
+        _check(self.ctx.lib, self.ctx.lib.gh_stream_push(self.ctx.h, self.h, len(ids), _ptr(ids, _c_i64p), samples.ctypes.data_as(C.c_void_p),
+                                                         _ptr(sample_off, _c_i64p), _ptr(end, _c_u8p), C.byref(h)))
+        # the batch's utterance table is a function of the sample counts (the library computed the same)
+        fin = np.zeros(len(ids), dtype=bool) if end is None else end.astype(bool)
+        counts = (stream_frames_ready(before + np.diff(sample_off), self.flen, self.step, fin)
+                  - stream_frames_ready(before, self.flen, self.step))
+        return Batch._adopt(self.ctx, h, np.concatenate([[0], np.cumsum(counts)]), 39, self.np_dtype)
+
+    def reset(self, ids=None):
+        ids = None if ids is None else np.ascontiguousarray(ids, dtype=np.int64)
+        _check(self.ctx.lib, self.ctx.lib.gh_stream_reset(self.h, 0 if ids is None else len(ids), _ptr(ids, _c_i64p)))
+
+    def samples(self):
+        """Samples every stream has taken since its last reset: int64 [n_streams]."""
+        out = np.empty(self.n_streams, dtype=np.int64)
+        _check(self.ctx.lib, self.ctx.lib.gh_stream_samples(self.h, _ptr(out, _c_i64p)))
+        return out
+
+    def profile(self, on=True):
+        """HIP events around the phases of every push from now on (gh_stream_profile)."""
+        _check(self.ctx.lib, self.ctx.lib.gh_stream_profile(self.h, 1 if on else 0))
+
+    def phase_ms(self):
+        """dict(upload, mfcc, stack, carry): device time of the last push's phases in ms (after `profile()`)."""
+        out = np.zeros(4)
+        _check(self.ctx.lib, self.ctx.lib.gh_stream_phase_ms(self.h, _ptr(out, _c_f64p)))
+        return dict(zip(("upload", "mfcc", "stack", "carry"), out.tolist()))
+
+    def close(self):
+        if getattr(self, "h", None):
+            if getattr(self.ctx, "h", None):
+                self.ctx.lib.gh_stream_destroy(self.h)
             self.h = None
 
     def __del__(self):

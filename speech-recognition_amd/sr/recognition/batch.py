@@ -381,12 +381,13 @@ class ContinuousDecoder:
         """Decode `xs` and tally against the label strings like main.py:54-84 -- see `sequence_report`."""
         return sequence_report(self.decode(xs), labels, verbose=verbose)
 
-    def online(self, n_streams, max_frames=None, window=None):
+    def online(self, n_streams, max_frames=None, window=None, frontend=None):
         """An `OnlineDecoder` of `n_streams` live utterances sharing this decoder's packed mixtures and graph
         (grammar="loop" only: anything else raises `_hip.Unsupported`).  Exactly one of `max_frames` (utterances of up to
         that many frames, whole history kept) and `window` (utterances of any length, history for that many unsettled
-        frames) must be given."""
-        return OnlineDecoder(self, n_streams, max_frames, window)
+        frames) must be given.  frontend: a `sr.feature.StreamingFrontend` of the same context, dtype and `n_streams`
+        (39 features, like the models) -- the decoder then takes audio (`push_audio`)."""
+        return OnlineDecoder(self, n_streams, max_frames, window, frontend)
 
 
 class OnlineDecoder:
@@ -415,15 +416,35 @@ class OnlineDecoder:
     With `window=` instead of `max_frames=` a stream may run for any length: the history is a ring that holds the frames
     behind the settled prefix, and a push that would take a stream's unsettled frames (frames - settled_frames) past the
     window raises ValueError like one past `max_frames`.  There is NO forced commit: a stream whose traces have not met
-    within the window cannot take more frames and can only be finished.  A windowed decoder offers no paths."""
+    within the window cannot take more frames and can only be finished.  A windowed decoder offers no paths.
 
-    def __init__(self, decoder, n_streams, max_frames=None, window=None):
+    AUDIO.  With a `sr.feature.StreamingFrontend` the streams take int16 PCM instead of feature frames:
+
+        fe = StreamingFrontend(n_streams=64, normalize=feature_stats(training_signals))
+        on = dec.online(n_streams=64, max_frames=3000, frontend=fe)
+        on.push_audio([3, 7], [pcm_of_3, pcm_of_7])            # chunks of any length; the frames they make final are decoded
+        on.push_audio([3], [last_piece], end=[True])            # the utterance's audio ends: its remaining frames come out
+        words, info = on.finish([3])                            # ... and the id is free in both objects
+
+    `reset` / `finish` reset the front-end's streams too; `push` / `push_batch` keep working beside `push_audio`."""
+
+    def __init__(self, decoder, n_streams, max_frames=None, window=None, frontend=None):
         if decoder.grammar != "loop":
             raise _hip.Unsupported("online decoding takes the word-loop grammar (grammar='loop'), not %r" % (decoder.grammar,))
         if (max_frames is None) == (window is None):
             raise ValueError("exactly one of max_frames and window must be given")
         if int(n_streams) < 1 or int(window if max_frames is None else max_frames) < 1:
             raise ValueError("n_streams and max_frames / window must be positive")
+        if frontend is not None:
+            if frontend.ctx is not decoder.ctx:
+                raise ValueError("the front-end lives on another context than the decoder")
+            if np.dtype(frontend.dtype) != np.dtype(decoder.dtype):
+                raise ValueError("the front-end emits %s, the decoder takes %s" % (np.dtype(frontend.dtype), np.dtype(decoder.dtype)))
+            if frontend.D != decoder.gmm.D:
+                raise ValueError("the front-end emits %d features, the models take %d" % (frontend.D, decoder.gmm.D))
+            if frontend.n_streams != int(n_streams):
+                raise ValueError("the front-end has %d streams, the decoder %d" % (frontend.n_streams, int(n_streams)))
+        self.frontend = frontend
         self.decoder = decoder
         self.n_streams = int(n_streams)
         self.max_frames = None if max_frames is None else int(max_frames)
@@ -513,6 +534,24 @@ class OnlineDecoder:
         self.session.push(batch, ids, first, count)
         self._frames[ids] += count
 
+    def push_audio(self, ids, chunks, end=None):
+        """Stream ids[i] takes the int16 samples chunks[i] through the decoder's `StreamingFrontend` (`online(...,
+        frontend=)`) and then the frames those samples made final; end[i] true ends the utterance's audio (its remaining
+        frames come out; `finish` then frees the id).  The frames every stream will receive are computed on the host first:
+        a push that the front-end would refuse, or one past `max_frames` / `window`, raises ValueError with nothing moved
+        in either object."""
+        if self.frontend is None:
+            raise ValueError("this decoder has no front-end: dec.online(..., frontend=StreamingFrontend(...))")
+        ids, chunks, end, counts = self.frontend.plan(ids, chunks, end)
+        self._room(ids, counts)
+        batch = self.frontend._push(ids, chunks, end, counts)
+        try:
+            if counts.sum():
+                self.push_batch(ids, batch)
+                self.decoder.ctx.sync()                   # (the batch's matrix is read until the sweep is done)
+        finally:
+            batch.close()
+
     def result(self, ids=None, want_path=False):
         """(word-index lists, dict(end_cost [n, n_end], best_end [n], frames [n][, paths])) of the streams `ids` (None:
         all) for the frames pushed so far: what `decode_batch` returns for those frames as whole utterances."""
@@ -552,6 +591,8 @@ class OnlineDecoder:
         """The streams `ids` (None: all) start again at frame 0, with nothing settled."""
         ids = None if ids is None else self._ids(ids, distinct=False)
         self.session.reset(ids)
+        if self.frontend is not None:
+            self.frontend.reset(ids)
         if ids is None:
             self._frames[:] = 0
             self._settled[:] = 0
