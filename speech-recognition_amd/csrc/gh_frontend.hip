@@ -6,16 +6,10 @@
 // composed by load_wav_as_mfcc (sr/core.py:41-44).  fp64 arithmetic, HBM-bound.
 #include "gh_internal.h"
 #include "gh_host.h"
+#include "gh_delta.h"
 #include <functional>
 
 namespace {
-
-__device__ __forceinline__ double delta_at(const double* __restrict__ f, int t, int T, int C, int c) {
-    // f: [T,C] of one utterance
-    if (t == 0) return f[(int64_t)C + c] - f[c];
-    if (t == T - 1) return f[(int64_t)t * C + c] - f[(int64_t)(t - 1) * C + c];
-    return f[(int64_t)(t + 1) * C + c] - f[(int64_t)(t - 1) * C + c];
-}
 
 // one workgroup per utterance; raw: [N,3C] fp64 scratch
 __global__ __launch_bounds__(256) void stack_kernel(const double* __restrict__ ceps, const int64_t* __restrict__ off, int C,
@@ -23,16 +17,13 @@ __global__ __launch_bounds__(256) void stack_kernel(const double* __restrict__ c
     const int64_t f0 = off[blockIdx.x];
     const int T = (int)(off[blockIdx.x + 1] - f0);
     if (T < 2) return;
-    const double* f = ceps + f0 * C;
+    const double* f = ceps + f0 * C;   // [T,C] of one utterance
     double* o = raw + f0 * 3 * C;
     for (int i = threadIdx.x; i < T * C; i += blockDim.x) {
         const int t = i / C, c = i % C;
-        const double d = delta_at(f, t, T, C, c);
-        double dd;  // delta of the delta track, same edge rules
-        if (t == 0) dd = delta_at(f, 1, T, C, c) - d;
-        else if (t == T - 1) dd = d - delta_at(f, t - 1, T, C, c);
-        else dd = delta_at(f, t + 1, T, C, c) - delta_at(f, t - 1, T, C, c);
-        o[(int64_t)t * 3 * C + c] = f[(int64_t)t * C + c];
+        double x, d, dd;
+        delta_stack([&](int r, int k) { return f[(int64_t)r * C + k]; }, t, T, c, x, d, dd);
+        o[(int64_t)t * 3 * C + c] = x;
         o[(int64_t)t * 3 * C + C + c] = d;
         o[(int64_t)t * 3 * C + 2 * C + c] = dd;
     }
