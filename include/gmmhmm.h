@@ -758,6 +758,46 @@ int gh_stream_push(gh_ctx* ctx, gh_stream* fe, int64_t n, const int64_t* ids /*[
                    const int64_t* sample_off /*[n+1]*/, const uint8_t* end /*[n] or NULL*/, gh_batch** out);
 int gh_batch_affine(gh_ctx* ctx, gh_batch* b, const double* mean /*[D]*/, const double* std_ /*[D]*/);
 
+/* ------------------------------------------------ streaming endpoint detection: audio chunks in, start / end events out
+ * gh_endpoints for n_streams live recordings whose int16 audio arrives in pieces of any size: the reference's
+ * record_callback (:116-174) as it runs, once per chunk with its state carried, on the device for many streams at once.
+ * CONTRACT: however a recording is cut, its stream's events, frames_done and per-frame values are exactly those of
+ * gh_endpoints(max_segments = large) on the whole recording (same integer sums, same fp64 operations in the same order).
+ * After n samples a stream has classified gh_endpoint_frames(n, width, stride) frames.  Carried on the device per stream:
+ * level, background, the carried decision, started and the two counters (32 B), and the samples from the first sample of
+ * the next frame to classify up to the newest.  gh_epstream_create requires width % stride == 0 (GH_ERR_INVALID otherwise):
+ * the carry is then always shorter than 2 width - stride samples; without it the reference's frames fall behind the audio by
+ * width - (width / stride) stride samples per chunk, without bound (such recordings are for gh_endpoints).  The limit of the
+ * energy kernel is that of gh_endpoints (GH_ERR_UNSUPPORTED).
+ * gh_epstream_push: stream ids[u] takes samples [sample_off[u], sample_off[u+1]) of `samples` (0 .. max_chunk_samples of
+ * them); end[u] != 0 (end may be NULL) ends its recording with this chunk.  Everything is checked before anything is
+ * enqueued and a refused push (GH_ERR_INVALID) moves no stream: an id twice or out of range, a chunk over
+ * max_chunk_samples, a stream that has ended and was not reset.  Events come back ordered by position in ids, then by time:
+ * ev_stream, ev_kind (0 = start at sample i stride, 1 = end at sample i stride + width), ev_sample, ev_open; the detector
+ * re-arms after every end with all state left as it is (the semantics of max_segments > 1, without a cap).  A recording
+ * that ends while speech is open gets a closing event: kind 1, sample n - 1, ev_open = 1.  ev_cap = the room of the four
+ * event arrays; two events of a stream are at least g = max(1, min(speech_frames, silence_frames) + 1) frames apart, so
+ * the push can emit at most sum_u ((new frames of u + g - 1) / g + 1) events and ev_cap must be at least that.
+ * frames_done[n] / started[n]: frames classified so far and the `started` register of every stream of the push, after it.
+ * Optional per-frame outputs of the NEWLY classified frames (all four or none), addressed by frame_off[n+1] built from the
+ * differences of gh_endpoint_frames: as for gh_endpoints.  Synchronises.
+ * gh_epstream_reset: streams ids[0..n) (NULL: all) start a new recording at sample 0; nothing happens on the device.
+ * gh_epstream_samples: samples every stream has taken since its last reset.
+ * gh_epstream_profile(on) / gh_epstream_phase_ms: HIP events around the last push's upload, energy kernel, classifier
+ * kernel and carry kernel, in ms (measurement plumbing, as gh_stream_profile). */
+typedef struct gh_epstream gh_epstream;
+int gh_epstream_create(gh_ctx* ctx, int64_t n_streams, const gh_endpoint_params* prm, int64_t max_chunk_samples, gh_epstream** out);
+void gh_epstream_destroy(gh_epstream* ep);
+int gh_epstream_reset(gh_epstream* ep, int64_t n, const int64_t* ids /*[n] or NULL*/);
+int gh_epstream_samples(const gh_epstream* ep, int64_t* out /*[n_streams]*/);
+int gh_epstream_profile(gh_epstream* ep, int on);
+int gh_epstream_phase_ms(const gh_epstream* ep, double* out /*[4]*/);
+int gh_epstream_push(gh_ctx* ctx, gh_epstream* ep, int64_t n, const int64_t* ids /*[n], distinct*/, const int16_t* samples,
+                     const int64_t* sample_off /*[n+1]*/, const uint8_t* end /*[n] or NULL*/, int64_t ev_cap, int64_t* n_events,
+                     int64_t* ev_stream /*[ev_cap]*/, uint8_t* ev_kind, int64_t* ev_sample, uint8_t* ev_open,
+                     int64_t* frames_done /*[n]*/, uint8_t* started /*[n]*/, const int64_t* frame_off /*[n+1] or NULL*/,
+                     uint8_t* out_is_speech, double* out_level, double* out_background, double* out_energy);
+
 #ifdef __cplusplus
 }
 #endif

@@ -26,7 +26,9 @@ EXTRA = {"gh_loglik_mfma.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"],
          # instantiation of a refit kernel then round alike (hipcc's default, fast, left them 1e-15 apart)
          "gh_refit_mfma.hip": ["-ffp-contract=on"],
          # no contraction at all: the endpoint classifier rounds every product and sum like the reference's numpy scalars
-         "gh_endpoint.hip": ["-ffp-contract=off"]}
+         "gh_endpoint.hip": ["-ffp-contract=off"],
+         # ... and the streaming detector rounds like the one-shot one
+         "gh_endpoint_stream.hip": ["-ffp-contract=off"]}
 
 
 def _sources():

@@ -181,6 +181,14 @@ SIGNATURES = {
     "gh_stream_phase_ms": (C.c_int, [C.c_void_p, _c_f64p]),
     "gh_stream_push": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, _c_i64p, C.c_void_p, _c_i64p, _c_u8p, C.POINTER(C.c_void_p)]),
     "gh_batch_affine": (C.c_int, [C.c_void_p, C.c_void_p, _c_f64p, _c_f64p]),
+    "gh_epstream_create": (C.c_int, [C.c_void_p, C.c_int64, C.POINTER(EndpointParams), C.c_int64, C.POINTER(C.c_void_p)]),
+    "gh_epstream_destroy": (None, [C.c_void_p]),
+    "gh_epstream_reset": (C.c_int, [C.c_void_p, C.c_int64, _c_i64p]),
+    "gh_epstream_samples": (C.c_int, [C.c_void_p, _c_i64p]),
+    "gh_epstream_profile": (C.c_int, [C.c_void_p, C.c_int]),
+    "gh_epstream_phase_ms": (C.c_int, [C.c_void_p, _c_f64p]),
+    "gh_epstream_push": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, _c_i64p, C.c_void_p, _c_i64p, _c_u8p, C.c_int64, _c_i64p, _c_i64p,
+                                   _c_u8p, _c_i64p, _c_u8p, _c_i64p, _c_u8p, _c_i64p, _c_u8p, _c_f64p, _c_f64p, _c_f64p]),
 }
 
 
@@ -1637,6 +1645,106 @@ class StreamFrontend:
         if getattr(self, "h", None):
             if getattr(self.ctx, "h", None):
                 self.ctx.lib.gh_stream_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def endpoint_event_room(new_frames, speech_frames, silence_frames):
+    """Events one stream can emit in a push that classifies `new_frames` frames (a scalar or an array): two events are at
+    least min(speech_frames, silence_frames) + 1 frames apart, plus one for the closing event (gh_epstream_push)."""
+    g = max(1, min(int(speech_frames), int(silence_frames)) + 1)
+    return (np.asarray(new_frames, dtype=np.int64) + g - 1) // g + 1
+
+
+class EndpointStream:
+    """Streaming endpoint detection (gh_epstream): `n_streams` live recordings take int16 audio in chunks, `push` returns
+    the start / end events the new frames produced.  The raw binding: arguments are checked by the library, which refuses
+    with `BackendError`; `sr.audio_capture.StreamingEndpointer` is the checked front.  cfg: a DERIVED config."""
+
+    def __init__(self, ctx, n_streams, cfg, max_chunk=16000):
+        self.ctx, self.n_streams, self.max_chunk = ctx, int(n_streams), int(max_chunk)
+        self.prm = endpoint_params(cfg)
+        h = C.c_void_p()
+        rc = ctx.lib.gh_epstream_create(ctx.h, self.n_streams, C.byref(self.prm), self.max_chunk, C.byref(h))
+        if rc == GH_ERR_UNSUPPORTED:
+            raise Unsupported(ctx.lib.gh_last_error().decode("utf-8", "replace"))
+        _check(ctx.lib, rc)
+        self.h = h
+
+    def frames_after(self, n_samples):
+        """gh_endpoint_frames of an array of sample counts."""
+        n = np.asarray(n_samples, dtype=np.int64)
+        w, s = int(self.prm.width), int(self.prm.stride)
+        return np.where(n // w == 0, 0, 1 + (w // s) * (n // w - 1))
+
+    def push(self, ids, samples, sample_off, end=None, want_frames=False):
+        """Stream ids[u] takes samples[sample_off[u]:sample_off[u + 1]] (int16); end [n] (uint8 / bool) ends recordings.
+        dict(stream, kind, sample, open: one entry per event, by position in ids, then by time; frames_done, started [n]
+        [, frame_off [n + 1], is_speech, level, background, energy: lists of arrays of the newly classified frames])."""
+        ids = np.ascontiguousarray(ids, dtype=np.int64)
+        samples = np.ascontiguousarray(samples)
+        assert samples.dtype == np.int16
+        sample_off = np.ascontiguousarray(sample_off, dtype=np.int64)
+        end = None if end is None else np.ascontiguousarray(end, dtype=np.uint8)
+        n = len(ids)
+        assert len(sample_off) == n + 1 and (end is None or len(end) == n)
+        # the frames every stream gains are a function of the sample counts (the library computes the same and checks)
+        ok = (ids >= 0) & (ids < self.n_streams)
+        before = np.where(ok, self.samples()[np.where(ok, ids, 0)], 0) if n else np.zeros(0, dtype=np.int64)
+        new = self.frames_after(before + np.diff(sample_off)) - self.frames_after(before) if n else np.zeros(0, dtype=np.int64)
+        new = np.maximum(new, 0)
+        cap = int(endpoint_event_room(new, self.prm.speech_frames, self.prm.silence_frames).sum()) if n else 0
+        ev_stream, ev_sample = np.zeros(cap, dtype=np.int64), np.zeros(cap, dtype=np.int64)
+        ev_kind, ev_open = np.zeros(cap, dtype=np.uint8), np.zeros(cap, dtype=np.uint8)
+        n_ev = C.c_int64(0)
+        done, started = np.zeros(n, dtype=np.int64), np.zeros(n, dtype=np.uint8)
+        f_off = attr = level = bg = energy = None
+        if want_frames:
+            f_off = np.concatenate([[0], np.cumsum(new)]).astype(np.int64)
+            N = int(f_off[-1])
+            attr, level, bg, energy = np.zeros(N, dtype=np.uint8), np.zeros(N), np.zeros(N), np.zeros(N)
+        _check(self.ctx.lib, self.ctx.lib.gh_epstream_push(
+            self.ctx.h, self.h, n, _ptr(ids, _c_i64p), samples.ctypes.data_as(C.c_void_p), _ptr(sample_off, _c_i64p), _ptr(end, _c_u8p),
+            cap, C.byref(n_ev), _ptr(ev_stream, _c_i64p), _ptr(ev_kind, _c_u8p), _ptr(ev_sample, _c_i64p), _ptr(ev_open, _c_u8p),
+            _ptr(done, _c_i64p), _ptr(started, _c_u8p), _ptr(f_off, _c_i64p), _ptr(attr, _c_u8p), _ptr(level, _c_f64p),
+            _ptr(bg, _c_f64p), _ptr(energy, _c_f64p)))
+        k = int(n_ev.value)
+        r = dict(stream=ev_stream[:k], kind=ev_kind[:k].astype(np.int64), sample=ev_sample[:k], open=ev_open[:k].astype(bool),
+                 frames_done=done, started=started.astype(bool))
+        if want_frames:
+            cut = lambda a: [a[f_off[u]:f_off[u + 1]] for u in range(n)]
+            r.update(frame_off=f_off, is_speech=cut(attr.astype(bool)), level=cut(level), background=cut(bg), energy=cut(energy))
+        return r
+
+    def reset(self, ids=None):
+        ids = None if ids is None else np.ascontiguousarray(ids, dtype=np.int64)
+        _check(self.ctx.lib, self.ctx.lib.gh_epstream_reset(self.h, 0 if ids is None else len(ids), _ptr(ids, _c_i64p)))
+
+    def samples(self):
+        """Samples every stream has taken since its last reset: int64 [n_streams]."""
+        out = np.empty(self.n_streams, dtype=np.int64)
+        _check(self.ctx.lib, self.ctx.lib.gh_epstream_samples(self.h, _ptr(out, _c_i64p)))
+        return out
+
+    def profile(self, on=True):
+        """HIP events around the phases of every push from now on (gh_epstream_profile)."""
+        _check(self.ctx.lib, self.ctx.lib.gh_epstream_profile(self.h, 1 if on else 0))
+
+    def phase_ms(self):
+        """dict(upload, energy, classify, carry): device time of the last push's phases in ms (after `profile()`)."""
+        out = np.zeros(4)
+        _check(self.ctx.lib, self.ctx.lib.gh_epstream_phase_ms(self.h, _ptr(out, _c_f64p)))
+        return dict(zip(("upload", "energy", "classify", "carry"), out.tolist()))
+
+    def close(self):
+        if getattr(self, "h", None):
+            if getattr(self.ctx, "h", None):
+                self.ctx.lib.gh_epstream_destroy(self.h)
             self.h = None
 
     def __del__(self):

@@ -381,13 +381,15 @@ class ContinuousDecoder:
         """Decode `xs` and tally against the label strings like main.py:54-84 -- see `sequence_report`."""
         return sequence_report(self.decode(xs), labels, verbose=verbose)
 
-    def online(self, n_streams, max_frames=None, window=None, frontend=None):
+    def online(self, n_streams, max_frames=None, window=None, frontend=None, endpointer=None):
         """An `OnlineDecoder` of `n_streams` live utterances sharing this decoder's packed mixtures and graph
         (grammar="loop" only: anything else raises `_hip.Unsupported`).  Exactly one of `max_frames` (utterances of up to
         that many frames, whole history kept) and `window` (utterances of any length, history for that many unsettled
         frames) must be given.  frontend: a `sr.feature.StreamingFrontend` of the same context, dtype and `n_streams`
-        (39 features, like the models) -- the decoder then takes audio (`push_audio`)."""
-        return OnlineDecoder(self, n_streams, max_frames, window, frontend)
+        (39 features, like the models) -- the decoder then takes audio (`push_audio`).  endpointer: a
+        `sr.audio_capture.StreamingEndpointer` of the same context, sample rate and `n_streams` (needs a front-end) -- the
+        decoder then takes whole recordings and cuts the utterances out itself (`push_recording`)."""
+        return OnlineDecoder(self, n_streams, max_frames, window, frontend, endpointer)
 
 
 class OnlineDecoder:
@@ -426,9 +428,25 @@ class OnlineDecoder:
         on.push_audio([3], [last_piece], end=[True])            # the utterance's audio ends: its remaining frames come out
         words, info = on.finish([3])                            # ... and the id is free in both objects
 
-    `reset` / `finish` reset the front-end's streams too; `push` / `push_batch` keep working beside `push_audio`."""
+    `reset` / `finish` reset the front-end's streams too; `push` / `push_batch` keep working beside `push_audio`.
 
-    def __init__(self, decoder, n_streams, max_frames=None, window=None, frontend=None):
+    RECORDINGS.  A microphone stream carries no end flag.  With a `sr.audio_capture.StreamingEndpointer` as well, the
+    streams take the recording as it arrives and the utterances are cut out by the endpoint detector:
+
+        ep = StreamingEndpointer(n_streams=64, config=default_config(16000), max_chunk=3200)
+        fe = StreamingFrontend(n_streams=64, normalize=stats, max_chunk=ep.max_piece)
+        on = dec.online(n_streams=64, window=400, frontend=fe, endpointer=ep)
+        for utt in on.push_recording([3, 7], [pcm_of_3, pcm_of_7]):       # every tick; end=[...] ends a recording
+            print(utt["stream"], utt["words"], utt["begin"], utt["stop"], utt["open"])
+
+    `push_recording` returns the utterances that ended with this call; `begin` / `stop` are the slice of the recording
+    (`trim_ranges` of the offline detection; a recording without a segment yields no utterance).  The audio crosses the
+    host link twice, once for the endpointer and once for the front-end.  If the decoder or the front-end refuses a
+    piece (`max_frames`, `window`), the endpointer has already moved: `push_recording` raises ValueError naming the
+    streams, and they must be `reset`.  With an endpointer `reset` starts a new RECORDING (all three objects), `finish`
+    a new utterance (decoder and front-end only)."""
+
+    def __init__(self, decoder, n_streams, max_frames=None, window=None, frontend=None, endpointer=None):
         if decoder.grammar != "loop":
             raise _hip.Unsupported("online decoding takes the word-loop grammar (grammar='loop'), not %r" % (decoder.grammar,))
         if (max_frames is None) == (window is None):
@@ -444,7 +462,24 @@ class OnlineDecoder:
                 raise ValueError("the front-end emits %d features, the models take %d" % (frontend.D, decoder.gmm.D))
             if frontend.n_streams != int(n_streams):
                 raise ValueError("the front-end has %d streams, the decoder %d" % (frontend.n_streams, int(n_streams)))
+        if endpointer is not None:
+            if frontend is None:
+                raise ValueError("an endpointer needs a front-end: dec.online(..., frontend=StreamingFrontend(...), endpointer=...)")
+            if endpointer.ctx is not decoder.ctx:
+                raise ValueError("the endpointer lives on another context than the decoder")
+            if endpointer.sample_rate != frontend.sample_rate:
+                raise ValueError("the endpointer takes %d Hz, the front-end %d Hz" % (endpointer.sample_rate, frontend.sample_rate))
+            if endpointer.n_streams != int(n_streams):
+                raise ValueError("the endpointer has %d streams, the decoder %d" % (endpointer.n_streams, int(n_streams)))
+            if frontend.max_chunk < endpointer.max_piece:
+                raise ValueError("the front-end takes chunks of %d samples, the gate can hand out %d ('start boundary' %d + carry %d + "
+                                 "the endpointer's max_chunk %d)" % (frontend.max_chunk, endpointer.max_piece, endpointer.boundary,
+                                                                    endpointer.carry_cap, endpointer.max_chunk))
+            if -(-endpointer.min_utterance // frontend.step) < 2:
+                raise ValueError("the shortest utterance of this endpoint config has %d samples: fewer than 2 frames of %d samples' stride"
+                                 % (endpointer.min_utterance, frontend.step))
         self.frontend = frontend
+        self.endpointer = endpointer
         self.decoder = decoder
         self.n_streams = int(n_streams)
         self.max_frames = None if max_frames is None else int(max_frames)
@@ -587,9 +622,42 @@ class OnlineDecoder:
         ids = np.arange(self.n_streams, dtype=np.int64) if ids is None else self._ids(ids, distinct=False)
         return [list(self._words[k]) for k in ids], self._settled[ids].copy()
 
+    def push_recording(self, ids, chunks, end=None):
+        """Stream ids[i] takes the int16 samples chunks[i] of its RECORDING through the decoder's `StreamingEndpointer`
+        (`online(..., endpointer=)`); what its gate lets through goes on through `push_audio` (with `window=`, followed by
+        `commit`), and utterances that ended are finished.  end[i] true ends the recording.  Returns the finished
+        utterances in order: dicts `stream`, `words`, `begin`, `stop` (recording sample coordinates), `open` (the
+        recording ended while speech was open).  A bad argument raises ValueError with nothing moved; a piece that the
+        decoder or the front-end refuses raises ValueError AFTER the endpointer has moved: the streams it names must be
+        `reset`."""
+        if self.endpointer is None:
+            raise ValueError("this decoder has no endpointer: dec.online(..., frontend=..., endpointer=StreamingEndpointer(...))")
+        out = []
+        for r_ids, pieces, flags, ranges in self.endpointer.gate(ids, chunks, end):
+            try:
+                self.push_audio(r_ids, pieces, flags)
+            except ValueError as e:
+                raise ValueError("streams %s: the decoder refused what the endpointer let through (%s); the endpointer has moved: "
+                                 "reset these streams" % (r_ids.tolist(), e))
+            if self.window is not None:
+                self.commit(r_ids)
+            done = r_ids[flags]
+            if len(done):
+                words, _ = self.result(done)
+                self._reset_utterance(done)
+                for k, w, rg in zip(done, words, [rg for rg in ranges if rg is not None]):
+                    out.append(dict(stream=int(k), words=w, begin=int(rg[0]), stop=int(rg[1]), open=bool(rg[2])))
+        return out
+
     def reset(self, ids=None):
-        """The streams `ids` (None: all) start again at frame 0, with nothing settled."""
+        """The streams `ids` (None: all) start again at frame 0, with nothing settled -- and, with an endpointer, at sample
+        0 of a new recording."""
         ids = None if ids is None else self._ids(ids, distinct=False)
+        if self.endpointer is not None:
+            self.endpointer.reset(ids)
+        self._reset_utterance(ids)
+
+    def _reset_utterance(self, ids):
         self.session.reset(ids)
         if self.frontend is not None:
             self.frontend.reset(ids)
@@ -603,9 +671,10 @@ class OnlineDecoder:
             self._words[int(k)] = []
 
     def finish(self, ids, want_path=False):
-        """`result(ids)` followed by `reset(ids)`: the final decode of utterances that have ended; their ids are free."""
+        """`result(ids)` followed by a reset of the decoder's and the front-end's streams: the final decode of utterances
+        that have ended; their ids are free (an endpointer's recording goes on)."""
         out = self.result(ids, want_path=want_path)
-        self.reset(ids)
+        self._reset_utterance(None if ids is None else self._ids(ids, distinct=False))
         return out
 
     def close(self):
