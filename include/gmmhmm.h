@@ -721,6 +721,40 @@ int gh_online_commit(gh_ctx* ctx, gh_online* on, int64_t n, const int64_t* ids /
 int gh_online_tail(gh_ctx* ctx, gh_online* on, int64_t n, const int64_t* ids /*[n] or NULL*/, double* end_cost, int32_t* best_end,
                    const int32_t* row_label, int32_t* labels, const int64_t* label_off /*[n+1]*/, int32_t* n_labels);
 
+/* ------------------------------------------------ online isolated-word recognition: A5 while the audio is still arriving
+ * HMM.evaluate (hmm.py:126-135) of every word model, carried across the chunks of n_streams live utterances: the cost of a
+ * word is the last state's cell of the last column, and a column depends on the previous column only, so a stream keeps
+ * ONE cost column on the device ([N states][C chains] doubles, fp64 for fp32 likelihoods too: 400 B at 10 words x 5
+ * states) and nothing else -- no decision history, hence no capacity: a stream may run for any length.
+ * CONTRACT: for a stream that holds k >= 2 frames, gh_wordstream_result returns bitwise the end costs gh_viterbi
+ * (want_path = 0) returns for a one-utterance decode of those k frames from the same likelihoods.  A stream that holds
+ * exactly ONE frame shows column 0 of every longer decode (start rows hold their emission, all other rows +inf); the
+ * reference's one-frame special case (the column wrap of decode.py:109-114) is not reproduced.
+ * gh_wordstream_create: `lat` must be ONE graph in the chain form whose chains all have the same number of rows, 1 .. 8,
+ * with consecutive states (stacked word models), without a beam, and must outlive the session; a loop, bigram or K-layer
+ * graph, chains of unequal length or of more than 8 rows, several graphs or a beam are GH_ERR_UNSUPPORTED and the message
+ * names the reason (there is no other path).
+ * gh_wordstream_push: as gh_online_push -- stream ids[u] takes the columns [first[u], first[u] + count[u]) of utterance u
+ * of the batch, whose likelihood matrix must be resident (gh_loglik); first NULL: 0, count NULL: to the utterance's end;
+ * count 0 is a stream that sits the tick out.  Everything is checked before anything is enqueued, and a refused push
+ * (GH_ERR_INVALID: an id twice or out of range, a column range outside the utterance, a batch without likelihoods, a graph
+ * that uses a state the model lacks, a foreign context) moves no stream.  The call only enqueues work on the context's
+ * stream; the batch must stay alive until that work is done.
+ * gh_wordstream_result: end_cost [n, n_end] of the streams ids[0..n) (NULL: all n_streams) and best [n], the index of the
+ * cheapest end as the FIRST of equal minima (np.argmin, core.py:82-87 -- not the last-of-equal rule of decode.py:129-134);
+ * a stream without frames gives +inf and -1.  Either output may be NULL.  Synchronises. */
+typedef struct gh_wordstream gh_wordstream;
+int gh_wordstream_create(gh_ctx* ctx, const gh_lattices* lat, int64_t n_streams, gh_wordstream** out);
+void gh_wordstream_destroy(gh_wordstream* ws);
+/* streams ids[0..n) (NULL: all) start again at column 0; nothing happens on the device */
+int gh_wordstream_reset(gh_ctx* ctx, gh_wordstream* ws, int64_t n, const int64_t* ids /*[n] or NULL*/);
+/* frames every stream has taken since its last reset */
+int gh_wordstream_frames(const gh_wordstream* ws, int64_t* out /*[n_streams]*/);
+int gh_wordstream_push(gh_ctx* ctx, gh_wordstream* ws, const gh_batch* b, const int64_t* ids /*[U], distinct*/,
+                       const int64_t* first /*[U] or NULL*/, const int64_t* count /*[U] or NULL*/);
+int gh_wordstream_result(gh_ctx* ctx, gh_wordstream* ws, int64_t n, const int64_t* ids /*[n] or NULL*/,
+                         double* end_cost /*[n, n_end]*/, int32_t* best /*[n]*/);
+
 /* ------------------------------------------------ streaming front-end: audio chunks in, final feature frames out
  * gh_batch_create_from_pcm(mode 1) for n_streams live utterances whose int16 audio arrives in pieces of any size: a push
  * returns exactly the frames [cepstra | delta | delta-delta] (39 columns) that have become final.

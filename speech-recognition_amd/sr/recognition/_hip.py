@@ -172,6 +172,12 @@ SIGNATURES = {
     "gh_online_create_window": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.POINTER(C.c_void_p)]),
     "gh_online_commit": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, _c_i64p, _c_i64p, _c_i32p, _c_i32p, _c_i64p, _c_i32p]),
     "gh_online_tail": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, _c_i64p, _c_f64p, _c_i32p, _c_i32p, _c_i32p, _c_i64p, _c_i32p]),
+    "gh_wordstream_create": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_void_p)]),
+    "gh_wordstream_destroy": (None, [C.c_void_p]),
+    "gh_wordstream_reset": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, _c_i64p]),
+    "gh_wordstream_frames": (C.c_int, [C.c_void_p, _c_i64p]),
+    "gh_wordstream_push": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, _c_i64p, _c_i64p, _c_i64p]),
+    "gh_wordstream_result": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, _c_i64p, _c_f64p, _c_i32p]),
     "gh_stream_create": (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_double, C.c_double, C.c_double, C.c_double, C.c_int64, C.c_int,
                                    _c_f64p, _c_f64p, C.POINTER(C.c_void_p)]),
     "gh_stream_destroy": (None, [C.c_void_p]),
@@ -1558,6 +1564,73 @@ class OnlineSession:
         if getattr(self, "h", None):
             if getattr(self.ctx, "h", None):
                 self.ctx.lib.gh_online_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class WordStreamSession:
+    """Online isolated-word recognition over ONE graph of stacked word chains (gh_wordstream): `n_streams` live utterances
+    whose previous cost column stays on the device -- and nothing else, so a stream may run for any length.  `push`
+    advances streams by chunks of resident likelihoods; `result` is, from two frames on, bitwise the end costs of the
+    one-shot decode of the frames a stream has taken (one frame: column 0 of every longer decode).  `lat` (a `Lattices`
+    with one graph whose chains all have the same 1 .. 8 consecutive states) must outlive the session; any other graph
+    raises `Unsupported`."""
+
+    def __init__(self, ctx, lat, n_streams):
+        self.ctx, self.lat = ctx, lat
+        self.n_streams = int(n_streams)
+        h = C.c_void_p()
+        rc = ctx.lib.gh_wordstream_create(ctx.h, lat.h, self.n_streams, C.byref(h))
+        if rc == GH_ERR_UNSUPPORTED:
+            raise Unsupported(ctx.lib.gh_last_error().decode("utf-8", "replace"))
+        _check(ctx.lib, rc)
+        self.h = h
+        self.n_end = int(lat.n_end[0])
+
+    @staticmethod
+    def _i64(a):
+        return None if a is None else np.ascontiguousarray(a, dtype=np.int64)
+
+    def push(self, batch, ids, first=None, count=None):
+        """Stream ids[u] takes the columns [first[u], first[u] + count[u]) of utterance u of `batch` (likelihoods resident;
+        first None: 0, count None: to the utterance's end).  Only enqueues work: keep the batch alive until it is done."""
+        ids, first, count = self._i64(ids), self._i64(first), self._i64(count)
+        assert len(ids) == batch.U and (first is None or len(first) == batch.U) and (count is None or len(count) == batch.U)
+        _check(self.ctx.lib, self.ctx.lib.gh_wordstream_push(self.ctx.h, self.h, batch.h, _ptr(ids, _c_i64p), _ptr(first, _c_i64p),
+                                                             _ptr(count, _c_i64p)))
+
+    def reset(self, ids=None):
+        ids = self._i64(ids)
+        _check(self.ctx.lib, self.ctx.lib.gh_wordstream_reset(self.ctx.h, self.h, 0 if ids is None else len(ids), _ptr(ids, _c_i64p)))
+
+    def frames(self):
+        """Frames every stream has taken since its last reset: int64 [n_streams]."""
+        out = np.empty(self.n_streams, dtype=np.int64)
+        _check(self.ctx.lib, self.ctx.lib.gh_wordstream_frames(self.h, _ptr(out, _c_i64p)))
+        return out
+
+    def result(self, ids=None):
+        """dict(costs [n, W]: the cost of every word's end, best [n]: the cheapest word, first of equal minima (-1: no
+        frames), frames [n]) for the streams `ids` (None: all)."""
+        ids = np.arange(self.n_streams, dtype=np.int64) if ids is None else self._i64(ids)
+        n = len(ids)
+        ok = (ids >= 0) & (ids < self.n_streams)                          # an id out of range is the library's to refuse
+        T = np.where(ok, self.frames()[np.where(ok, ids, 0)], 0) if n else np.zeros(0, dtype=np.int64)
+        costs = np.empty((n, self.n_end), dtype=np.float64)
+        best = np.empty(n, dtype=np.int32)
+        _check(self.ctx.lib, self.ctx.lib.gh_wordstream_result(self.ctx.h, self.h, n, _ptr(ids, _c_i64p), _ptr(costs, _c_f64p),
+                                                               _ptr(best, _c_i32p)))
+        return dict(costs=costs, best=best, frames=T)
+
+    def close(self):
+        if getattr(self, "h", None):
+            if getattr(self.ctx, "h", None):
+                self.ctx.lib.gh_wordstream_destroy(self.h)
             self.h = None
 
     def __del__(self):

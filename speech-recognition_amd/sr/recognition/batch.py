@@ -13,7 +13,7 @@ from . import _hip
 from . import _pack
 from .continuous_speech import packed_lattice, packed_loop_lattice, packed_bigram_lattice
 
-__all__ = ["IsolatedWordRecognizer", "ContinuousDecoder", "OnlineDecoder", "InFlight", "path_to_words", "sequence_report", "train_words"]
+__all__ = ["IsolatedWordRecognizer", "ContinuousDecoder", "OnlineDecoder", "OnlineWordRecognizer", "InFlight", "path_to_words", "sequence_report", "train_words"]
 
 
 def _stack_models(ctx, models):
@@ -266,6 +266,14 @@ class IsolatedWordRecognizer:
         return float(np.sum(got == words)) / len(words), got
 
 
+    def online(self, n_streams, frontend=None, endpointer=None):
+        """An `OnlineWordRecognizer` of `n_streams` live utterances sharing this recogniser's packed mixtures and graph
+        (single-Gaussian word models raise `_hip.Unsupported`).  frontend / endpointer: as `ContinuousDecoder.online` -- a
+        `sr.feature.StreamingFrontend` (`push_audio`) and a `sr.audio_capture.StreamingEndpointer` (`push_recording`) of
+        the same context and `n_streams`."""
+        return OnlineWordRecognizer(self, n_streams, frontend, endpointer)
+
+
 def sequence_report(decoded, labels, verbose=False):
     """The tally at the end of the reference's `main.py` (:69-84): an utterance is correct when its decoded word
     string equals the label string; for a wrong one the number of differing positions (np.count_nonzero(matched - l),
@@ -392,7 +400,165 @@ class ContinuousDecoder:
         return OnlineDecoder(self, n_streams, max_frames, window, frontend, endpointer)
 
 
-class OnlineDecoder:
+class _OnlineStreams:
+    """The stream plumbing `OnlineDecoder` and `OnlineWordRecognizer` share: `n_streams` live utterances that take feature
+    frames (`push`, `push_batch`), audio through a `StreamingFrontend` (`push_audio`) or recordings through a
+    `StreamingEndpointer` as well (the gate loop of `push_recording`), with every argument checked on the host first.
+    A subclass provides `self.session` (`push(batch, ids, first, count)`, `reset(ids)`), `_room(ids, counts)` (raises
+    ValueError where the streams cannot take that many frames) and `result`."""
+
+    _what = "decoder"
+
+    def _attach(self, ctx, dtype, gmm, n_streams, frontend, endpointer):
+        what = self._what
+        if frontend is not None:
+            if frontend.ctx is not ctx:
+                raise ValueError("the front-end lives on another context than the %s" % what)
+            if np.dtype(frontend.dtype) != np.dtype(dtype):
+                raise ValueError("the front-end emits %s, the %s takes %s" % (np.dtype(frontend.dtype), what, np.dtype(dtype)))
+            if frontend.D != gmm.D:
+                raise ValueError("the front-end emits %d features, the models take %d" % (frontend.D, gmm.D))
+            if frontend.n_streams != int(n_streams):
+                raise ValueError("the front-end has %d streams, the %s %d" % (frontend.n_streams, what, int(n_streams)))
+        if endpointer is not None:
+            if frontend is None:
+                raise ValueError("an endpointer needs a front-end: online(..., frontend=StreamingFrontend(...), endpointer=...)")
+            if endpointer.ctx is not ctx:
+                raise ValueError("the endpointer lives on another context than the %s" % what)
+            if endpointer.sample_rate != frontend.sample_rate:
+                raise ValueError("the endpointer takes %d Hz, the front-end %d Hz" % (endpointer.sample_rate, frontend.sample_rate))
+            if endpointer.n_streams != int(n_streams):
+                raise ValueError("the endpointer has %d streams, the %s %d" % (endpointer.n_streams, what, int(n_streams)))
+            if frontend.max_chunk < endpointer.max_piece:
+                raise ValueError("the front-end takes chunks of %d samples, the gate can hand out %d ('start boundary' %d + carry %d + "
+                                 "the endpointer's max_chunk %d)" % (frontend.max_chunk, endpointer.max_piece, endpointer.boundary,
+                                                                    endpointer.carry_cap, endpointer.max_chunk))
+            if -(-endpointer.min_utterance // frontend.step) < 2:
+                raise ValueError("the shortest utterance of this endpoint config has %d samples: fewer than 2 frames of %d samples' stride"
+                                 % (endpointer.min_utterance, frontend.step))
+        self._ctx, self._dtype, self._gmm = ctx, dtype, gmm
+        self.frontend = frontend
+        self.endpointer = endpointer
+        self.n_streams = int(n_streams)
+        self._frames = np.zeros(self.n_streams, dtype=np.int64)       # what the session holds, for the checks of a push
+
+    @property
+    def frames(self):
+        """Frames every stream has taken since its last reset: int64 [n_streams]."""
+        return self._frames.copy()
+
+    def _ids(self, ids, distinct=True):
+        a = np.asarray(ids)
+        if a.ndim != 1 or (a.size and a.dtype.kind not in "iu"):
+            raise ValueError("ids must be a one-dimensional sequence of stream indices")
+        a = a.astype(np.int64)
+        if a.size and (a.min() < 0 or a.max() >= self.n_streams):
+            raise ValueError("stream ids must lie in [0, %d)" % self.n_streams)
+        if distinct and len(np.unique(a)) != len(a):
+            raise ValueError("a stream is named twice in one push")
+        return a
+
+    def push(self, ids, chunks):
+        """Stream ids[i] takes the frames chunks[i], a [t_i, D] array (t_i = 0: the stream sits this tick out)."""
+        ids = self._ids(ids)
+        if len(chunks) != len(ids):
+            raise ValueError("%d chunks for %d ids" % (len(chunks), len(ids)))
+        D = self._gmm.D
+        chunks = [np.asarray(c) for c in chunks]
+        for c in chunks:
+            if c.ndim != 2 or c.shape[1] != D:
+                raise ValueError("a chunk must be a [t, %d] array, not one of shape %r" % (D, c.shape))
+        counts = np.array([len(c) for c in chunks], dtype=np.int64)
+        self._room(ids, counts)
+        if not counts.sum():
+            return
+        batch = _hip.Batch(self._ctx, chunks, dtype=self._dtype)
+        try:
+            batch.loglik(self._gmm, fetch=False)
+            self.session.push(batch, ids)
+            self._frames[ids] += counts
+            self._ctx.sync()                              # (the batch's matrix is read until the sweep is done)
+        finally:
+            batch.close()
+
+    def push_batch(self, ids, batch, first=None, count=None):
+        """Stream ids[u] takes the columns [first[u], first[u] + count[u]) of utterance u of a resident `_hip.Batch`
+        (e.g. from `features_from_signals`; first None: 0, count None: to the utterance's end).  A batch without
+        likelihoods gets them here (once); one that holds a likelihood matrix is taken as it is, so that it can be fed
+        piecewise.  The work is only enqueued: keep the batch alive until the context is synchronised (`result` does)."""
+        ids = self._ids(ids)
+        if batch.U != len(ids):
+            raise ValueError("%d utterances for %d ids" % (batch.U, len(ids)))
+        if batch.D != self._gmm.D:
+            raise ValueError("the batch has %d feature dimensions, the model %d" % (batch.D, self._gmm.D))
+        T = np.asarray(batch.lengths, dtype=np.int64)
+        first = np.zeros(len(ids), dtype=np.int64) if first is None else np.asarray(first, dtype=np.int64)
+        count = T - first if count is None else np.asarray(count, dtype=np.int64)
+        if first.shape != T.shape or count.shape != T.shape or np.any(first < 0) or np.any(count < 0) or np.any(first + count > T):
+            raise ValueError("first / count must name column ranges inside the batch's utterances")
+        self._room(ids, count)
+        if not count.sum():
+            return
+        if batch.S is None:
+            batch.loglik(self._gmm, fetch=False)
+        elif batch.S != self._gmm.S:
+            raise ValueError("the batch holds likelihoods of %d states, the model has %d" % (batch.S, self._gmm.S))
+        self.session.push(batch, ids, first, count)
+        self._frames[ids] += count
+
+    def push_audio(self, ids, chunks, end=None):
+        """Stream ids[i] takes the int16 samples chunks[i] through the `StreamingFrontend` (`online(..., frontend=)`) and
+        then the frames those samples made final; end[i] true ends the utterance's audio (its remaining frames come out;
+        `finish` then frees the id).  The frames every stream will receive are computed on the host first: a push that the
+        front-end would refuse, or one the streams have no room for, raises ValueError with nothing moved in either
+        object."""
+        if self.frontend is None:
+            raise ValueError("this %s has no front-end: online(..., frontend=StreamingFrontend(...))" % self._what)
+        ids, chunks, end, counts = self.frontend.plan(ids, chunks, end)
+        self._room(ids, counts)
+        batch = self.frontend._push(ids, chunks, end, counts)
+        try:
+            if counts.sum():
+                self.push_batch(ids, batch)
+                self._ctx.sync()                          # (the batch's matrix is read until the sweep is done)
+        finally:
+            batch.close()
+
+    def _gated(self, ids, chunks, end):
+        """The gate loop of `push_recording`: what the endpointer lets through goes on through `push_audio`; yields, per
+        round of the gate, (the streams of the round, those whose utterance ended with it, their (begin, stop, open))."""
+        if self.endpointer is None:
+            raise ValueError("this %s has no endpointer: online(..., frontend=..., endpointer=StreamingEndpointer(...))" % self._what)
+        for r_ids, pieces, flags, ranges in self.endpointer.gate(ids, chunks, end):
+            try:
+                self.push_audio(r_ids, pieces, flags)
+            except ValueError as e:
+                raise ValueError("streams %s: the %s refused what the endpointer let through (%s); the endpointer has moved: "
+                                 "reset these streams" % (r_ids.tolist(), self._what, e))
+            yield r_ids, r_ids[flags], [rg for rg in ranges if rg is not None]
+
+    def reset(self, ids=None):
+        """The streams `ids` (None: all) start again at frame 0 -- and, with an endpointer, at sample 0 of a new
+        recording."""
+        ids = None if ids is None else self._ids(ids, distinct=False)
+        if self.endpointer is not None:
+            self.endpointer.reset(ids)
+        self._reset_utterance(ids)
+
+    def _reset_utterance(self, ids):
+        self.session.reset(ids)
+        if self.frontend is not None:
+            self.frontend.reset(ids)
+        if ids is None:
+            self._frames[:] = 0
+        else:
+            self._frames[ids] = 0
+
+    def close(self):
+        self.session.close()
+
+
+class OnlineDecoder(_OnlineStreams):
     """Decode while the audio is still arriving: `n_streams` utterances take feature frames chunk by chunk, and
     `result` gives at any time what `ContinuousDecoder.decode_batch` would give for the frames pushed so far -- the same
     words, end costs, chosen ends and paths, without decoding the prefix again (the dynamic program of a stream is
@@ -453,61 +619,17 @@ class OnlineDecoder:
             raise ValueError("exactly one of max_frames and window must be given")
         if int(n_streams) < 1 or int(window if max_frames is None else max_frames) < 1:
             raise ValueError("n_streams and max_frames / window must be positive")
-        if frontend is not None:
-            if frontend.ctx is not decoder.ctx:
-                raise ValueError("the front-end lives on another context than the decoder")
-            if np.dtype(frontend.dtype) != np.dtype(decoder.dtype):
-                raise ValueError("the front-end emits %s, the decoder takes %s" % (np.dtype(frontend.dtype), np.dtype(decoder.dtype)))
-            if frontend.D != decoder.gmm.D:
-                raise ValueError("the front-end emits %d features, the models take %d" % (frontend.D, decoder.gmm.D))
-            if frontend.n_streams != int(n_streams):
-                raise ValueError("the front-end has %d streams, the decoder %d" % (frontend.n_streams, int(n_streams)))
-        if endpointer is not None:
-            if frontend is None:
-                raise ValueError("an endpointer needs a front-end: dec.online(..., frontend=StreamingFrontend(...), endpointer=...)")
-            if endpointer.ctx is not decoder.ctx:
-                raise ValueError("the endpointer lives on another context than the decoder")
-            if endpointer.sample_rate != frontend.sample_rate:
-                raise ValueError("the endpointer takes %d Hz, the front-end %d Hz" % (endpointer.sample_rate, frontend.sample_rate))
-            if endpointer.n_streams != int(n_streams):
-                raise ValueError("the endpointer has %d streams, the decoder %d" % (endpointer.n_streams, int(n_streams)))
-            if frontend.max_chunk < endpointer.max_piece:
-                raise ValueError("the front-end takes chunks of %d samples, the gate can hand out %d ('start boundary' %d + carry %d + "
-                                 "the endpointer's max_chunk %d)" % (frontend.max_chunk, endpointer.max_piece, endpointer.boundary,
-                                                                    endpointer.carry_cap, endpointer.max_chunk))
-            if -(-endpointer.min_utterance // frontend.step) < 2:
-                raise ValueError("the shortest utterance of this endpoint config has %d samples: fewer than 2 frames of %d samples' stride"
-                                 % (endpointer.min_utterance, frontend.step))
-        self.frontend = frontend
-        self.endpointer = endpointer
+        self._attach(decoder.ctx, decoder.dtype, decoder.gmm, n_streams, frontend, endpointer)
         self.decoder = decoder
-        self.n_streams = int(n_streams)
         self.max_frames = None if max_frames is None else int(max_frames)
         self.window = None if window is None else int(window)
         if window is None:
             self.session = _hip.OnlineSession(decoder.ctx, decoder.lat, self.n_streams, self.max_frames)
         else:
             self.session = _hip.OnlineSession(decoder.ctx, decoder.lat, self.n_streams, window=self.window)
-        self._frames = np.zeros(self.n_streams, dtype=np.int64)       # what the session holds, for the checks below
         self._settled = np.zeros(self.n_streams, dtype=np.int64)      # settled frames (anchor column + 1) of every stream
         self._words = [[] for _ in range(self.n_streams)]             # ... and its settled words
         self._row_word = np.where(decoder.row_state >= 0, decoder.row_state // decoder.n, -1).astype(np.int32)
-
-    @property
-    def frames(self):
-        """Frames every stream has taken since its last reset: int64 [n_streams]."""
-        return self._frames.copy()
-
-    def _ids(self, ids, distinct=True):
-        a = np.asarray(ids)
-        if a.ndim != 1 or (a.size and a.dtype.kind not in "iu"):
-            raise ValueError("ids must be a one-dimensional sequence of stream indices")
-        a = a.astype(np.int64)
-        if a.size and (a.min() < 0 or a.max() >= self.n_streams):
-            raise ValueError("stream ids must lie in [0, %d)" % self.n_streams)
-        if distinct and len(np.unique(a)) != len(a):
-            raise ValueError("a stream is named twice in one push")
-        return a
 
     def _room(self, ids, counts):
         if self.window is not None:
@@ -520,72 +642,6 @@ class OnlineDecoder:
         if np.any(over):
             k = int(np.flatnonzero(over)[0])
             raise ValueError("stream %d would hold %d frames, capacity %d" % (ids[k], self._frames[ids[k]] + counts[k], self.max_frames))
-
-    def push(self, ids, chunks):
-        """Stream ids[i] takes the frames chunks[i], a [t_i, D] array (t_i = 0: the stream sits this tick out)."""
-        ids = self._ids(ids)
-        if len(chunks) != len(ids):
-            raise ValueError("%d chunks for %d ids" % (len(chunks), len(ids)))
-        D = self.decoder.gmm.D
-        chunks = [np.asarray(c) for c in chunks]
-        for c in chunks:
-            if c.ndim != 2 or c.shape[1] != D:
-                raise ValueError("a chunk must be a [t, %d] array, not one of shape %r" % (D, c.shape))
-        counts = np.array([len(c) for c in chunks], dtype=np.int64)
-        self._room(ids, counts)
-        if not counts.sum():
-            return
-        batch = _hip.Batch(self.decoder.ctx, chunks, dtype=self.decoder.dtype)
-        try:
-            batch.loglik(self.decoder.gmm, fetch=False)
-            self.session.push(batch, ids)
-            self._frames[ids] += counts
-            self.decoder.ctx.sync()                       # (the batch's matrix is read until the sweep is done)
-        finally:
-            batch.close()
-
-    def push_batch(self, ids, batch, first=None, count=None):
-        """Stream ids[u] takes the columns [first[u], first[u] + count[u]) of utterance u of a resident `_hip.Batch`
-        (e.g. from `features_from_signals`; first None: 0, count None: to the utterance's end).  A batch without
-        likelihoods gets them here (once); one that holds a likelihood matrix is taken as it is, so that it can be fed
-        piecewise.  The work is only enqueued: keep the batch alive until the context is synchronised (`result` does)."""
-        ids = self._ids(ids)
-        if batch.U != len(ids):
-            raise ValueError("%d utterances for %d ids" % (batch.U, len(ids)))
-        if batch.D != self.decoder.gmm.D:
-            raise ValueError("the batch has %d feature dimensions, the model %d" % (batch.D, self.decoder.gmm.D))
-        T = np.asarray(batch.lengths, dtype=np.int64)
-        first = np.zeros(len(ids), dtype=np.int64) if first is None else np.asarray(first, dtype=np.int64)
-        count = T - first if count is None else np.asarray(count, dtype=np.int64)
-        if first.shape != T.shape or count.shape != T.shape or np.any(first < 0) or np.any(count < 0) or np.any(first + count > T):
-            raise ValueError("first / count must name column ranges inside the batch's utterances")
-        self._room(ids, count)
-        if not count.sum():
-            return
-        if batch.S is None:
-            batch.loglik(self.decoder.gmm, fetch=False)
-        elif batch.S != self.decoder.gmm.S:
-            raise ValueError("the batch holds likelihoods of %d states, the model has %d" % (batch.S, self.decoder.gmm.S))
-        self.session.push(batch, ids, first, count)
-        self._frames[ids] += count
-
-    def push_audio(self, ids, chunks, end=None):
-        """Stream ids[i] takes the int16 samples chunks[i] through the decoder's `StreamingFrontend` (`online(...,
-        frontend=)`) and then the frames those samples made final; end[i] true ends the utterance's audio (its remaining
-        frames come out; `finish` then frees the id).  The frames every stream will receive are computed on the host first:
-        a push that the front-end would refuse, or one past `max_frames` / `window`, raises ValueError with nothing moved
-        in either object."""
-        if self.frontend is None:
-            raise ValueError("this decoder has no front-end: dec.online(..., frontend=StreamingFrontend(...))")
-        ids, chunks, end, counts = self.frontend.plan(ids, chunks, end)
-        self._room(ids, counts)
-        batch = self.frontend._push(ids, chunks, end, counts)
-        try:
-            if counts.sum():
-                self.push_batch(ids, batch)
-                self.decoder.ctx.sync()                   # (the batch's matrix is read until the sweep is done)
-        finally:
-            batch.close()
 
     def result(self, ids=None, want_path=False):
         """(word-index lists, dict(end_cost [n, n_end], best_end [n], frames [n][, paths])) of the streams `ids` (None:
@@ -630,42 +686,22 @@ class OnlineDecoder:
         recording ended while speech was open).  A bad argument raises ValueError with nothing moved; a piece that the
         decoder or the front-end refuses raises ValueError AFTER the endpointer has moved: the streams it names must be
         `reset`."""
-        if self.endpointer is None:
-            raise ValueError("this decoder has no endpointer: dec.online(..., frontend=..., endpointer=StreamingEndpointer(...))")
         out = []
-        for r_ids, pieces, flags, ranges in self.endpointer.gate(ids, chunks, end):
-            try:
-                self.push_audio(r_ids, pieces, flags)
-            except ValueError as e:
-                raise ValueError("streams %s: the decoder refused what the endpointer let through (%s); the endpointer has moved: "
-                                 "reset these streams" % (r_ids.tolist(), e))
+        for r_ids, done, ranges in self._gated(ids, chunks, end):
             if self.window is not None:
                 self.commit(r_ids)
-            done = r_ids[flags]
             if len(done):
                 words, _ = self.result(done)
                 self._reset_utterance(done)
-                for k, w, rg in zip(done, words, [rg for rg in ranges if rg is not None]):
+                for k, w, rg in zip(done, words, ranges):
                     out.append(dict(stream=int(k), words=w, begin=int(rg[0]), stop=int(rg[1]), open=bool(rg[2])))
         return out
 
-    def reset(self, ids=None):
-        """The streams `ids` (None: all) start again at frame 0, with nothing settled -- and, with an endpointer, at sample
-        0 of a new recording."""
-        ids = None if ids is None else self._ids(ids, distinct=False)
-        if self.endpointer is not None:
-            self.endpointer.reset(ids)
-        self._reset_utterance(ids)
-
     def _reset_utterance(self, ids):
-        self.session.reset(ids)
-        if self.frontend is not None:
-            self.frontend.reset(ids)
+        super()._reset_utterance(ids)                     # ... and nothing is settled
         if ids is None:
-            self._frames[:] = 0
             self._settled[:] = 0
         else:
-            self._frames[ids] = 0
             self._settled[ids] = 0
         for k in (range(self.n_streams) if ids is None else ids):
             self._words[int(k)] = []
@@ -677,8 +713,85 @@ class OnlineDecoder:
         self._reset_utterance(None if ids is None else self._ids(ids, distinct=False))
         return out
 
-    def close(self):
-        self.session.close()
+
+class OnlineWordRecognizer(_OnlineStreams):
+    """Isolated-word recognition while the audio is still arriving: `n_streams` utterances take feature frames chunk by
+    chunk, and `result` gives at any time what `IsolatedWordRecognizer.recognize` would give for the frames pushed so far,
+    without scoring the prefix again.  The reference's `record` action (cli.py:44-66: record, detect_endpoints, MFCC,
+    `m.evaluate(x)` for every word model, arg-min) as a live path:
+
+        rec = IsolatedWordRecognizer(models)
+        on = rec.online(n_streams=64)
+        on.push([3, 7], [frames_of_3, frames_of_7])          # [t_i, D] arrays, t_i >= 0
+        words, info = on.result([3])                          # running arg-min word of stream 3; info["costs"] [n, W]
+        words, info = on.finish([7])                          # ... of stream 7, whose id is free again
+
+    THE CONTRACT.  For a stream that holds k >= 2 frames, `result` is what `IsolatedWordRecognizer` gives for those k
+    frames as a whole utterance: on the same likelihood matrix the costs are bitwise equal, and the word is their
+    np.argmin (the first of equal minima, core.py:82-87).  For a stream that holds exactly ONE frame, `result` gives
+    column 0 of every longer decode: a word's cost is its first state's emission if that state is also its last, +inf
+    otherwise.  The reference's one-frame special case is NOT reproduced: it is the column wrap of decode.py:109-114,
+    which lets row r read row r-1 of the same column.  Utterances cut by an endpointer always have >= 2 frames.  A stream
+    without frames gives +inf costs and word -1.
+
+    A word chain needs no decision history to report its cost, so a stream is ONE cost column on the device (W x n
+    doubles: 400 B at 10 words x 5 states).  Streams may run for any length: there is no capacity argument, no window and
+    nothing to settle.  Bad arguments (an id twice in one push or out of range, a chunk of another feature dimension, a
+    column range outside its utterance) raise ValueError before the GPU is touched, and no stream moves.
+
+    MODELS.  Mixture recognisers -- one-component mixtures included -- run `batch.loglik` and the carried sweep.  A
+    recogniser of single-Gaussian word models (use_gmm=False: scored by mahalanobis inside the fused kernel, which has no
+    carried form) raises `_hip.Unsupported`.
+
+    AUDIO and RECORDINGS work as in `OnlineDecoder`: with `frontend=` the streams take int16 PCM (`push_audio`), with
+    `endpointer=` as well whole recordings, and `push_recording` returns the utterances that ended with the call as dicts
+    `stream`, `word`, `costs` [W], `begin`, `stop` (recording sample coordinates) and `open`.  With an endpointer `reset`
+    starts a new RECORDING (all three objects), `finish` a new utterance (recogniser and front-end only)."""
+
+    _what = "recogniser"
+
+    def __init__(self, recognizer, n_streams, frontend=None, endpointer=None):
+        if recognizer.single:
+            raise _hip.Unsupported("online word recognition takes mixture word models: single-Gaussian models (use_gmm=False) are "
+                                   "scored inside the fused sweep, which has no carried form")
+        if int(n_streams) < 1:
+            raise ValueError("n_streams must be positive")
+        self._attach(recognizer.ctx, recognizer.dtype, recognizer.gmm, n_streams, frontend, endpointer)
+        self.recognizer = recognizer
+        self.session = _hip.WordStreamSession(recognizer.ctx, recognizer.lat, self.n_streams)
+
+    def _room(self, ids, counts):
+        pass                                              # (a stream holds one column: it takes any number of frames)
+
+    def result(self, ids=None):
+        """(words int64 [n], dict(costs [n, W], frames [n])) of the streams `ids` (None: all) for the frames pushed so far:
+        what `recognize` returns for those frames as whole utterances (a stream without frames: word -1, costs +inf)."""
+        ids = np.arange(self.n_streams, dtype=np.int64) if ids is None else self._ids(ids, distinct=False)
+        r = self.session.result(ids)
+        return np.asarray(r["best"], dtype=np.int64), dict(costs=r["costs"], frames=r["frames"])
+
+    def push_recording(self, ids, chunks, end=None):
+        """Stream ids[i] takes the int16 samples chunks[i] of its RECORDING through the recogniser's `StreamingEndpointer`
+        (`online(..., endpointer=)`); what its gate lets through goes on through `push_audio`, and utterances that ended
+        are finished.  end[i] true ends the recording.  Returns the finished utterances in order: dicts `stream`, `word`,
+        `costs`, `begin`, `stop`, `open` (the recording ended while speech was open).  A bad argument raises ValueError with
+        nothing moved; a piece that the front-end refuses raises ValueError AFTER the endpointer has moved: the streams it
+        names must be `reset`."""
+        out = []
+        for _, done, ranges in self._gated(ids, chunks, end):
+            if len(done):
+                words, info = self.result(done)
+                self._reset_utterance(done)
+                for k, w, c, rg in zip(done, words, info["costs"], ranges):
+                    out.append(dict(stream=int(k), word=int(w), costs=c, begin=int(rg[0]), stop=int(rg[1]), open=bool(rg[2])))
+        return out
+
+    def finish(self, ids):
+        """`result(ids)` followed by a reset of the recogniser's and the front-end's streams: the final scores of
+        utterances that have ended; their ids are free (an endpointer's recording goes on)."""
+        out = self.result(ids)
+        self._reset_utterance(None if ids is None else self._ids(ids, distinct=False))
+        return out
 
 
 class InFlight:
