@@ -359,6 +359,19 @@ int gh_viterbi_labels(gh_ctx* ctx, const gh_lattices* lat, const gh_batch* b,
                       const int32_t* utt_lattice /*[U] or NULL*/, const int32_t* row_label,
                       double* out_end_cost, int32_t* out_best_end,
                       int32_t* out_labels, const int64_t* label_off /*[U+1]*/, int32_t* out_n_labels);
+/* gh_viterbi_labels with WORD BEGIN TIMES: out_begin, laid out exactly like out_labels (utterance u at label_off[u]), takes
+ * one int32 frame index per label.
+ * THE BEGIN RULE (main.py:59-67): walk the path start -> end; a word is a maximal run of cells on emitting rows between
+ * non-emitting rows, its label is the label of the run's first cell, and ITS BEGIN IS THE COLUMN OF THAT FIRST CELL.
+ * Ends are not stored: word k ends where word k + 1 begins and the last word ends at the utterance's frame count (a
+ * non-emitting row shares its column with the cell behind it: the boundary frame goes to the next word only, as in
+ * gh_align_segments).  Labels, end costs and chosen ends are those of gh_viterbi_labels bit for bit.  out_begin == NULL:
+ * no times -- the call IS gh_viterbi_labels and runs its kernels. */
+int gh_viterbi_labels_timed(gh_ctx* ctx, const gh_lattices* lat, const gh_batch* b,
+                            const int32_t* utt_lattice /*[U] or NULL*/, const int32_t* row_label,
+                            double* out_end_cost, int32_t* out_best_end,
+                            int32_t* out_labels, const int64_t* label_off /*[U+1]*/, int32_t* out_n_labels,
+                            int32_t* out_begin /*like out_labels, or NULL*/);
 
 /* A6 + the regrouping step of continuous_train in one call (continuous_speech.py:80-106): the same decode, the path
  * stays on the device and what comes back is, per FRAME of the batch, the state whose training data the frame joins:
@@ -387,6 +400,16 @@ int gh_viterbi_labels_packed(gh_ctx* ctx, const gh_lattices* lat, const gh_batch
                              const int32_t* utt_lattice /*[U] or NULL*/, const int32_t* row_label, int max_labels,
                              double* out_end_cost, int32_t* out_best_end,
                              int32_t* out_labels, int64_t out_capacity, int32_t* out_n_labels);
+/* gh_viterbi_labels_packed with word begin times: out_begin in the PACKED layout of out_labels (utterance u at the sum of
+ * out_n_labels[0..u-1], capacity out_capacity).
+ * THE BEGIN RULE (main.py:59-67): walk the path start -> end; a word is a maximal run of cells on emitting rows between
+ * non-emitting rows, its label is the label of the run's first cell, and ITS BEGIN IS THE COLUMN OF THAT FIRST CELL.
+ * See gh_viterbi_labels_timed for the boundary convention.  out_begin == NULL: gh_viterbi_labels_packed. */
+int gh_viterbi_labels_packed_timed(gh_ctx* ctx, const gh_lattices* lat, const gh_batch* b,
+                                   const int32_t* utt_lattice /*[U] or NULL*/, const int32_t* row_label, int max_labels,
+                                   double* out_end_cost, int32_t* out_best_end,
+                                   int32_t* out_labels, int64_t out_capacity, int32_t* out_n_labels,
+                                   int32_t* out_begin /*like out_labels, or NULL*/);
 
 /* ------------------------------------------------------------------ A5: dtw
  * Template DP of every utterance of an fp64 batch against the n template rows y
@@ -686,6 +709,15 @@ int gh_online_frames(const gh_online* on, int64_t* out /*[n_streams]*/);
 int gh_online_result(gh_ctx* ctx, gh_online* on, int64_t n, const int64_t* ids /*[n] or NULL*/, double* end_cost,
                      int32_t* best_end, const int32_t* row_label, int32_t* labels, const int64_t* label_off /*[n+1]*/,
                      int32_t* n_labels, int32_t* path, const int64_t* path_off /*[n+1]*/, int32_t* path_len);
+/* gh_online_result with word begin times: out_begin laid out like labels (stream ids[i] at label_off[i]); needs labels.
+ * THE BEGIN RULE (main.py:59-67): walk the path start -> end; a word is a maximal run of cells on emitting rows between
+ * non-emitting rows, its label is the label of the run's first cell, and ITS BEGIN IS THE COLUMN OF THAT FIRST CELL.
+ * Begins are columns of the stream since its last reset: what gh_viterbi_labels_timed returns for the same frames.
+ * out_begin == NULL: gh_online_result. */
+int gh_online_result_timed(gh_ctx* ctx, gh_online* on, int64_t n, const int64_t* ids /*[n] or NULL*/, double* end_cost,
+                           int32_t* best_end, const int32_t* row_label, int32_t* labels, const int64_t* label_off /*[n+1]*/,
+                           int32_t* n_labels, int32_t* path, const int64_t* path_off /*[n+1]*/, int32_t* path_len,
+                           int32_t* out_begin /*like labels, or NULL*/);
 
 /* ------------------------------------------------ online decode: the settled prefix and a bounded history
  * Trace back from EVERY cell of a stream's newest column that is alive (finite carried cost).  Where all those traces
@@ -720,6 +752,20 @@ int gh_online_commit(gh_ctx* ctx, gh_online* on, int64_t n, const int64_t* ids /
  * Any output may be NULL.  Synchronises. */
 int gh_online_tail(gh_ctx* ctx, gh_online* on, int64_t n, const int64_t* ids /*[n] or NULL*/, double* end_cost, int32_t* best_end,
                    const int32_t* row_label, int32_t* labels, const int64_t* label_off /*[n+1]*/, int32_t* n_labels);
+/* gh_online_commit / gh_online_tail with word begin times: out_begin laid out like labels; needs labels.
+ * THE BEGIN RULE (main.py:59-67): walk the path start -> end; a word is a maximal run of cells on emitting rows between
+ * non-emitting rows, its label is the label of the run's first cell, and ITS BEGIN IS THE COLUMN OF THAT FIRST CELL.
+ * Begins are ABSOLUTE columns of the stream since its last reset, also on a session with a window whose ring has wrapped
+ * any number of times.  A commit gives a settled word's begin at once; its end -- the next word's begin -- becomes known
+ * when the next word settles.  The run the old anchor lies in was reported by the commit that settled it: its pending label
+ * is dropped and its begin with it.  The begins of all commits followed by the tail's are the gh_online_result_timed begins.
+ * out_begin == NULL: gh_online_commit / gh_online_tail. */
+int gh_online_commit_timed(gh_ctx* ctx, gh_online* on, int64_t n, const int64_t* ids /*[n] or NULL*/, int64_t* settled_frames /*[n]*/,
+                           const int32_t* row_label, int32_t* labels, const int64_t* label_off /*[n+1]*/, int32_t* n_new_labels,
+                           int32_t* out_begin /*like labels, or NULL*/);
+int gh_online_tail_timed(gh_ctx* ctx, gh_online* on, int64_t n, const int64_t* ids /*[n] or NULL*/, double* end_cost, int32_t* best_end,
+                         const int32_t* row_label, int32_t* labels, const int64_t* label_off /*[n+1]*/, int32_t* n_labels,
+                         int32_t* out_begin /*like labels, or NULL*/);
 
 /* ------------------------------------------------ online isolated-word recognition: A5 while the audio is still arriving
  * HMM.evaluate (hmm.py:126-135) of every word model, carried across the chunks of n_streams live utterances: the cost of a

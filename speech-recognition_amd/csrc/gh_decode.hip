@@ -12,13 +12,16 @@ namespace {
 
 // A12 on the device: one wave per utterance walks its path (stored end -> start) in start -> end order, 64
 // cells at a time; a cell opens a run when its row is emitting and the cell before it is not (or it is the
-// first); the run's label is written at the position given by a ballot prefix count.
-__global__ __launch_bounds__(64) void path_labels_kernel(const int32_t* __restrict__ path, const int64_t* __restrict__ path_off,
-                                                         const int32_t* __restrict__ path_len, const int32_t* __restrict__ utt_lat,
-                                                         const gh_lattices::desc* __restrict__ descs,
-                                                         const int32_t* __restrict__ row_label,
-                                                         const int64_t* __restrict__ label_off, int32_t* __restrict__ labels,
-                                                         int32_t* __restrict__ n_labels, int* __restrict__ flag) {
+// first); the run's label is written at the position given by a ballot prefix count.  TIMED: the column of that opening
+// cell -- the word's begin frame -- goes to the same position of `begins`, read next to the row the walk reads anyway.
+template <bool TIMED>
+__device__ __forceinline__ void path_labels_walk(const int32_t* __restrict__ path, const int64_t* __restrict__ path_off,
+                                                 const int32_t* __restrict__ path_len, const int32_t* __restrict__ utt_lat,
+                                                 const gh_lattices::desc* __restrict__ descs,
+                                                 const int32_t* __restrict__ row_label,
+                                                 const int64_t* __restrict__ label_off, int32_t* __restrict__ labels,
+                                                 int32_t* __restrict__ n_labels, int* __restrict__ flag,
+                                                 int32_t* __restrict__ begins) {
     const int64_t u = blockIdx.x;
     const int lane = threadIdx.x;
     const int len = path_len[u];
@@ -26,23 +29,47 @@ __global__ __launch_bounds__(64) void path_labels_kernel(const int32_t* __restri
     const int32_t* lab = row_label + descs[utt_lat ? utt_lat[u] : 0].row_base;
     const int64_t cap = label_off[u + 1] - label_off[u];
     int32_t* out = labels + label_off[u];
+    int32_t* outb = TIMED ? begins + label_off[u] : nullptr;
     int count = 0, carry = -1;  // label of the cell before this chunk (-1: start / non-emitting)
     for (int base = 0; base < len; base += 64) {
         const int i = base + lane;
         const int l = (i < len) ? lab[p[2 * (int64_t)(len - 1 - i)]] : -1;
+        const int col = (TIMED && i < len) ? p[2 * (int64_t)(len - 1 - i) + 1] : 0;
         int prev = __shfl_up(l, 1);
         if (lane == 0) prev = carry;
         const bool open = l >= 0 && prev < 0;
         const unsigned long long m = __ballot(open);
         const int pos = count + __popcll(m & ((1ull << lane) - 1));
         if (open) {
-            if (pos < cap) out[pos] = l;
+            if (pos < cap) {
+                out[pos] = l;
+                if (TIMED) outb[pos] = col;
+            }
             else atomicOr(flag, 8);
         }
         count += __popcll(m);
         carry = __shfl(l, 63);
     }
     if (lane == 0) n_labels[u] = count;
+}
+
+// (the untimed walk keeps its name and its machine code; the timed one is a kernel of its own)
+__global__ __launch_bounds__(64) void path_labels_kernel(const int32_t* __restrict__ path, const int64_t* __restrict__ path_off,
+                                                         const int32_t* __restrict__ path_len, const int32_t* __restrict__ utt_lat,
+                                                         const gh_lattices::desc* __restrict__ descs,
+                                                         const int32_t* __restrict__ row_label,
+                                                         const int64_t* __restrict__ label_off, int32_t* __restrict__ labels,
+                                                         int32_t* __restrict__ n_labels, int* __restrict__ flag) {
+    path_labels_walk<false>(path, path_off, path_len, utt_lat, descs, row_label, label_off, labels, n_labels, flag, nullptr);
+}
+__global__ __launch_bounds__(64) void path_labels_timed_kernel(const int32_t* __restrict__ path, const int64_t* __restrict__ path_off,
+                                                               const int32_t* __restrict__ path_len, const int32_t* __restrict__ utt_lat,
+                                                               const gh_lattices::desc* __restrict__ descs,
+                                                               const int32_t* __restrict__ row_label,
+                                                               const int64_t* __restrict__ label_off, int32_t* __restrict__ labels,
+                                                               int32_t* __restrict__ n_labels, int* __restrict__ flag,
+                                                               int32_t* __restrict__ begins) {
+    path_labels_walk<true>(path, path_off, path_len, utt_lat, descs, row_label, label_off, labels, n_labels, flag, begins);
 }
 
 // The regrouping step of continuous_train (continuous_speech.py:90-106) on the device-resident path, one lane per
@@ -129,7 +156,8 @@ static int viterbi_impl(gh_ctx* ctx, const gh_lattices* lat, const gh_batch* b, 
                         const int64_t* costs_off, const int32_t* row_label, int32_t* out_labels,
                         const int64_t* label_off, int32_t* out_n_labels, int64_t packed_cap = -1,
                         int32_t* out_frame_state = nullptr, const gh_gmm* fused = nullptr, int fused_log_domain = 0,
-                        int run_cap = 0, int32_t* out_runs = nullptr, int32_t* out_run_cnt = nullptr) {
+                        int run_cap = 0, int32_t* out_runs = nullptr, int32_t* out_run_cnt = nullptr,
+                        int32_t* out_begin = nullptr) {
     GH_REQUIRE(ctx && lat && b, "gh_viterbi: NULL argument");
     GH_REQUIRE(fused || b->nll || b->N == 0, "gh_viterbi: gh_loglik has not been run on this batch");
     GH_REQUIRE(!out_path || (path_off && out_path_len), "gh_viterbi: out_path needs path_off and out_path_len");
@@ -164,6 +192,7 @@ static int viterbi_impl(gh_ctx* ctx, const gh_lattices* lat, const gh_batch* b, 
         }
     }
     const bool want_labels = out_labels != nullptr;
+    const bool want_begin = want_labels && out_begin != nullptr;   // timed labels: MODE 2 / the timed path walk
     const bool want_runs = out_runs != nullptr && out_run_cnt != nullptr && run_cap > 0;
     const bool want_segments = out_frame_state != nullptr || want_runs;
     const bool uniform = utt_lattice == nullptr;
@@ -289,7 +318,7 @@ static int viterbi_impl(gh_ctx* ctx, const gh_lattices* lat, const gh_batch* b, 
     const int fused_rp = (lat->max_R + 63) & ~63;
     int32_t *d_rowlabel = nullptr, *d_labels = nullptr, *d_nlabels = nullptr;
     int64_t *d_labeloff = nullptr, *d_poff = nullptr;
-    int32_t* d_packed = nullptr;
+    int32_t *d_packed = nullptr, *d_begins = nullptr, *d_pbegins = nullptr;
     int64_t n_rows_total = 0;
     for (auto& lh : lat->lat) n_rows_total = std::max<int64_t>(n_rows_total, lh.row_base + lh.R);
     auto carve = [&]() -> int {
@@ -311,6 +340,10 @@ static int viterbi_impl(gh_ctx* ctx, const gh_lattices* lat, const gh_batch* b, 
             cv.add(&d_rowlabel, n_rows_total); cv.add(&d_labeloff, U + 1);
             cv.add(&d_nlabels, U); cv.add(&d_labels, label_off[U]);   // [n_labels | labels] back to back: one copy
             if (packed_cap >= 0) { cv.add(&d_poff, U + 1); cv.add(&d_packed, label_off[U]); }
+            if (want_begin) {
+                cv.add(&d_begins, label_off[U]);
+                if (packed_cap >= 0) cv.add(&d_pbegins, label_off[U]);
+            }
         }
         return cv.commit(ctx);
     };
@@ -394,11 +427,11 @@ static int viterbi_impl(gh_ctx* ctx, const gh_lattices* lat, const gh_batch* b, 
         c.nll = b->nll; c.utt_off = b->d_offsets; c.perm = b->d_perm; c.bp = d_bp; c.bp_off = d_bpoff;
         c.end_cost = d_endcost; c.best_end = d_bestend; c.path = d_path; c.path_off = d_pathoff; c.path_len = d_pathlen;
         c.flag = d_flag2;
-        if (labels_direct) { c.row_label = d_rowlabel; c.labels = d_labels; c.label_off = d_labeloff; c.n_labels = d_nlabels; }
+        if (labels_direct) { c.row_label = d_rowlabel; c.labels = d_labels; c.label_off = d_labeloff; c.n_labels = d_nlabels; if (want_begin) c.path = d_begins; }
         for (size_t k = 0; k + 1 < chunk_begin.size(); ++k) {
             rc = gh_launch_viterbi_layers(ctx, c, lat->h_layers, chunk_begin[k], chunk_begin[k + 1] - chunk_begin[k],
                                           b->dtype == GH_F64, want_path);
-            if (!rc && want_path) rc = gh_launch_lattice_backtrace(ctx, c, lat->h_layers, chunk_begin[k], chunk_begin[k + 1] - chunk_begin[k]);
+            if (!rc && want_path) rc = gh_launch_lattice_backtrace(ctx, c, lat->h_layers, chunk_begin[k], chunk_begin[k + 1] - chunk_begin[k], labels_direct && want_begin);
             if (rc) return rc;
         }
     }
@@ -409,11 +442,11 @@ static int viterbi_impl(gh_ctx* ctx, const gh_lattices* lat, const gh_batch* b, 
         c.nll = b->nll; c.utt_off = b->d_offsets; c.perm = b->d_perm; c.bp = d_bp; c.bp_off = d_bpoff;
         c.end_cost = d_endcost; c.best_end = d_bestend; c.path = d_path; c.path_off = d_pathoff; c.path_len = d_pathlen;
         c.flag = d_flag2;
-        if (labels_direct) { c.row_label = d_rowlabel; c.labels = d_labels; c.label_off = d_labeloff; c.n_labels = d_nlabels; }
+        if (labels_direct) { c.row_label = d_rowlabel; c.labels = d_labels; c.label_off = d_labeloff; c.n_labels = d_nlabels; if (want_begin) c.path = d_begins; }
         for (size_t k = 0; k + 1 < chunk_begin.size(); ++k) {
             const int64_t u0 = chunk_begin[k], nu = chunk_begin[k + 1] - u0;
             rc = gh_launch_viterbi_bigram(ctx, c, lat->h_layers, u0, nu, b->dtype == GH_F64, want_path);
-            if (!rc && want_path) rc = gh_launch_bigram_backtrace(ctx, c, lat->h_layers, u0, nu);
+            if (!rc && want_path) rc = gh_launch_bigram_backtrace(ctx, c, lat->h_layers, u0, nu, labels_direct && want_begin);
             if (rc) return rc;
         }
         use_layers = true;   // (from here on: "a lattice kernel has run", the row-per-lane kernels are skipped)
@@ -506,8 +539,12 @@ static int viterbi_impl(gh_ctx* ctx, const gh_lattices* lat, const gh_batch* b, 
     if (rc) return rc;
     if (want_labels) {
         if (!labels_direct) {
-            hipLaunchKernelGGL(path_labels_kernel, dim3((unsigned)U), dim3(64), 0, st, d_path, d_pathoff, d_pathlen, d_uttlat,
-                               lat->d_desc, d_rowlabel, d_labeloff, d_labels, d_nlabels, d_flag2);
+            if (want_begin)
+                hipLaunchKernelGGL(path_labels_timed_kernel, dim3((unsigned)U), dim3(64), 0, st, d_path, d_pathoff, d_pathlen, d_uttlat,
+                                   lat->d_desc, d_rowlabel, d_labeloff, d_labels, d_nlabels, d_flag2, d_begins);
+            else
+                hipLaunchKernelGGL(path_labels_kernel, dim3((unsigned)U), dim3(64), 0, st, d_path, d_pathoff, d_pathlen, d_uttlat,
+                                   lat->d_desc, d_rowlabel, d_labeloff, d_labels, d_nlabels, d_flag2);
             GH_HIP(hipGetLastError());
         }
         GH_HIP(hipMemcpyAsync(out_n_labels, d_nlabels, U * 4, hipMemcpyDeviceToHost, st));
@@ -524,8 +561,17 @@ static int viterbi_impl(gh_ctx* ctx, const gh_lattices* lat, const gh_batch* b, 
                                d_poff, d_packed, U);
             GH_HIP(hipGetLastError());
             if (poff[U] > 0) GH_HIP(hipMemcpyAsync(out_labels, d_packed, (size_t)poff[U] * 4, hipMemcpyDeviceToHost, st));
+            if (want_begin) {   // the begins take the labels' way, slot -> packed, with the same counts and offsets
+                hipLaunchKernelGGL(pack_labels_kernel, dim3((unsigned)((U + 255) / 256)), dim3(256), 0, st, d_begins, d_labeloff, d_nlabels,
+                                   d_poff, d_pbegins, U);
+                GH_HIP(hipGetLastError());
+                if (poff[U] > 0) GH_HIP(hipMemcpyAsync(out_begin, d_pbegins, (size_t)poff[U] * 4, hipMemcpyDeviceToHost, st));
+            }
             GH_HIP(hipStreamSynchronize(st));   // (poff is a host vector of this scope)
-        } else if (label_off[U] > 0) GH_HIP(hipMemcpyAsync(out_labels, d_labels, label_off[U] * 4, hipMemcpyDeviceToHost, st));
+        } else if (label_off[U] > 0) {
+            GH_HIP(hipMemcpyAsync(out_labels, d_labels, label_off[U] * 4, hipMemcpyDeviceToHost, st));
+            if (want_begin) GH_HIP(hipMemcpyAsync(out_begin, d_begins, label_off[U] * 4, hipMemcpyDeviceToHost, st));
+        }
     }
     if (want_segments && b->N > 0) {
         if (d_framestate) GH_HIP(hipMemsetAsync(d_framestate, 0xFF, (size_t)b->N * 4, st));
@@ -604,12 +650,19 @@ extern "C" int gh_viterbi_fused(gh_ctx* ctx, const gh_gmm* g, const gh_lattices*
 
 extern "C" int gh_ctx_last_fused(const gh_ctx* ctx) { return ctx ? ctx->last_fused : -1; }
 
+extern "C" int gh_viterbi_labels_timed(gh_ctx* ctx, const gh_lattices* lat, const gh_batch* b, const int32_t* utt_lattice,
+                                       const int32_t* row_label, double* out_end_cost, int32_t* out_best_end,
+                                       int32_t* out_labels, const int64_t* label_off, int32_t* out_n_labels, int32_t* out_begin) {
+    GH_REQUIRE(row_label && out_labels && label_off && out_n_labels, "gh_viterbi_labels: NULL argument");
+    return viterbi_impl(ctx, lat, b, utt_lattice, out_end_cost, out_best_end, nullptr, nullptr, nullptr, nullptr, nullptr,
+                        row_label, out_labels, label_off, out_n_labels, -1, nullptr, nullptr, 0, 0, nullptr, nullptr, out_begin);
+}
+
 extern "C" int gh_viterbi_labels(gh_ctx* ctx, const gh_lattices* lat, const gh_batch* b, const int32_t* utt_lattice,
                                  const int32_t* row_label, double* out_end_cost, int32_t* out_best_end,
                                  int32_t* out_labels, const int64_t* label_off, int32_t* out_n_labels) {
-    GH_REQUIRE(row_label && out_labels && label_off && out_n_labels, "gh_viterbi_labels: NULL argument");
-    return viterbi_impl(ctx, lat, b, utt_lattice, out_end_cost, out_best_end, nullptr, nullptr, nullptr, nullptr, nullptr,
-                        row_label, out_labels, label_off, out_n_labels);
+    return gh_viterbi_labels_timed(ctx, lat, b, utt_lattice, row_label, out_end_cost, out_best_end, out_labels, label_off, out_n_labels,
+                                   nullptr);
 }
 
 // ---------------------------------------------------------------------- dtw
@@ -969,13 +1022,20 @@ extern "C" int gh_align_runs(gh_ctx* ctx, const gh_lattices* lat, const gh_batch
                         nullptr, nullptr, nullptr, nullptr, -1, nullptr, nullptr, 0, run_cap, out_runs, out_run_cnt);
 }
 
-extern "C" int gh_viterbi_labels_packed(gh_ctx* ctx, const gh_lattices* lat, const gh_batch* b, const int32_t* utt_lattice,
-                                        const int32_t* row_label, int max_labels, double* out_end_cost, int32_t* out_best_end,
-                                        int32_t* out_labels, int64_t out_capacity, int32_t* out_n_labels) {
+extern "C" int gh_viterbi_labels_packed_timed(gh_ctx* ctx, const gh_lattices* lat, const gh_batch* b, const int32_t* utt_lattice,
+                                              const int32_t* row_label, int max_labels, double* out_end_cost, int32_t* out_best_end,
+                                              int32_t* out_labels, int64_t out_capacity, int32_t* out_n_labels, int32_t* out_begin) {
     GH_REQUIRE(ctx && lat && b && row_label && out_labels && out_n_labels, "gh_viterbi_labels_packed: NULL argument");
     GH_REQUIRE(max_labels > 0 && out_capacity >= 0, "gh_viterbi_labels_packed: max_labels=%d", max_labels);
     std::vector<int64_t> off((size_t)b->U + 1);
     for (int64_t u = 0; u <= b->U; ++u) off[u] = u * (int64_t)max_labels;
     return viterbi_impl(ctx, lat, b, utt_lattice, out_end_cost, out_best_end, nullptr, nullptr, nullptr, nullptr, nullptr,
-                        row_label, out_labels, off.data(), out_n_labels, out_capacity);
+                        row_label, out_labels, off.data(), out_n_labels, out_capacity, nullptr, nullptr, 0, 0, nullptr, nullptr, out_begin);
+}
+
+extern "C" int gh_viterbi_labels_packed(gh_ctx* ctx, const gh_lattices* lat, const gh_batch* b, const int32_t* utt_lattice,
+                                        const int32_t* row_label, int max_labels, double* out_end_cost, int32_t* out_best_end,
+                                        int32_t* out_labels, int64_t out_capacity, int32_t* out_n_labels) {
+    return gh_viterbi_labels_packed_timed(ctx, lat, b, utt_lattice, row_label, max_labels, out_end_cost, out_best_end, out_labels,
+                                          out_capacity, out_n_labels, nullptr);
 }

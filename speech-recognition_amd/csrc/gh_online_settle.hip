@@ -47,6 +47,7 @@ struct gh_settle_args {
     int32_t* n_labels;
     int64_t* settled_frames;       // [n] (commit)
     int* flag;
+    int32_t* begins;               // timed twins: the begin column of every label, laid out like `labels` (appended: no older field moves)
 };
 
 namespace {
@@ -148,8 +149,10 @@ __global__ __launch_bounds__(64) void online_settle_kernel(gh_settle_args a) {
 // One path, lane = stream.  Commit mode (a.cand): from the new anchor (visited) down to the old one; tail mode: from the
 // chosen end of the newest column (not visited, as in the one-shot back-trace) down to the anchor.  Without an anchor the
 // walk ends in column 0 like the one-shot back-trace.  Labels: MODE 1 of lattice_backtrace_kernel; the run of labelled rows
-// the anchor lies in belongs to the settled side, so the label pending on arrival is dropped.
-template <int N, bool SKIP>
+// the anchor lies in belongs to the settled side, so the label pending on arrival is dropped.  TIMED (MODE 2 of that kernel):
+// every label also stores the column of the cell visited last -- the first cell of the word's run (main.py:59-67), an
+// absolute column of the stream whatever the ring has overwritten -- and the pending column is dropped with the pending label.
+template <int N, bool SKIP, bool TIMED>
 __global__ __launch_bounds__(64) void online_segment_kernel(gh_settle_args a) {
     constexpr int HB = gh_loop_hb(N, SKIP), CPW = gh_loop_cpw(N, SKIP);
     constexpr uint32_t HBM = (uint32_t)((1ull << HB) - 1ull);
@@ -187,6 +190,8 @@ __global__ __launch_bounds__(64) void online_segment_kernel(gh_settle_args a) {
     const int lo = stop.col >= 0 ? stop.col : 0;
     const uint32_t* bpu = reinterpret_cast<const uint32_t*>(a.hist + (int64_t)tk.stream * a.hist_stride);
     int32_t* labs = a.labels + a.label_off[i];
+    int32_t* begs = TIMED ? a.begins + a.label_off[i] : nullptr;
+    int prev_col = 0;                                           // TIMED: column of the cell visited last
     const int64_t cap = a.label_off[i + 1] - a.label_off[i];
     const int ring = a.ring_words;
     int64_t len = 0;
@@ -194,16 +199,18 @@ __global__ __launch_bounds__(64) void online_segment_kernel(gh_settle_args a) {
     int hwi = -1, hwr = 0;                                      // word index whose ring position is held
     int64_t key = -1;
     uint32_t cw = 0;
-    auto visit = [&](int row) {
+    auto visit = [&](int row, int col) {
         const int l = a.row_label[row];
         if (prev_label >= 0 && l < 0) {
             if (len >= cap) { flag |= 8; return; }
             labs[cap - 1 - len] = prev_label;
+            if (TIMED) begs[cap - 1 - len] = prev_col;
             ++len;
         }
         prev_label = l;
+        if (TIMED) prev_col = col;
     };
-    if (commit) visit(row_of(bw, bs));
+    if (commit) visit(row_of(bw, bs), j);
     while (j > lo && !flag) {
         const int wi = j / CPW;
         const int shift = (CPW - 1 - j % CPW) * HB;
@@ -227,13 +234,13 @@ __global__ __launch_bounds__(64) void online_segment_kernel(gh_settle_args a) {
                 if (code < 0) { flag |= 2; break; }
                 bs -= code;
                 --j;
-                visit(row_of(bw, bs));
+                visit(row_of(bw, bs), j);
             } else {
                 const int b_l = (hb >> 1) & 1, b_s = hb & 1;
                 int pick = b_s ? 0 : (b_l ? 3 : 4);
                 if (!((arcs >> pick) & 1)) pick = (arcs & 16) ? 4 : (arcs & 8) ? 3 : (arcs & 1) ? 0 : -1;
-                if (pick == 0) { --j; visit(row_of(bw, 0)); }
-                else if (pick == 3) { kind = 1; visit(Lr); }
+                if (pick == 0) { --j; visit(row_of(bw, 0), j); }
+                else if (pick == 3) { kind = 1; visit(Lr, j); }
                 else { flag |= 2; break; }                      // no origin, or the start row in a column > 0
             }
         } else {
@@ -251,7 +258,7 @@ __global__ __launch_bounds__(64) void online_segment_kernel(gh_settle_args a) {
             bw = found;
             bs = N - 1;
             kind = 0;
-            visit(row_of(bw, bs));
+            visit(row_of(bw, bs), j);
         }
     }
     if (!flag && stop.col >= 0) {
@@ -261,9 +268,15 @@ __global__ __launch_bounds__(64) void online_segment_kernel(gh_settle_args a) {
     if (flag) atomicOr(a.flag, flag);
     if (!flag && prev_label >= 0) {
         if (len >= cap) atomicOr(a.flag, 8);
-        else { labs[cap - 1 - len] = prev_label; ++len; }
+        else {
+            labs[cap - 1 - len] = prev_label;
+            if (TIMED) begs[cap - 1 - len] = prev_col;
+            ++len;
+        }
     }
     for (int64_t k = 0; k < len; ++k) labs[k] = labs[cap - len + k];
+    if (TIMED)
+        for (int64_t k = 0; k < len; ++k) begs[k] = begs[cap - len + k];
     a.n_labels[i] = (int32_t)len;
 }
 
@@ -273,7 +286,8 @@ int launch_settle(gh_ctx* ctx, const gh_settle_args& a, const gh_layerform& f, b
 #define GH_ST(ET, NN, SK)                                                                                    \
     do {                                                                                                     \
         if (settle) hipLaunchKernelGGL((online_settle_kernel<NN, SK>), grid, blk, 0, ctx->stream, a);        \
-        else hipLaunchKernelGGL((online_segment_kernel<NN, SK>), grid, blk, 0, ctx->stream, a);              \
+        else if (a.begins) hipLaunchKernelGGL((online_segment_kernel<NN, SK, true>), grid, blk, 0, ctx->stream, a); \
+        else hipLaunchKernelGGL((online_segment_kernel<NN, SK, false>), grid, blk, 0, ctx->stream, a);       \
     } while (0)
     GH_NSKIP_SWITCH(f.N, f.skip, 16, GH_ST, , "%s: loop form with %d states per word", who, f.N)
 #undef GH_ST
@@ -306,9 +320,11 @@ int tasks_of(gh_online* on, const char* who, int64_t& n, const int64_t* ids, boo
 }  // namespace
 
 // --------------------------------------------------------------------------------------------------------------- C ABI
-extern "C" int gh_online_commit(gh_ctx* ctx, gh_online* on, int64_t n, const int64_t* ids, int64_t* settled_frames,
-                                const int32_t* row_label, int32_t* labels, const int64_t* label_off, int32_t* n_new_labels) {
+extern "C" int gh_online_commit_timed(gh_ctx* ctx, gh_online* on, int64_t n, const int64_t* ids, int64_t* settled_frames,
+                                      const int32_t* row_label, int32_t* labels, const int64_t* label_off, int32_t* n_new_labels,
+                                      int32_t* out_begin) {
     GH_REQUIRE(ctx && on, "gh_online_commit: NULL argument");
+    GH_REQUIRE(!out_begin || labels, "gh_online_commit_timed: out_begin needs labels");
     GH_REQUIRE(ctx == on->ctx, "gh_online_commit: the session belongs to another context");
     GH_REQUIRE(!labels || (row_label && label_off && n_new_labels), "gh_online_commit: labels need row_label, label_off and n_new_labels");
     std::vector<gh_settle_task> tasks;
@@ -323,10 +339,11 @@ extern "C" int gh_online_commit(gh_ctx* ctx, gh_online* on, int64_t n, const int
     gh_settle_task* d_tasks;
     gh_online_anchor* d_cand;
     int64_t *d_settled, *d_labeloff = nullptr;
-    int32_t *d_rowlabel = nullptr, *d_nlabels = nullptr, *d_labels = nullptr;
+    int32_t *d_rowlabel = nullptr, *d_nlabels = nullptr, *d_labels = nullptr, *d_begins = nullptr;
     Carver cv;
     cv.add(&d_flag, 64); cv.add(&d_tasks, (size_t)n); cv.add(&d_cand, (size_t)n); cv.add(&d_settled, (size_t)n);
     if (labels) { cv.add(&d_rowlabel, (size_t)R); cv.add(&d_labeloff, (size_t)n + 1); cv.add(&d_nlabels, (size_t)n); cv.add(&d_labels, (size_t)label_off[n] + 1); }
+    if (out_begin) cv.add(&d_begins, (size_t)label_off[n] + 1);
     rc = cv.commit(ctx);
     if (rc) return rc;
     hipStream_t st = ctx->stream;
@@ -341,7 +358,7 @@ extern "C" int gh_online_commit(gh_ctx* ctx, gh_online* on, int64_t n, const int
     a.lf = lat->d_layers; a.end_rows = lat->d_end_rows; a.tasks = d_tasks; a.n = n; a.prev = on->d_prev; a.hist = on->d_hist;
     a.hist_stride = on->hist_stride; a.ring_words = on->ring_words; a.anchor = on->d_anchor; a.cand = d_cand;
     a.row_label = d_rowlabel; a.labels = d_labels; a.label_off = d_labeloff; a.n_labels = d_nlabels; a.settled_frames = d_settled;
-    a.flag = d_flag;
+    a.flag = d_flag; a.begins = d_begins;
     rc = launch_settle(ctx, a, f, true, "gh_online_commit");
     if (rc) return rc;
     rc = launch_settle(ctx, a, f, false, "gh_online_commit");
@@ -353,6 +370,7 @@ extern "C" int gh_online_commit(gh_ctx* ctx, gh_online* on, int64_t n, const int
     if (labels) {
         GH_HIP(hipMemcpyAsync(n_new_labels, d_nlabels, (size_t)n * 4, hipMemcpyDeviceToHost, st));
         if (label_off[n] > 0) GH_HIP(hipMemcpyAsync(labels, d_labels, (size_t)label_off[n] * 4, hipMemcpyDeviceToHost, st));
+        if (out_begin && label_off[n] > 0) GH_HIP(hipMemcpyAsync(out_begin, d_begins, (size_t)label_off[n] * 4, hipMemcpyDeviceToHost, st));
     }
     GH_HIP(hipStreamSynchronize(st));
     // (the anchors on the device have moved whatever the flag says: the mirror follows them)
@@ -369,9 +387,16 @@ extern "C" int gh_online_commit(gh_ctx* ctx, gh_online* on, int64_t n, const int
     return GH_OK;
 }
 
-extern "C" int gh_online_tail(gh_ctx* ctx, gh_online* on, int64_t n, const int64_t* ids, double* end_cost, int32_t* best_end,
-                              const int32_t* row_label, int32_t* labels, const int64_t* label_off, int32_t* n_labels) {
+extern "C" int gh_online_commit(gh_ctx* ctx, gh_online* on, int64_t n, const int64_t* ids, int64_t* settled_frames,
+                                const int32_t* row_label, int32_t* labels, const int64_t* label_off, int32_t* n_new_labels) {
+    return gh_online_commit_timed(ctx, on, n, ids, settled_frames, row_label, labels, label_off, n_new_labels, nullptr);
+}
+
+extern "C" int gh_online_tail_timed(gh_ctx* ctx, gh_online* on, int64_t n, const int64_t* ids, double* end_cost, int32_t* best_end,
+                                    const int32_t* row_label, int32_t* labels, const int64_t* label_off, int32_t* n_labels,
+                                    int32_t* out_begin) {
     GH_REQUIRE(ctx && on, "gh_online_tail: NULL argument");
+    GH_REQUIRE(!out_begin || labels, "gh_online_tail_timed: out_begin needs labels");
     GH_REQUIRE(ctx == on->ctx, "gh_online_tail: the session belongs to another context");
     GH_REQUIRE(!labels || (row_label && label_off && n_labels), "gh_online_tail: labels need row_label, label_off and n_labels");
     std::vector<gh_settle_task> tasks;
@@ -391,11 +416,12 @@ extern "C" int gh_online_tail(gh_ctx* ctx, gh_online* on, int64_t n, const int64
     gh_settle_task* d_tasks;
     double* d_endcost;
     int64_t *d_ids, *d_uttoff, *d_labeloff = nullptr;
-    int32_t *d_best, *d_rowlabel = nullptr, *d_nlabels = nullptr, *d_labels = nullptr;
+    int32_t *d_best, *d_rowlabel = nullptr, *d_nlabels = nullptr, *d_labels = nullptr, *d_begins = nullptr;
     Carver cv;
     cv.add(&d_flag, 64); cv.add(&d_tasks, (size_t)n); cv.add(&d_best, (size_t)n); cv.add(&d_endcost, (size_t)n * n_end);
     cv.add(&d_ids, (size_t)n); cv.add(&d_uttoff, (size_t)n + 1);
     if (labels) { cv.add(&d_rowlabel, (size_t)R); cv.add(&d_labeloff, (size_t)n + 1); cv.add(&d_nlabels, (size_t)n); cv.add(&d_labels, (size_t)label_off[n] + 1); }
+    if (out_begin) cv.add(&d_begins, (size_t)label_off[n] + 1);
     rc = cv.commit(ctx);
     if (rc) return rc;
     hipStream_t st = ctx->stream;
@@ -415,6 +441,7 @@ extern "C" int gh_online_tail(gh_ctx* ctx, gh_online* on, int64_t n, const int64
         a.lf = lat->d_layers; a.end_rows = lat->d_end_rows; a.tasks = d_tasks; a.n = n; a.prev = on->d_prev; a.hist = on->d_hist;
         a.hist_stride = on->hist_stride; a.ring_words = on->ring_words; a.anchor = on->d_anchor; a.best_end = d_best;
         a.row_label = d_rowlabel; a.labels = d_labels; a.label_off = d_labeloff; a.n_labels = d_nlabels; a.flag = d_flag;
+        a.begins = d_begins;
         rc = launch_settle(ctx, a, f, false, "gh_online_tail");
         if (rc) return rc;
     }
@@ -425,6 +452,7 @@ extern "C" int gh_online_tail(gh_ctx* ctx, gh_online* on, int64_t n, const int64
     if (labels) {
         GH_HIP(hipMemcpyAsync(n_labels, d_nlabels, (size_t)n * 4, hipMemcpyDeviceToHost, st));
         if (label_off[n] > 0) GH_HIP(hipMemcpyAsync(labels, d_labels, (size_t)label_off[n] * 4, hipMemcpyDeviceToHost, st));
+        if (out_begin && label_off[n] > 0) GH_HIP(hipMemcpyAsync(out_begin, d_begins, (size_t)label_off[n] * 4, hipMemcpyDeviceToHost, st));
     }
     GH_HIP(hipStreamSynchronize(st));
     if (flag & 2) {
@@ -436,4 +464,9 @@ extern "C" int gh_online_tail(gh_ctx* ctx, gh_online* on, int64_t n, const int64
         return GH_ERR_INVALID;
     }
     return GH_OK;
+}
+
+extern "C" int gh_online_tail(gh_ctx* ctx, gh_online* on, int64_t n, const int64_t* ids, double* end_cost, int32_t* best_end,
+                              const int32_t* row_label, int32_t* labels, const int64_t* label_off, int32_t* n_labels) {
+    return gh_online_tail_timed(ctx, on, n, ids, end_cost, best_end, row_label, labels, label_off, n_labels, nullptr);
 }

@@ -118,7 +118,8 @@ struct gh_layers_args {
     const int64_t* bp_off;
     double* end_cost;          // [U, n_end]
     int32_t* best_end;         // [U]
-    int32_t* path;
+    int32_t* path;             // timed label mode (MODE 2 of the back-trace kernels): the begin column of every label, laid out like
+                               // `labels` -- a label launch writes no path, and the block keeps its size and offsets
     const int64_t* path_off;
     int32_t* path_len;
     // sequence form (gh_seq.hip): per-utterance graphs made of shared word templates
@@ -136,13 +137,15 @@ struct gh_layers_args {
 size_t gh_layers_bp_entries(const gh_layerform& f, int64_t T);
 int gh_launch_viterbi_layers(gh_ctx* ctx, const gh_layers_args& a, const gh_layerform& f, int64_t u_begin, int64_t n_utts,
                              bool f64, bool want_path);
-int gh_launch_lattice_backtrace(gh_ctx* ctx, const gh_layers_args& a, const gh_layerform& f, int64_t u_begin, int64_t n_utts);
+int gh_launch_lattice_backtrace(gh_ctx* ctx, const gh_layers_args& a, const gh_layerform& f, int64_t u_begin, int64_t n_utts,
+        bool timed = false);   // timed: label mode with begins in a.path
 // more than GH_LAYERS_ROWW words per layer (gh_viterbi_layers_wide.hip: lane = word); the two launchers above hand over to these
 size_t gh_layers_wide_bp_entries(int64_t T);
 size_t gh_loop_wide_bp_entries(int64_t T);
 int gh_launch_viterbi_layers_wide(gh_ctx* ctx, const gh_layers_args& a, const gh_layerform& f, int64_t u_begin, int64_t n_utts,
                                   bool f64, bool want_path);
-int gh_launch_lattice_backtrace_wide(gh_ctx* ctx, const gh_layers_args& a, const gh_layerform& f, int64_t u_begin, int64_t n_utts);
+int gh_launch_lattice_backtrace_wide(gh_ctx* ctx, const gh_layers_args& a, const gh_layerform& f, int64_t u_begin, int64_t n_utts,
+        bool timed = false);   // timed: label mode with begins in a.path
 // sequence form (forced-alignment lattices, gh_seq.hip): forward sweep, four utterances per wave, and its back-trace
 size_t gh_seq_bp_entries(int N, int skip, int64_t T);
 int gh_launch_viterbi_seq(gh_ctx* ctx, const gh_layers_args& a, int N, int skip, int64_t u_begin, int64_t n_utts, bool f64,
@@ -154,7 +157,8 @@ bool gh_bigram_n_ok(int N, int skip);
 size_t gh_bigram_bp_entries(const gh_layerform& f, int64_t T);
 int gh_launch_viterbi_bigram(gh_ctx* ctx, const gh_layers_args& a, const gh_layerform& f, int64_t u_begin, int64_t n_utts,
                              bool f64, bool want_path);
-int gh_launch_bigram_backtrace(gh_ctx* ctx, const gh_layers_args& a, const gh_layerform& f, int64_t u_begin, int64_t n_utts);
+int gh_launch_bigram_backtrace(gh_ctx* ctx, const gh_layers_args& a, const gh_layerform& f, int64_t u_begin, int64_t n_utts,
+        bool timed = false);   // timed: label mode with begins in a.path
 
 // ---------------------------------------------------------------------------------------------------------------------
 // Decision-word layout of the register forms above, ONE definition for the sweep that writes the words, the back-trace that

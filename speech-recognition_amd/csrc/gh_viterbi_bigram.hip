@@ -181,7 +181,8 @@ __global__ __launch_bounds__(64) void viterbi_bigram_kernel(gh_layers_args a, in
 // of its current (word index, word) in a register and the one below it prefetched.  An entry row's predecessor is the
 // nibble of the SAME lane's record (the loop form scans 16 lanes' equality bits instead).  MODE 0: the (row, column) path
 // as decode_hmm_states returns it, entry rows included; MODE 1: only the label sequence of main.py:59-67
-// (gh_viterbi_labels), collected from the back of the utterance's slot and moved to its front at the end.
+// (gh_viterbi_labels), collected from the back of the utterance's slot and moved to its front at the end; MODE 2: the labels
+// and, in a.path, the column of the first cell of every word's run (gh_viterbi_labels_timed).
 template <int N, bool SKIP, int MODE>
 __global__ __launch_bounds__(64) void bigram_backtrace_kernel(gh_layers_args a, int64_t slot_end) {
     constexpr int HB = BigramBits<N, SKIP>::HB, CPW = BigramBits<N, SKIP>::CPW;
@@ -207,7 +208,9 @@ __global__ __launch_bounds__(64) void bigram_backtrace_kernel(gh_layers_args a, 
     }
     const uint32_t* bpu = reinterpret_cast<const uint32_t*>(a.bp + a.bp_off[slot]);
     int32_t* path = MODE == 0 ? a.path + 2 * a.path_off[u] : nullptr;
-    int32_t* labs = MODE == 1 ? a.labels + a.label_off[u] : nullptr;
+    int32_t* labs = MODE >= 1 ? a.labels + a.label_off[u] : nullptr;
+    int32_t* begs = MODE == 2 ? a.path + a.label_off[u] : nullptr;     // MODE 2: begin column of every label (a.path: see gh_layers_args)
+    int prev_col = 0;                                         // MODE 2: column of the cell visited last
     const int64_t cap = MODE == 0 ? a.path_off[u + 1] - a.path_off[u] : a.label_off[u + 1] - a.label_off[u];
     int64_t len = 0;
     int prev_label = -1;                                      // MODE 1: label of the cell visited last
@@ -225,9 +228,11 @@ __global__ __launch_bounds__(64) void bigram_backtrace_kernel(gh_layers_args a, 
             if (prev_label >= 0 && l < 0) {
                 if (len >= cap) { flag |= 8; return; }
                 labs[cap - 1 - len] = prev_label;
+                if (MODE == 2) begs[cap - 1 - len] = prev_col;
                 ++len;
             }
             prev_label = l;
+            if (MODE == 2) prev_col = col;
         }
     };
     while (j != 0 && !flag) {
@@ -281,12 +286,18 @@ __global__ __launch_bounds__(64) void bigram_backtrace_kernel(gh_layers_args a, 
         }
     }
     if (flag) atomicOr(a.flag, flag);
-    if (MODE == 1) {
+    if (MODE >= 1) {
         if (!flag && prev_label >= 0) {
             if (len >= cap) atomicOr(a.flag, 8);
-            else { labs[cap - 1 - len] = prev_label; ++len; }
+            else {
+                labs[cap - 1 - len] = prev_label;
+                if (MODE == 2) begs[cap - 1 - len] = prev_col;
+                ++len;
+            }
         }
         for (int64_t i = 0; i < len; ++i) labs[i] = labs[cap - len + i];       // to the front, start -> end order
+        if (MODE == 2)
+            for (int64_t i = 0; i < len; ++i) begs[i] = begs[cap - len + i];
     }
     out_n[u] = (int32_t)len;
 }
@@ -323,7 +334,7 @@ int gh_launch_viterbi_bigram(gh_ctx* ctx, const gh_layers_args& a, const gh_laye
 }
 
 // the path (a.path) or the label sequences (a.labels) of the utterances [u_begin, u_begin + n_utts) from the decision words
-int gh_launch_bigram_backtrace(gh_ctx* ctx, const gh_layers_args& a, const gh_layerform& f, int64_t u_begin, int64_t n_utts) {
+int gh_launch_bigram_backtrace(gh_ctx* ctx, const gh_layers_args& a, const gh_layerform& f, int64_t u_begin, int64_t n_utts, bool timed) {
     if (n_utts <= 0 || !(a.path || a.labels)) return GH_OK;
     gh_layers_args b = a;
     b.slot0 = u_begin;
@@ -332,7 +343,8 @@ int gh_launch_bigram_backtrace(gh_ctx* ctx, const gh_layers_args& a, const gh_la
     const bool labels = a.labels != nullptr;
 #define GH_BT(ET, NN, SK)                                                                                             \
     do {                                                                                                              \
-        if (labels) hipLaunchKernelGGL((bigram_backtrace_kernel<NN, SK, 1>), grid, blk, 0, ctx->stream, b, slot_end);   \
+        if (timed) hipLaunchKernelGGL((bigram_backtrace_kernel<NN, SK, 2>), grid, blk, 0, ctx->stream, b, slot_end); \
+        else if (labels) hipLaunchKernelGGL((bigram_backtrace_kernel<NN, SK, 1>), grid, blk, 0, ctx->stream, b, slot_end); \
         else hipLaunchKernelGGL((bigram_backtrace_kernel<NN, SK, 0>), grid, blk, 0, ctx->stream, b, slot_end);          \
     } while (0)
     GH_BG_CASES(double, GH_BT)

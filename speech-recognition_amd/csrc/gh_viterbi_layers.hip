@@ -367,7 +367,8 @@ __global__ __launch_bounds__(64) void viterbi_loop_kernel(gh_layers_args a, int6
 // MODE 0: the (row, column) path as decode_hmm_states returns it; MODE 1: only the label sequence of main.py:59-67
 // (gh_viterbi_labels) -- cells are visited end -> start, a run of labelled rows reports the label of its first row
 // in start -> end order, i.e. of the last one visited before an unlabelled row; labels are collected from the back of
-// the utterance's slot and moved to its front at the end.
+// the utterance's slot and moved to its front at the end.  MODE 2 (gh_viterbi_labels_timed): MODE 1, and every label also stores
+// the column of the cell visited last -- the first cell of the word's run, the word's begin frame -- at the same position of the begins (a.path).
 template <int N, bool SKIP, bool LOOP, int MODE, int H = 2>
 __global__ __launch_bounds__(64) void lattice_backtrace_kernel(gh_layers_args a, int64_t slot_end) {
     constexpr int HB = LOOP ? LoopBits<N, SKIP>::HB : LayerBits<N, SKIP, H>::HB;
@@ -405,7 +406,9 @@ __global__ __launch_bounds__(64) void lattice_backtrace_kernel(gh_layers_args a,
     }
     const WT* bpu = reinterpret_cast<const WT*>(a.bp + a.bp_off[slot]);
     int32_t* path = MODE == 0 ? a.path + 2 * a.path_off[u] : nullptr;
-    int32_t* labs = MODE == 1 ? a.labels + a.label_off[u] : nullptr;
+    int32_t* labs = MODE >= 1 ? a.labels + a.label_off[u] : nullptr;
+    int32_t* begs = MODE == 2 ? a.path + a.label_off[u] : nullptr;     // MODE 2: begin column of every label (a.path: see gh_layers_args)
+    int prev_col = 0;                                         // MODE 2: column of the cell visited last
     const int64_t cap = MODE == 0 ? a.path_off[u + 1] - a.path_off[u] : a.label_off[u + 1] - a.label_off[u];
     int64_t len = 0;
     int prev_label = -1;                                      // MODE 1: label of the cell visited last
@@ -423,9 +426,11 @@ __global__ __launch_bounds__(64) void lattice_backtrace_kernel(gh_layers_args a,
             if (prev_label >= 0 && l < 0) {
                 if (len >= cap) { flag |= 8; return; }
                 labs[cap - 1 - len] = prev_label;
+                if (MODE == 2) begs[cap - 1 - len] = prev_col;
                 ++len;
             }
             prev_label = l;
+            if (MODE == 2) prev_col = col;
         }
     };
     while (j != 0 && !flag) {
@@ -508,12 +513,18 @@ __global__ __launch_bounds__(64) void lattice_backtrace_kernel(gh_layers_args a,
         }
     }
     if (flag) atomicOr(a.flag, flag);
-    if (MODE == 1) {
+    if (MODE >= 1) {
         if (!flag && prev_label >= 0) {
             if (len >= cap) atomicOr(a.flag, 8);
-            else { labs[cap - 1 - len] = prev_label; ++len; }
+            else {
+                labs[cap - 1 - len] = prev_label;
+                if (MODE == 2) begs[cap - 1 - len] = prev_col;
+                ++len;
+            }
         }
         for (int64_t i = 0; i < len; ++i) labs[i] = labs[cap - len + i];       // to the front, start -> end order
+        if (MODE == 2)
+            for (int64_t i = 0; i < len; ++i) begs[i] = begs[cap - len + i];
     }
     out_n[u] = (int32_t)len;
 }
@@ -571,9 +582,9 @@ int gh_launch_viterbi_layers(gh_ctx* ctx, const gh_layers_args& a, const gh_laye
 }
 
 // the path (a.path) or the label sequences (a.labels) of the utterances [u_begin, u_begin + n_utts) from the decision words
-int gh_launch_lattice_backtrace(gh_ctx* ctx, const gh_layers_args& a, const gh_layerform& f, int64_t u_begin, int64_t n_utts) {
+int gh_launch_lattice_backtrace(gh_ctx* ctx, const gh_layers_args& a, const gh_layerform& f, int64_t u_begin, int64_t n_utts, bool timed) {
     if (n_utts <= 0 || !(a.path || a.labels)) return GH_OK;
-    if (f.W > GH_LAYERS_ROWW) return gh_launch_lattice_backtrace_wide(ctx, a, f, u_begin, n_utts);
+    if (f.W > GH_LAYERS_ROWW) return gh_launch_lattice_backtrace_wide(ctx, a, f, u_begin, n_utts, timed);
     gh_layers_args b = a;
     b.slot0 = u_begin;
     const dim3 grid((unsigned)((n_utts + 63) / 64)), blk(64);
@@ -582,17 +593,20 @@ int gh_launch_lattice_backtrace(gh_ctx* ctx, const gh_layers_args& a, const gh_l
 #define GH_BT(ET, NN, SK)                                                                                               \
     do {                                                                                                                \
         if (f.loop) {                                                                                                   \
-            if (labels) hipLaunchKernelGGL((lattice_backtrace_kernel<NN, SK, true, 1>), grid, blk, 0, ctx->stream, b, slot_end);  \
+            if (timed) hipLaunchKernelGGL((lattice_backtrace_kernel<NN, SK, true, 2>), grid, blk, 0, ctx->stream, b, slot_end); \
+            else if (labels) hipLaunchKernelGGL((lattice_backtrace_kernel<NN, SK, true, 1>), grid, blk, 0, ctx->stream, b, slot_end); \
             else hipLaunchKernelGGL((lattice_backtrace_kernel<NN, SK, true, 0>), grid, blk, 0, ctx->stream, b, slot_end);         \
         } else {                                                                                                        \
             if constexpr (NN <= 8) {                                                                                    \
                 if (f.K > 8) {                                                                                          \
-                    if (labels) hipLaunchKernelGGL((lattice_backtrace_kernel<NN, SK, false, 1, 4>), grid, blk, 0, ctx->stream, b, slot_end); \
+                    if (timed) hipLaunchKernelGGL((lattice_backtrace_kernel<NN, SK, false, 2, 4>), grid, blk, 0, ctx->stream, b, slot_end); \
+                    else if (labels) hipLaunchKernelGGL((lattice_backtrace_kernel<NN, SK, false, 1, 4>), grid, blk, 0, ctx->stream, b, slot_end); \
                     else hipLaunchKernelGGL((lattice_backtrace_kernel<NN, SK, false, 0, 4>), grid, blk, 0, ctx->stream, b, slot_end);        \
                     break;                                                                                              \
                 }                                                                                                       \
             }                                                                                                           \
-            if (labels) hipLaunchKernelGGL((lattice_backtrace_kernel<NN, SK, false, 1>), grid, blk, 0, ctx->stream, b, slot_end); \
+            if (timed) hipLaunchKernelGGL((lattice_backtrace_kernel<NN, SK, false, 2>), grid, blk, 0, ctx->stream, b, slot_end); \
+            else if (labels) hipLaunchKernelGGL((lattice_backtrace_kernel<NN, SK, false, 1>), grid, blk, 0, ctx->stream, b, slot_end); \
             else hipLaunchKernelGGL((lattice_backtrace_kernel<NN, SK, false, 0>), grid, blk, 0, ctx->stream, b, slot_end);        \
         }                                                                                                               \
     } while (0)

@@ -172,7 +172,8 @@ __global__ __launch_bounds__(64) void viterbi_layers_wide_kernel(gh_layers_args 
 
 // Back-trace (decode.py:143-145), ONE LANE PER UTTERANCE (see lattice_backtrace_kernel, gh_viterbi_layers.hip: 64 walks per
 // wave on the vector units).  The decision word of (column j, set of layer bk, word bw) is bpu[(j SETS + (bk >> 2)) 64 + bw];
-// layer bk's bits sit (3 - (bk & 3)) HB bits up.  MODE 0: the (row, column) path; MODE 1: only the label sequence.
+// layer bk's bits sit (3 - (bk & 3)) HB bits up.  MODE 0: the (row, column) path; MODE 1: only the label sequence;
+// MODE 2: the labels and, in a.path, the column of the first cell of every word's run (see lattice_backtrace_kernel).
 template <int N, bool SKIP, int MODE>
 __global__ __launch_bounds__(64) void lattice_backtrace_wide_kernel(gh_layers_args a, int64_t slot_end) {
     constexpr int HB = gh_layer_hb(N, SKIP);
@@ -199,7 +200,9 @@ __global__ __launch_bounds__(64) void lattice_backtrace_wide_kernel(gh_layers_ar
     }
     const uint64_t* bpu = reinterpret_cast<const uint64_t*>(a.bp + a.bp_off[slot]);
     int32_t* path = MODE == 0 ? a.path + 2 * a.path_off[u] : nullptr;
-    int32_t* labs = MODE == 1 ? a.labels + a.label_off[u] : nullptr;
+    int32_t* labs = MODE >= 1 ? a.labels + a.label_off[u] : nullptr;
+    int32_t* begs = MODE == 2 ? a.path + a.label_off[u] : nullptr;     // MODE 2: begin column of every label (a.path: see gh_layers_args)
+    int prev_col = 0;                                         // MODE 2: column of the cell visited last
     const int64_t cap = MODE == 0 ? a.path_off[u + 1] - a.path_off[u] : a.label_off[u + 1] - a.label_off[u];
     int64_t len = 0;
     int prev_label = -1;                                      // MODE 1: label of the cell visited last
@@ -217,9 +220,11 @@ __global__ __launch_bounds__(64) void lattice_backtrace_wide_kernel(gh_layers_ar
             if (prev_label >= 0 && l < 0) {
                 if (len >= cap) { flag |= 8; return; }
                 labs[cap - 1 - len] = prev_label;
+                if (MODE == 2) begs[cap - 1 - len] = prev_col;
                 ++len;
             }
             prev_label = l;
+            if (MODE == 2) prev_col = col;
         }
     };
     while (j != 0 && !flag) {
@@ -275,12 +280,18 @@ __global__ __launch_bounds__(64) void lattice_backtrace_wide_kernel(gh_layers_ar
         }
     }
     if (flag) atomicOr(a.flag, flag);
-    if (MODE == 1) {
+    if (MODE >= 1) {
         if (!flag && prev_label >= 0) {
             if (len >= cap) atomicOr(a.flag, 8);
-            else { labs[cap - 1 - len] = prev_label; ++len; }
+            else {
+                labs[cap - 1 - len] = prev_label;
+                if (MODE == 2) begs[cap - 1 - len] = prev_col;
+                ++len;
+            }
         }
         for (int64_t i = 0; i < len; ++i) labs[i] = labs[cap - len + i];       // to the front, start -> end order
+        if (MODE == 2)
+            for (int64_t i = 0; i < len; ++i) begs[i] = begs[cap - len + i];
     }
     out_n[u] = (int32_t)len;
 }
@@ -429,7 +440,9 @@ __global__ __launch_bounds__(64) void loop_backtrace_wide_kernel(gh_layers_args 
     }
     const uint32_t* bpu = reinterpret_cast<const uint32_t*>(a.bp + a.bp_off[slot]);
     int32_t* path = MODE == 0 ? a.path + 2 * a.path_off[u] : nullptr;
-    int32_t* labs = MODE == 1 ? a.labels + a.label_off[u] : nullptr;
+    int32_t* labs = MODE >= 1 ? a.labels + a.label_off[u] : nullptr;
+    int32_t* begs = MODE == 2 ? a.path + a.label_off[u] : nullptr;     // MODE 2: begin column of every label (a.path: see gh_layers_args)
+    int prev_col = 0;                                         // MODE 2: column of the cell visited last
     const int64_t cap = MODE == 0 ? a.path_off[u + 1] - a.path_off[u] : a.label_off[u + 1] - a.label_off[u];
     int64_t len = 0;
     int prev_label = -1;
@@ -445,9 +458,11 @@ __global__ __launch_bounds__(64) void loop_backtrace_wide_kernel(gh_layers_args 
             if (prev_label >= 0 && l < 0) {
                 if (len >= cap) { flag |= 8; return; }
                 labs[cap - 1 - len] = prev_label;
+                if (MODE == 2) begs[cap - 1 - len] = prev_col;
                 ++len;
             }
             prev_label = l;
+            if (MODE == 2) prev_col = col;
         }
     };
     while (j != 0 && !flag) {
@@ -500,12 +515,18 @@ __global__ __launch_bounds__(64) void loop_backtrace_wide_kernel(gh_layers_args 
         }
     }
     if (flag) atomicOr(a.flag, flag);
-    if (MODE == 1) {
+    if (MODE >= 1) {
         if (!flag && prev_label >= 0) {
             if (len >= cap) atomicOr(a.flag, 8);
-            else { labs[cap - 1 - len] = prev_label; ++len; }
+            else {
+                labs[cap - 1 - len] = prev_label;
+                if (MODE == 2) begs[cap - 1 - len] = prev_col;
+                ++len;
+            }
         }
         for (int64_t i = 0; i < len; ++i) labs[i] = labs[cap - len + i];
+        if (MODE == 2)
+            for (int64_t i = 0; i < len; ++i) begs[i] = begs[cap - len + i];
     }
     out_n[u] = (int32_t)len;
 }
@@ -558,7 +579,7 @@ int gh_launch_viterbi_layers_wide(gh_ctx* ctx, const gh_layers_args& a, const gh
     return GH_OK;
 }
 
-int gh_launch_lattice_backtrace_wide(gh_ctx* ctx, const gh_layers_args& a, const gh_layerform& f, int64_t u_begin, int64_t n_utts) {
+int gh_launch_lattice_backtrace_wide(gh_ctx* ctx, const gh_layers_args& a, const gh_layerform& f, int64_t u_begin, int64_t n_utts, bool timed) {
     if (n_utts <= 0 || !(a.path || a.labels)) return GH_OK;
     gh_layers_args b = a;
     b.slot0 = u_begin;
@@ -568,10 +589,12 @@ int gh_launch_lattice_backtrace_wide(gh_ctx* ctx, const gh_layers_args& a, const
 #define GH_BW(ET, NN, SK)                                                                                                       \
     do {                                                                                                                    \
         if (f.loop) {                                                                                                       \
-            if (labels) hipLaunchKernelGGL((loop_backtrace_wide_kernel<NN, SK, 1>), grid, blk, 0, ctx->stream, b, slot_end); \
+            if (timed) hipLaunchKernelGGL((loop_backtrace_wide_kernel<NN, SK, 2>), grid, blk, 0, ctx->stream, b, slot_end); \
+            else if (labels) hipLaunchKernelGGL((loop_backtrace_wide_kernel<NN, SK, 1>), grid, blk, 0, ctx->stream, b, slot_end); \
             else hipLaunchKernelGGL((loop_backtrace_wide_kernel<NN, SK, 0>), grid, blk, 0, ctx->stream, b, slot_end);        \
         } else {                                                                                                            \
-            if (labels) hipLaunchKernelGGL((lattice_backtrace_wide_kernel<NN, SK, 1>), grid, blk, 0, ctx->stream, b, slot_end); \
+            if (timed) hipLaunchKernelGGL((lattice_backtrace_wide_kernel<NN, SK, 2>), grid, blk, 0, ctx->stream, b, slot_end); \
+            else if (labels) hipLaunchKernelGGL((lattice_backtrace_wide_kernel<NN, SK, 1>), grid, blk, 0, ctx->stream, b, slot_end); \
             else hipLaunchKernelGGL((lattice_backtrace_wide_kernel<NN, SK, 0>), grid, blk, 0, ctx->stream, b, slot_end);        \
         }                                                                                                                   \
     } while (0)

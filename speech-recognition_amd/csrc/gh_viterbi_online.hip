@@ -373,10 +373,11 @@ extern "C" int gh_online_push(gh_ctx* ctx, gh_online* on, const gh_batch* b, con
     return GH_OK;
 }
 
-extern "C" int gh_online_result(gh_ctx* ctx, gh_online* on, int64_t n, const int64_t* ids, double* end_cost, int32_t* best_end,
-                                const int32_t* row_label, int32_t* labels, const int64_t* label_off, int32_t* n_labels,
-                                int32_t* path, const int64_t* path_off, int32_t* path_len) {
+extern "C" int gh_online_result_timed(gh_ctx* ctx, gh_online* on, int64_t n, const int64_t* ids, double* end_cost, int32_t* best_end,
+                                      const int32_t* row_label, int32_t* labels, const int64_t* label_off, int32_t* n_labels,
+                                      int32_t* path, const int64_t* path_off, int32_t* path_len, int32_t* out_begin) {
     GH_REQUIRE(ctx && on, "gh_online_result: NULL argument");
+    GH_REQUIRE(!out_begin || labels, "gh_online_result_timed: out_begin needs labels");
     GH_REQUIRE(ctx == on->ctx, "gh_online_result: the session belongs to another context");
     GH_REQUIRE(!labels || (row_label && label_off && n_labels), "gh_online_result: labels need row_label, label_off and n_labels");
     GH_REQUIRE(!path || (path_off && path_len), "gh_online_result: path needs path_off and path_len");
@@ -402,13 +403,14 @@ extern "C" int gh_online_result(gh_ctx* ctx, gh_online* on, int64_t n, const int
     }
     GH_HIP(hipSetDevice(ctx->device));
     int* d_flag;
-    int32_t *d_best, *d_rowlabel = nullptr, *d_nlabels = nullptr, *d_labels = nullptr, *d_path = nullptr, *d_pathlen = nullptr;
+    int32_t *d_best, *d_rowlabel = nullptr, *d_nlabels = nullptr, *d_labels = nullptr, *d_begins = nullptr, *d_path = nullptr, *d_pathlen = nullptr;
     double* d_endcost;
     int64_t *d_ids, *d_uttoff, *d_bpoff, *d_labeloff = nullptr, *d_pathoff = nullptr;
     Carver cv;
     cv.add(&d_flag, 64); cv.add(&d_best, (size_t)n); cv.add(&d_endcost, (size_t)n * n_end);
     cv.add(&d_ids, (size_t)n); cv.add(&d_uttoff, (size_t)n + 1); cv.add(&d_bpoff, (size_t)n);
     if (labels) { cv.add(&d_rowlabel, (size_t)R); cv.add(&d_labeloff, (size_t)n + 1); cv.add(&d_nlabels, (size_t)n); cv.add(&d_labels, (size_t)label_off[n]); }
+    if (out_begin) cv.add(&d_begins, (size_t)label_off[n]);
     if (path) { cv.add(&d_pathoff, (size_t)n + 1); cv.add(&d_pathlen, (size_t)n); cv.add(&d_path, (size_t)2 * path_off[n]); }
     int rc = cv.commit(ctx);
     if (rc) return rc;
@@ -436,7 +438,8 @@ extern "C" int gh_online_result(gh_ctx* ctx, gh_online* on, int64_t n, const int
     }
     if (labels) {
         c.row_label = d_rowlabel; c.labels = d_labels; c.label_off = d_labeloff; c.n_labels = d_nlabels;
-        rc = gh_launch_lattice_backtrace(ctx, c, f, 0, n);
+        if (d_begins) c.path = d_begins;                    // timed label mode: the begins go where a path launch has its path
+        rc = gh_launch_lattice_backtrace(ctx, c, f, 0, n, d_begins != nullptr);
         if (rc) return rc;
     }
     int flag = 0;
@@ -446,6 +449,7 @@ extern "C" int gh_online_result(gh_ctx* ctx, gh_online* on, int64_t n, const int
     if (labels) {
         GH_HIP(hipMemcpyAsync(n_labels, d_nlabels, (size_t)n * 4, hipMemcpyDeviceToHost, st));
         if (label_off[n] > 0) GH_HIP(hipMemcpyAsync(labels, d_labels, (size_t)label_off[n] * 4, hipMemcpyDeviceToHost, st));
+        if (out_begin && label_off[n] > 0) GH_HIP(hipMemcpyAsync(out_begin, d_begins, (size_t)label_off[n] * 4, hipMemcpyDeviceToHost, st));
     }
     if (path) {
         GH_HIP(hipMemcpyAsync(path_len, d_pathlen, (size_t)n * 4, hipMemcpyDeviceToHost, st));
@@ -465,4 +469,11 @@ extern "C" int gh_online_result(gh_ctx* ctx, gh_online* on, int64_t n, const int
         return GH_ERR_INVALID;
     }
     return GH_OK;
+}
+
+extern "C" int gh_online_result(gh_ctx* ctx, gh_online* on, int64_t n, const int64_t* ids, double* end_cost, int32_t* best_end,
+                                const int32_t* row_label, int32_t* labels, const int64_t* label_off, int32_t* n_labels,
+                                int32_t* path, const int64_t* path_off, int32_t* path_len) {
+    return gh_online_result_timed(ctx, on, n, ids, end_cost, best_end, row_label, labels, label_off, n_labels, path, path_off, path_len,
+                                  nullptr);
 }

@@ -104,10 +104,14 @@ SIGNATURES = {
     "gh_viterbi_path_cap": (C.c_int64, [C.c_void_p, C.c_int, C.c_int64]),
     "gh_viterbi_labels": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, _c_i32p, _c_i32p, _c_f64p, _c_i32p, _c_i32p,
                                     _c_i64p, _c_i32p]),
+    "gh_viterbi_labels_timed": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, _c_i32p, _c_i32p, _c_f64p, _c_i32p, _c_i32p,
+                                    _c_i64p, _c_i32p, _c_i32p]),
     "gh_align_segments": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, _c_i32p, _c_f64p, _c_i32p, _c_i32p]),
     "gh_align_runs": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, _c_i32p, _c_f64p, _c_i32p, C.c_int, _c_i32p, _c_i32p]),
     "gh_viterbi_labels_packed": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, _c_i32p, _c_i32p, C.c_int, _c_f64p, _c_i32p,
                                            _c_i32p, C.c_int64, _c_i32p]),
+    "gh_viterbi_labels_packed_timed": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, _c_i32p, _c_i32p, C.c_int, _c_f64p, _c_i32p,
+                                           _c_i32p, C.c_int64, _c_i32p, _c_i32p]),
     "gh_dtw": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, _c_f64p, _c_f64p, _c_f64p, C.c_int, _c_f64p,
                          _c_f64p, _c_i32p, _c_i32p]),
     "gh_kmeans_assign": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int, _c_f64p, _c_f64p,
@@ -169,9 +173,13 @@ SIGNATURES = {
     "gh_online_frames": (C.c_int, [C.c_void_p, _c_i64p]),
     "gh_online_result": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, _c_i64p, _c_f64p, _c_i32p, _c_i32p, _c_i32p, _c_i64p, _c_i32p,
                                    _c_i32p, _c_i64p, _c_i32p]),
+    "gh_online_result_timed": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, _c_i64p, _c_f64p, _c_i32p, _c_i32p, _c_i32p, _c_i64p, _c_i32p,
+                                   _c_i32p, _c_i64p, _c_i32p, _c_i32p]),
     "gh_online_create_window": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.POINTER(C.c_void_p)]),
     "gh_online_commit": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, _c_i64p, _c_i64p, _c_i32p, _c_i32p, _c_i64p, _c_i32p]),
+    "gh_online_commit_timed": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, _c_i64p, _c_i64p, _c_i32p, _c_i32p, _c_i64p, _c_i32p, _c_i32p]),
     "gh_online_tail": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, _c_i64p, _c_f64p, _c_i32p, _c_i32p, _c_i32p, _c_i64p, _c_i32p]),
+    "gh_online_tail_timed": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, _c_i64p, _c_f64p, _c_i32p, _c_i32p, _c_i32p, _c_i64p, _c_i32p, _c_i32p]),
     "gh_wordstream_create": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_void_p)]),
     "gh_wordstream_destroy": (None, [C.c_void_p]),
     "gh_wordstream_reset": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, _c_i64p]),
@@ -1289,7 +1297,8 @@ class Lattices:
                             for u in range(U)]
         return out
 
-    def viterbi_labels(self, batch, row_label, utt_lattice=None, max_labels=None, as_lists=True, want_end_cost=True):
+    def viterbi_labels(self, batch, row_label, utt_lattice=None, max_labels=None, as_lists=True, want_end_cost=True,
+                       want_begin=False):
         """A6 + A12 in one call: decode, keep the path on the device, return the decoded label sequences
         (main.py:59-67: first row of every emitting run between non-emitting rows).  row_label: one int32 array per
         graph (label per row, < 0 on non-emitting rows) or a single array when there is one graph.
@@ -1298,7 +1307,9 @@ class Lattices:
         n_labels); as_lists=False leaves out the per-utterance list (at 10^5 utterances building it costs more host
         time than the decode takes on the GPU): utterance u is labels_flat[label_off[u] : label_off[u] + n_labels[u]].
         want_end_cost=False: the costs of the end rows stay on the device (best_end, the chosen end row, still comes back) --
-        for a 10-word grammar that is 80 bytes per utterance of copy-back a label decode has no use for."""
+        for a 10-word grammar that is 80 bytes per utterance of copy-back a label decode has no use for.
+        want_begin=True (gh_viterbi_labels_timed): adds begins_flat, aligned with labels_flat on both routes, and with
+        as_lists `begins` -- the begin frame of every word: the column of the first cell of its run (main.py:59-67)."""
         lib, U = self.ctx.lib, batch.U
         lat = None if utt_lattice is None else np.ascontiguousarray(utt_lattice, dtype=np.int32)
         lidx = np.zeros(U, dtype=np.int64) if lat is None else lat.astype(np.int64)
@@ -1322,21 +1333,40 @@ class Lattices:
             # packed: one device slot of the largest capacity per utterance, only the labels that exist come back
             mx = int(max(1, np.max(cap)))
             labels = np.empty(U * mx, dtype=np.int32)
-            _check(lib, lib.gh_viterbi_labels_packed(self.ctx.h, self.h, batch.h, _ptr(lat, _c_i32p), _ptr(rl, _c_i32p), mx,
-                                                     _ptr(end_cost, _c_f64p), _ptr(best_end, _c_i32p), _ptr(labels, _c_i32p),
-                                                     labels.size, _ptr(n_labels, _c_i32p)))
+            if want_begin:
+                begins = np.empty(U * mx, dtype=np.int32)
+                _check(lib, lib.gh_viterbi_labels_packed_timed(self.ctx.h, self.h, batch.h, _ptr(lat, _c_i32p), _ptr(rl, _c_i32p), mx,
+                                                               _ptr(end_cost, _c_f64p), _ptr(best_end, _c_i32p), _ptr(labels, _c_i32p),
+                                                               labels.size, _ptr(n_labels, _c_i32p), _ptr(begins, _c_i32p)))
+            else:
+                _check(lib, lib.gh_viterbi_labels_packed(self.ctx.h, self.h, batch.h, _ptr(lat, _c_i32p), _ptr(rl, _c_i32p), mx,
+                                                         _ptr(end_cost, _c_f64p), _ptr(best_end, _c_i32p), _ptr(labels, _c_i32p),
+                                                         labels.size, _ptr(n_labels, _c_i32p)))
             label_off = np.concatenate([[0], np.cumsum(n_labels)]).astype(np.int64)
-            return dict(best_end=best_end, end_off=end_off, end_cost_flat=end_cost, labels_flat=labels[:label_off[-1]],
-                        label_off=label_off[:-1], n_labels=n_labels)
+            out = dict(best_end=best_end, end_off=end_off, end_cost_flat=end_cost, labels_flat=labels[:label_off[-1]],
+                       label_off=label_off[:-1], n_labels=n_labels)
+            if want_begin:
+                out["begins_flat"] = begins[:label_off[-1]]
+            return out
         label_off = np.concatenate([[0], np.cumsum(cap)]).astype(np.int64)
         labels = np.empty(int(label_off[-1]), dtype=np.int32)
-        _check(lib, lib.gh_viterbi_labels(self.ctx.h, self.h, batch.h, _ptr(lat, _c_i32p), _ptr(rl, _c_i32p),
-                                          _ptr(end_cost, _c_f64p), _ptr(best_end, _c_i32p), _ptr(labels, _c_i32p),
-                                          _ptr(label_off, _c_i64p), _ptr(n_labels, _c_i32p)))
+        if want_begin:
+            begins = np.empty(int(label_off[-1]), dtype=np.int32)
+            _check(lib, lib.gh_viterbi_labels_timed(self.ctx.h, self.h, batch.h, _ptr(lat, _c_i32p), _ptr(rl, _c_i32p),
+                                                    _ptr(end_cost, _c_f64p), _ptr(best_end, _c_i32p), _ptr(labels, _c_i32p),
+                                                    _ptr(label_off, _c_i64p), _ptr(n_labels, _c_i32p), _ptr(begins, _c_i32p)))
+        else:
+            _check(lib, lib.gh_viterbi_labels(self.ctx.h, self.h, batch.h, _ptr(lat, _c_i32p), _ptr(rl, _c_i32p),
+                                              _ptr(end_cost, _c_f64p), _ptr(best_end, _c_i32p), _ptr(labels, _c_i32p),
+                                              _ptr(label_off, _c_i64p), _ptr(n_labels, _c_i32p)))
         out = dict(best_end=best_end, end_off=end_off, end_cost_flat=end_cost, labels_flat=labels, label_off=label_off,
                    n_labels=n_labels)
+        if want_begin:
+            out["begins_flat"] = begins
         if as_lists:
             out["labels"] = [labels[label_off[u]:label_off[u] + n_labels[u]] for u in range(U)]
+            if want_begin:
+                out["begins"] = [begins[label_off[u]:label_off[u] + n_labels[u]] for u in range(U)]
         return out
 
     SEGMENT_START = 1 << 30
@@ -1476,10 +1506,11 @@ class OnlineSession:
         _check(self.ctx.lib, self.ctx.lib.gh_online_frames(self.h, _ptr(out, _c_i64p)))
         return out
 
-    def result(self, ids=None, row_label=None, max_labels=None, want_path=False):
+    def result(self, ids=None, row_label=None, max_labels=None, want_path=False, want_begin=False):
         """dict(end_cost [n, n_end], best_end [n], frames [n][, labels: list of int32 arrays][, paths: list of int64 [K, 2]])
         for the streams `ids` (None: all).  row_label [R]: the label sequences of gh_viterbi_labels (max_labels: scalar or
-        [n] bound per stream); want_path: the reference-style (row, column) paths."""
+        [n] bound per stream); want_path: the reference-style (row, column) paths; want_begin (with row_label): adds
+        `begins`, the begin frame of every label (gh_online_result_timed)."""
         lib = self.ctx.lib
         ids = np.arange(self.n_streams, dtype=np.int64) if ids is None else self._i64(ids)
         n = len(ids)
@@ -1497,19 +1528,23 @@ class OnlineSession:
             label_off = np.concatenate([[0], np.cumsum(cap)]).astype(np.int64)
             labels = np.empty(int(label_off[-1]), dtype=np.int32)
             n_labels = np.empty(n, dtype=np.int32)
+        begins = np.empty(int(label_off[-1]), dtype=np.int32) if want_begin and rl is not None else None
         if want_path:
             path_off = np.concatenate([[0], np.cumsum(np.where(T > 1, T * self._nlev, 0))]).astype(np.int64)
             path = np.empty((int(path_off[-1]), 2), dtype=np.int32)
             path_len = np.empty(n, dtype=np.int32)
-        rc = lib.gh_online_result(self.ctx.h, self.h, n, _ptr(ids, _c_i64p), _ptr(end_cost, _c_f64p), _ptr(best_end, _c_i32p),
-                                  _ptr(rl, _c_i32p), _ptr(labels, _c_i32p), _ptr(label_off, _c_i64p), _ptr(n_labels, _c_i32p),
-                                  _ptr(path, _c_i32p), _ptr(path_off, _c_i64p), _ptr(path_len, _c_i32p))
+        args = (self.ctx.h, self.h, n, _ptr(ids, _c_i64p), _ptr(end_cost, _c_f64p), _ptr(best_end, _c_i32p),
+                _ptr(rl, _c_i32p), _ptr(labels, _c_i32p), _ptr(label_off, _c_i64p), _ptr(n_labels, _c_i32p),
+                _ptr(path, _c_i32p), _ptr(path_off, _c_i64p), _ptr(path_len, _c_i32p))
+        rc = lib.gh_online_result_timed(*args, _ptr(begins, _c_i32p)) if begins is not None else lib.gh_online_result(*args)
         if rc == GH_ERR_UNSUPPORTED:                                      # a session with a window: commit() and tail()
             raise Unsupported(lib.gh_last_error().decode("utf-8", "replace"))
         _check(lib, rc)
         out = dict(end_cost=end_cost, best_end=best_end, frames=T)
         if rl is not None:
             out["labels"] = [labels[label_off[i]:label_off[i] + n_labels[i]] for i in range(n)]
+        if begins is not None:
+            out["begins"] = [begins[label_off[i]:label_off[i] + n_labels[i]] for i in range(n)]
         if want_path:
             out["paths"] = [path[path_off[i]:path_off[i] + path_len[i]].astype(np.int64) for i in range(n)]
         return out
@@ -1522,10 +1557,11 @@ class OnlineSession:
         label_off = np.concatenate([[0], np.cumsum(cap)]).astype(np.int64)
         return rl, np.empty(int(label_off[-1]), dtype=np.int32), label_off, np.empty(len(ids), dtype=np.int32)
 
-    def commit(self, ids=None, row_label=None, max_labels=None):
+    def commit(self, ids=None, row_label=None, max_labels=None, want_begin=False):
         """Advances the anchor of the streams `ids` (None: all; distinct): dict(settled_frames [n]: anchor column + 1, 0 =
         nothing settled yet[, labels: list of int32 arrays -- what THIS call settled]).  max_labels: scalar or [n] bound
-        per stream (default: one label per frame of the session's longest stream)."""
+        per stream (default: one label per frame of the session's longest stream).  want_begin (with row_label): adds
+        `begins`, the begin frame of every newly settled word -- an absolute column of the stream (gh_online_commit_timed)."""
         lib = self.ctx.lib
         ids = np.arange(self.n_streams, dtype=np.int64) if ids is None else self._i64(ids)
         n = len(ids)
@@ -1533,16 +1569,21 @@ class OnlineSession:
         rl = labels = label_off = n_labels = None
         if row_label is not None:
             rl, labels, label_off, n_labels = self._label_room(ids, row_label, int(self.frames().max()) + 1 if max_labels is None else max_labels)
-        _check(lib, lib.gh_online_commit(self.ctx.h, self.h, n, _ptr(ids, _c_i64p), _ptr(settled, _c_i64p), _ptr(rl, _c_i32p),
-                                         _ptr(labels, _c_i32p), _ptr(label_off, _c_i64p), _ptr(n_labels, _c_i32p)))
+        begins = np.empty(len(labels), dtype=np.int32) if want_begin and rl is not None else None
+        args = (self.ctx.h, self.h, n, _ptr(ids, _c_i64p), _ptr(settled, _c_i64p), _ptr(rl, _c_i32p),
+                _ptr(labels, _c_i32p), _ptr(label_off, _c_i64p), _ptr(n_labels, _c_i32p))
+        _check(lib, lib.gh_online_commit_timed(*args, _ptr(begins, _c_i32p)) if begins is not None else lib.gh_online_commit(*args))
         out = dict(settled_frames=settled)
         if rl is not None:
             out["labels"] = [labels[label_off[i]:label_off[i] + n_labels[i]] for i in range(n)]
+        if begins is not None:
+            out["begins"] = [begins[label_off[i]:label_off[i] + n_labels[i]] for i in range(n)]
         return out
 
-    def tail(self, ids=None, row_label=None, max_labels=None):
+    def tail(self, ids=None, row_label=None, max_labels=None, want_begin=False):
         """dict(end_cost [n, n_end], best_end [n], frames [n][, labels: the labels behind the anchor, list of int32 arrays])
-        for the streams `ids` (None: all); a stream without an anchor gives its whole label sequence."""
+        for the streams `ids` (None: all); a stream without an anchor gives its whole label sequence.  want_begin (with
+        row_label): adds `begins`, the begin frames of those labels (gh_online_tail_timed)."""
         lib = self.ctx.lib
         ids = np.arange(self.n_streams, dtype=np.int64) if ids is None else self._i64(ids)
         n = len(ids)
@@ -1553,11 +1594,15 @@ class OnlineSession:
         rl = labels = label_off = n_labels = None
         if row_label is not None:
             rl, labels, label_off, n_labels = self._label_room(ids, row_label, T + 1 if max_labels is None else max_labels)
-        _check(lib, lib.gh_online_tail(self.ctx.h, self.h, n, _ptr(ids, _c_i64p), _ptr(end_cost, _c_f64p), _ptr(best_end, _c_i32p),
-                                       _ptr(rl, _c_i32p), _ptr(labels, _c_i32p), _ptr(label_off, _c_i64p), _ptr(n_labels, _c_i32p)))
+        begins = np.empty(len(labels), dtype=np.int32) if want_begin and rl is not None else None
+        args = (self.ctx.h, self.h, n, _ptr(ids, _c_i64p), _ptr(end_cost, _c_f64p), _ptr(best_end, _c_i32p),
+                _ptr(rl, _c_i32p), _ptr(labels, _c_i32p), _ptr(label_off, _c_i64p), _ptr(n_labels, _c_i32p))
+        _check(lib, lib.gh_online_tail_timed(*args, _ptr(begins, _c_i32p)) if begins is not None else lib.gh_online_tail(*args))
         out = dict(end_cost=end_cost, best_end=best_end, frames=T)
         if rl is not None:
             out["labels"] = [labels[label_off[i]:label_off[i] + n_labels[i]] for i in range(n)]
+        if begins is not None:
+            out["begins"] = [begins[label_off[i]:label_off[i] + n_labels[i]] for i in range(n)]
         return out
 
     def close(self):

@@ -13,7 +13,8 @@ from . import _hip
 from . import _pack
 from .continuous_speech import packed_lattice, packed_loop_lattice, packed_bigram_lattice
 
-__all__ = ["IsolatedWordRecognizer", "ContinuousDecoder", "OnlineDecoder", "OnlineWordRecognizer", "InFlight", "path_to_words", "sequence_report", "train_words"]
+__all__ = ["IsolatedWordRecognizer", "ContinuousDecoder", "OnlineDecoder", "OnlineWordRecognizer", "InFlight", "path_to_words", "path_to_word_times", "word_spans",
+           "sequence_report", "train_words"]
 
 
 def _stack_models(ctx, models):
@@ -319,6 +320,29 @@ def path_to_words(path, row_state, n_per_word):
     return [int(s) // n_per_word for s in st[first]]
 
 
+def path_to_word_times(path, row_state, n_per_word):
+    """(words, begins) of a path as decode_hmm_states returns it (end -> start, without the end cell) -- the host statement
+    of the begin rule.  Walk the path start -> end (main.py:59-67): a word is a maximal run of cells on emitting rows
+    between non-emitting rows, its label is the label of the run's first cell (`path_to_words`), and ITS BEGIN IS THE
+    COLUMN OF THAT FIRST CELL.  Begins are frame indices inside the utterance; an empty path gives two empty lists."""
+    if len(path) == 0:
+        return [], []
+    cells = np.asarray(path)[::-1]
+    st = np.asarray(row_state)[cells[:, 0]]
+    emitting = st >= 0
+    first = emitting & np.insert(~emitting[:-1], 0, True)
+    return [int(s) // n_per_word for s in st[first]], [int(c) for c in cells[first, 1]]
+
+
+def word_spans(begins, frames):
+    """[(begin, end), ...] of the words of one utterance of `frames` frames from their begins: word k ends where word
+    k + 1 begins and the last word ends at the utterance's frame count.  (A non-emitting row shares its column with the
+    cell behind it, so a word's last frame and the next word's first frame are the same column; like the regrouping of
+    continuous_train, the boundary frame goes to the next word only.  The spans tile [begins[0], frames).)"""
+    b = [int(x) for x in begins]
+    return list(zip(b, b[1:] + [int(frames)]))
+
+
 class ContinuousDecoder:
     """Continuous-word decode over all `models`, then `path_to_words`.
 
@@ -365,22 +389,36 @@ class ContinuousDecoder:
         self.row_state = graph["row_state"]
         self.lat = _hip.Lattices(self.ctx, [graph])
 
-    def decode_batch(self, batch, want_path=False):
+    def decode_batch(self, batch, want_path=False, want_times=False):
         """Word-index lists of every utterance (+ the raw result dict).  By default the paths stay on the device
         and only the decoded word sequences come back (gh_viterbi_labels); want_path=True also returns the
-        reference-style (row, column) paths in `r["paths"]` and derives the words from them on the host."""
+        reference-style (row, column) paths in `r["paths"]` and derives the words from them on the host.
+        want_times=True: `r["begins"]` holds one int32 array per utterance, aligned with its words -- the frame every word
+        begins in (`path_to_word_times`; gh_viterbi_labels_timed, or the host rule on the paths with want_path=True).
+        Word k ends where word k + 1 begins, the last one at the utterance's frame count (`word_spans`)."""
         batch.loglik(self.gmm, fetch=False)
         if want_path:
             r = self.lat.viterbi(batch, want_path=True)
+            if want_times:
+                wt = [path_to_word_times(p, self.row_state, self.n) for p in r["paths"]]
+                r["begins"] = [np.asarray(b, dtype=np.int32) for _, b in wt]
+                return [w for w, _ in wt], r
             return [path_to_words(p, self.row_state, self.n) for p in r["paths"]], r
         row_word = np.where(self.row_state >= 0, self.row_state // self.n, -1).astype(np.int32)
-        r = self.lat.viterbi_labels(batch, row_word, max_labels=self._max_labels(batch.lengths))
+        if want_times:
+            r = self.lat.viterbi_labels(batch, row_word, max_labels=self._max_labels(batch.lengths), want_begin=True)
+        else:
+            r = self.lat.viterbi_labels(batch, row_word, max_labels=self._max_labels(batch.lengths))
         return [[int(w) for w in l] for l in r["labels"]], r
 
-    def decode(self, xs):
-        """xs: list of [T_u, D] arrays -> list of word-index lists."""
+    def decode(self, xs, want_times=False):
+        """xs: list of [T_u, D] arrays -> list of word-index lists; want_times=True: (words, begins), begins one int32
+        array per utterance (see `decode_batch`)."""
         batch = _hip.Batch(self.ctx, xs, dtype=self.dtype)
         try:
+            if want_times:
+                words, r = self.decode_batch(batch, want_times=True)
+                return words, r["begins"]
             return self.decode_batch(batch)[0]
         finally:
             batch.close()
@@ -389,15 +427,16 @@ class ContinuousDecoder:
         """Decode `xs` and tally against the label strings like main.py:54-84 -- see `sequence_report`."""
         return sequence_report(self.decode(xs), labels, verbose=verbose)
 
-    def online(self, n_streams, max_frames=None, window=None, frontend=None, endpointer=None):
+    def online(self, n_streams, max_frames=None, window=None, frontend=None, endpointer=None, times=False):
         """An `OnlineDecoder` of `n_streams` live utterances sharing this decoder's packed mixtures and graph
         (grammar="loop" only: anything else raises `_hip.Unsupported`).  Exactly one of `max_frames` (utterances of up to
         that many frames, whole history kept) and `window` (utterances of any length, history for that many unsettled
         frames) must be given.  frontend: a `sr.feature.StreamingFrontend` of the same context, dtype and `n_streams`
         (39 features, like the models) -- the decoder then takes audio (`push_audio`).  endpointer: a
         `sr.audio_capture.StreamingEndpointer` of the same context, sample rate and `n_streams` (needs a front-end) -- the
-        decoder then takes whole recordings and cuts the utterances out itself (`push_recording`)."""
-        return OnlineDecoder(self, n_streams, max_frames, window, frontend, endpointer)
+        decoder then takes whole recordings and cuts the utterances out itself (`push_recording`).  times=True: the
+        decoder also keeps and reports the frame every word begins in (see `OnlineDecoder`)."""
+        return OnlineDecoder(self, n_streams, max_frames, window, frontend, endpointer, times)
 
 
 class _OnlineStreams:
@@ -610,9 +649,21 @@ class OnlineDecoder(_OnlineStreams):
     host link twice, once for the endpointer and once for the front-end.  If the decoder or the front-end refuses a
     piece (`max_frames`, `window`), the endpointer has already moved: `push_recording` raises ValueError naming the
     streams, and they must be `reset`.  With an endpointer `reset` starts a new RECORDING (all three objects), `finish`
-    a new utterance (decoder and front-end only)."""
+    a new utterance (decoder and front-end only).
 
-    def __init__(self, decoder, n_streams, max_frames=None, window=None, frontend=None, endpointer=None):
+    WORD TIMES.  `online(..., times=True)` keeps the begin frame of every word beside the word (the column of the first
+    cell of its run, `path_to_word_times`; an absolute frame index since the stream's last reset, also with `window=`
+    after the ring has wrapped):
+
+        on = dec.online(n_streams=64, window=400, times=True)
+        new_words, new_begins = on.commit(ids, want_times=True)   # a settled word's begin is known at once ...
+        words, info = on.result([3]); info["begins"][0]            # ... its end is the next word's begin (`word_spans`)
+
+    `result` / `finish` add `info["begins"]`, `settled_times` gives the begins of all settled words, `push_recording`
+    dicts gain `begins` (frames inside the utterance) and `word_begin` (recording samples: `begin` + frame x the
+    front-end's `step`).  With times=False nothing changes and `want_times=True` raises ValueError."""
+
+    def __init__(self, decoder, n_streams, max_frames=None, window=None, frontend=None, endpointer=None, times=False):
         if decoder.grammar != "loop":
             raise _hip.Unsupported("online decoding takes the word-loop grammar (grammar='loop'), not %r" % (decoder.grammar,))
         if (max_frames is None) == (window is None):
@@ -629,6 +680,8 @@ class OnlineDecoder(_OnlineStreams):
             self.session = _hip.OnlineSession(decoder.ctx, decoder.lat, self.n_streams, window=self.window)
         self._settled = np.zeros(self.n_streams, dtype=np.int64)      # settled frames (anchor column + 1) of every stream
         self._words = [[] for _ in range(self.n_streams)]             # ... and its settled words
+        self.times = bool(times)
+        self._begins = [[] for _ in range(self.n_streams)]            # times=True: the begin frames of the settled words
         self._row_word = np.where(decoder.row_state >= 0, decoder.row_state // decoder.n, -1).astype(np.int32)
 
     def _room(self, ids, counts):
@@ -648,35 +701,59 @@ class OnlineDecoder(_OnlineStreams):
         all) for the frames pushed so far: what `decode_batch` returns for those frames as whole utterances."""
         ids = np.arange(self.n_streams, dtype=np.int64) if ids is None else self._ids(ids, distinct=False)
         dec = self.decoder
+        tm = dict(want_begin=True) if self.times else {}
         if self.window is not None:
             if want_path:
                 raise ValueError("a decoder with a window offers no paths")
-            r = self.session.tail(ids, row_label=self._row_word, max_labels=self._frames[ids] - self._settled[ids] + 2)
+            r = self.session.tail(ids, row_label=self._row_word, max_labels=self._frames[ids] - self._settled[ids] + 2, **tm)
+            if self.times:                                # the settled begins followed by the tail's
+                r["begins"] = [np.asarray(self._begins[k] + [int(b) for b in bl], dtype=np.int32) for k, bl in zip(ids, r["begins"])]
             return [self._words[k] + [int(w) for w in l] for k, l in zip(ids, r.pop("labels"))], r
         if want_path:
             r = self.session.result(ids, want_path=True)
+            if self.times:
+                wt = [path_to_word_times(p, dec.row_state, dec.n) for p in r["paths"]]
+                r["begins"] = [np.asarray(b, dtype=np.int32) for _, b in wt]
+                return [w for w, _ in wt], r
             return [path_to_words(p, dec.row_state, dec.n) for p in r["paths"]], r
-        r = self.session.result(ids, row_label=self._row_word, max_labels=dec._max_labels(self._frames[ids]))
+        r = self.session.result(ids, row_label=self._row_word, max_labels=dec._max_labels(self._frames[ids]), **tm)
         return [[int(w) for w in l] for l in r.pop("labels")], r
 
-    def commit(self, ids=None):
+    def commit(self, ids=None, want_times=False):
         """Settles what can no longer change of the streams `ids` (None: all; distinct): the list of the words that became
         final with THIS call, per stream.  Nothing is settled while a stream has fewer than two frames or no live cell, or
-        while its traces do not meet."""
+        while its traces do not meet.  want_times=True (a decoder with times=True): (new_words, new_begins), the begin
+        frame of every newly settled word beside it."""
+        if want_times and not self.times:
+            raise ValueError("this decoder keeps no word times: online(..., times=True)")
         ids = np.arange(self.n_streams, dtype=np.int64) if ids is None else self._ids(ids)
+        tm = dict(want_begin=True) if self.times else {}
         # (room for a word per unsettled frame: with skip arcs a word can pass in fewer than n - 1 column steps)
-        r = self.session.commit(ids, row_label=self._row_word, max_labels=self._frames[ids] - self._settled[ids] + 2)
+        r = self.session.commit(ids, row_label=self._row_word, max_labels=self._frames[ids] - self._settled[ids] + 2, **tm)
         new = [[int(w) for w in l] for l in r["labels"]]
         for k, s, ws in zip(ids, r["settled_frames"], new):
             self._settled[k] = s
             self._words[k] = self._words[k] + ws
-        return new
+        if not self.times:
+            return new
+        new_begins = [[int(b) for b in bl] for bl in r["begins"]]
+        for k, bs in zip(ids, new_begins):
+            self._begins[k] = self._begins[k] + bs
+        return (new, new_begins) if want_times else new
 
     def settled(self, ids=None):
         """(all settled words so far, settled_frames [n]) of the streams `ids` (None: all): stream k's first
         settled_frames[k] frames can no longer change its words."""
         ids = np.arange(self.n_streams, dtype=np.int64) if ids is None else self._ids(ids, distinct=False)
         return [list(self._words[k]) for k in ids], self._settled[ids].copy()
+
+    def settled_times(self, ids=None):
+        """The begin frames of all settled words so far of the streams `ids` (None: all), aligned with `settled`'s words
+        (a decoder with times=True)."""
+        if not self.times:
+            raise ValueError("this decoder keeps no word times: online(..., times=True)")
+        ids = np.arange(self.n_streams, dtype=np.int64) if ids is None else self._ids(ids, distinct=False)
+        return [list(self._begins[k]) for k in ids]
 
     def push_recording(self, ids, chunks, end=None):
         """Stream ids[i] takes the int16 samples chunks[i] of its RECORDING through the decoder's `StreamingEndpointer`
@@ -685,16 +762,21 @@ class OnlineDecoder(_OnlineStreams):
         utterances in order: dicts `stream`, `words`, `begin`, `stop` (recording sample coordinates), `open` (the
         recording ended while speech was open).  A bad argument raises ValueError with nothing moved; a piece that the
         decoder or the front-end refuses raises ValueError AFTER the endpointer has moved: the streams it names must be
-        `reset`."""
+        `reset`.  A decoder with times=True adds `begins` (the frame inside the utterance every word begins in) and
+        `word_begin` (the same in recording samples: `begin` + frame x the front-end's `step`)."""
         out = []
         for r_ids, done, ranges in self._gated(ids, chunks, end):
             if self.window is not None:
                 self.commit(r_ids)
             if len(done):
-                words, _ = self.result(done)
+                words, info = self.result(done)
                 self._reset_utterance(done)
-                for k, w, rg in zip(done, words, ranges):
-                    out.append(dict(stream=int(k), words=w, begin=int(rg[0]), stop=int(rg[1]), open=bool(rg[2])))
+                for i, (k, w, rg) in enumerate(zip(done, words, ranges)):
+                    utt = dict(stream=int(k), words=w, begin=int(rg[0]), stop=int(rg[1]), open=bool(rg[2]))
+                    if self.times:
+                        utt["begins"] = [int(b) for b in info["begins"][i]]
+                        utt["word_begin"] = [int(rg[0]) + b * int(self.frontend.step) for b in utt["begins"]]
+                    out.append(utt)
         return out
 
     def _reset_utterance(self, ids):
@@ -705,6 +787,7 @@ class OnlineDecoder(_OnlineStreams):
             self._settled[ids] = 0
         for k in (range(self.n_streams) if ids is None else ids):
             self._words[int(k)] = []
+            self._begins[int(k)] = []
 
     def finish(self, ids, want_path=False):
         """`result(ids)` followed by a reset of the decoder's and the front-end's streams: the final decode of utterances
