@@ -685,8 +685,8 @@ int gh_text_viterbi(gh_ctx* ctx, const gh_lextree* tree, int64_t n_strings, cons
  * a one-utterance decode of those k frames from the same likelihoods -- end costs, chosen end (last of equal minima,
  * decode.py:129-134), path (end -> start, end cell excluded, :143-145) and label sequence (main.py:59-67).
  * gh_online_create: `lat` must be ONE graph in the narrow loop form (gh_lattices_forms bit 2, up to 16 words of 2 .. 8,
- * 12 or 16 states) without a beam and must outlive the session; a K-layer lattice, a bigram grammar, more than 16 words,
- * several graphs or a beam are GH_ERR_UNSUPPORTED (there is no other path).  It allocates 128 N B of state, 64 B of open
+ * 12 or 16 states) without a beam and must outlive the session; a K-layer lattice, a bigram grammar (that is
+ * gh_online_create_bigram's, below), more than 16 words, several graphs or a beam are GH_ERR_UNSUPPORTED.  It allocates 128 N B of state, 64 B of open
  * word and 64 ceil(max_frames / columns per decision word) B of history per stream (16 B per frame at N = 5).
  * max_frames is a hard capacity: a push that would take ANY of its streams past it is refused as a whole
  * (GH_ERR_INVALID) before anything is enqueued, and so is one with a stream named twice or out of range. */
@@ -766,6 +766,19 @@ int gh_online_commit_timed(gh_ctx* ctx, gh_online* on, int64_t n, const int64_t*
 int gh_online_tail_timed(gh_ctx* ctx, gh_online* on, int64_t n, const int64_t* ids /*[n] or NULL*/, double* end_cost, int32_t* best_end,
                          const int32_t* row_label, int32_t* labels, const int64_t* label_off /*[n+1]*/, int32_t* n_labels,
                          int32_t* out_begin /*like labels, or NULL*/);
+
+/* ------------------------------------------------ online decode with a bigram grammar
+ * The same session object over ONE graph in bigram form (gh_lattices_forms bit 5: the word loop with word-to-word costs, up
+ * to 16 words of 2 .. 8, 12 or 16 states, 16 without skip arcs) without a beam: the carried form of the bigram sweep.
+ * CONTRACT as gh_online_create: after k frames gh_online_result / gh_online_result_timed return bitwise what gh_viterbi /
+ * gh_viterbi_labels / gh_viterbi_labels_timed return for those k frames.  A loop graph (gh_online_create takes it), a
+ * K-layer lattice, a graph that is in no bigram form, several graphs or a beam are GH_ERR_UNSUPPORTED.  Per stream: 128 N B
+ * of state, 64 B of open record word and 64 ceil(max_frames / columns per record word) B of history (the records carry a
+ * 4-bit predecessor word: 64 B per 3 frames at N = 5, against 4 frames of the loop form).  max_frames is a hard capacity
+ * as in gh_online_create.  FULL HISTORY ONLY: there is no window variant, and gh_online_commit* / gh_online_tail* on such
+ * a session are GH_ERR_UNSUPPORTED (the settle walk does not read the wider records).  gh_online_push, gh_online_result*,
+ * gh_online_reset, gh_online_frames and gh_online_destroy serve it as they serve a loop session. */
+int gh_online_create_bigram(gh_ctx* ctx, const gh_lattices* lat, int64_t n_streams, int64_t max_frames, gh_online** out);
 
 /* ------------------------------------------------ online isolated-word recognition: A5 while the audio is still arriving
  * HMM.evaluate (hmm.py:126-135) of every word model, carried across the chunks of n_streams live utterances: the cost of a

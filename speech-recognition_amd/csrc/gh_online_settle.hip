@@ -326,6 +326,11 @@ extern "C" int gh_online_commit_timed(gh_ctx* ctx, gh_online* on, int64_t n, con
     GH_REQUIRE(ctx && on, "gh_online_commit: NULL argument");
     GH_REQUIRE(!out_begin || labels, "gh_online_commit_timed: out_begin needs labels");
     GH_REQUIRE(ctx == on->ctx, "gh_online_commit: the session belongs to another context");
+    if (on->bigram) {
+        gh_set_error("gh_online_commit: a bigram session has no settled prefix (its records need their own settle walk); gh_online_result gives the "
+                     "running hypothesis");
+        return GH_ERR_UNSUPPORTED;
+    }
     GH_REQUIRE(!labels || (row_label && label_off && n_new_labels), "gh_online_commit: labels need row_label, label_off and n_new_labels");
     std::vector<gh_settle_task> tasks;
     int rc = tasks_of(on, "gh_online_commit", n, ids, true, tasks);
@@ -398,6 +403,11 @@ extern "C" int gh_online_tail_timed(gh_ctx* ctx, gh_online* on, int64_t n, const
     GH_REQUIRE(ctx && on, "gh_online_tail: NULL argument");
     GH_REQUIRE(!out_begin || labels, "gh_online_tail_timed: out_begin needs labels");
     GH_REQUIRE(ctx == on->ctx, "gh_online_tail: the session belongs to another context");
+    if (on->bigram) {
+        gh_set_error("gh_online_tail: a bigram session has no settled prefix (its records need their own settle walk); gh_online_result gives the "
+                     "running hypothesis");
+        return GH_ERR_UNSUPPORTED;
+    }
     GH_REQUIRE(!labels || (row_label && label_off && n_labels), "gh_online_tail: labels need row_label, label_off and n_labels");
     std::vector<gh_settle_task> tasks;
     int rc = tasks_of(on, "gh_online_tail", n, ids, false, tasks);

@@ -20,22 +20,13 @@
 // capacity (gh_online_create) has a ring as long as its last word index, so nothing ever wraps and it writes the bytes it
 // always wrote; one created with a window (gh_online_create_window) holds `window` unsettled frames and one word of slack
 // for the word the anchor lies in (gh_online_settle.hip: what is settled, and why the frames before it are dead).
+//
+// The same session object serves the BIGRAM form (gh_online_create_bigram, on->bigram): push, result, reset, frames and
+// destroy below dispatch on it -- the carried sweep and the end kernel of gh_viterbi_bigram_online.hip, the back-trace of
+// gh_viterbi_bigram.hip -- with every host-side check unchanged.  Such a session keeps its full history: no window, no commit.
 #include "gh_online.h"
 #include "gh_viterbi.h"
 #include "gh_wave.h"
-
-struct gh_online_args {
-    const gh_layerform* lf;
-    const void* nll;
-    int S;
-    const gh_online_slot* slots;
-    int64_t n_slots;
-    double* prev;          // [n_streams][N][16]
-    uint32_t* open;        // [n_streams][16]
-    uint16_t* hist;        // decision words, stream k at k * hist_stride (uint16 units, as gh_layers_args::bp)
-    int64_t hist_stride;
-    int ring_words;        // word index i of a stream lives at i % ring_words
-};
 
 namespace {
 
@@ -208,29 +199,37 @@ int launch_online(gh_ctx* ctx, const gh_online_args& a, const gh_layerform& f, b
 }
 
 // a session with history for `frames` frames per stream: all a stream will ever take, or (window) its unsettled tail
-int online_create(gh_ctx* ctx, const gh_lattices* lat, int64_t n_streams, int64_t frames, bool window, gh_online** out) {
-    const char* const who = window ? "gh_online_create_window" : "gh_online_create";
+// (bigram: the graph must be in bigram form instead, gh_online_create_bigram; full history only)
+int online_create(gh_ctx* ctx, const gh_lattices* lat, int64_t n_streams, int64_t frames, bool window, bool bigram, gh_online** out) {
+    const char* const who = bigram ? "gh_online_create_bigram" : window ? "gh_online_create_window" : "gh_online_create";
     GH_REQUIRE(ctx && lat && out, "%s: NULL argument", who);
     *out = nullptr;
     GH_REQUIRE(n_streams >= 1 && n_streams <= 0x7fffffff, "%s: n_streams=%lld", who, (long long)n_streams);
     GH_REQUIRE(frames >= 1 && frames <= 0x7fffffff, "%s: %s=%lld", who, window ? "window_frames" : "max_frames", (long long)frames);
     const char* why = nullptr;
-    if (lat->L != 1 || lat->deferred_src) why = "several graphs (one word-loop graph serves all streams)";
+    if (lat->L != 1 || lat->deferred_src) why = "several graphs (one graph serves all streams)";
     else if (lat->beam > 0) why = "a rank beam is set on the graph";
-    else if (lat->bigram_ok) why = "a bigram grammar";
+    else if (bigram) {
+        if (lat->layers_ok && lat->h_layers.loop) why = "a word-loop graph (gh_online_create takes it)";
+        else if (lat->layers_ok) why = "a K-layer word lattice";
+        else if (!lat->bigram_ok) why = "a graph that is not in bigram form (more than 16 words, and 16 states with skip arcs, are not)";
+        else if (!gh_bigram_n_ok(lat->h_layers.N, lat->h_layers.skip)) why = "a word size the bigram sweep is not built for";
+    }
+    else if (lat->bigram_ok) why = "a bigram grammar (gh_online_create_bigram takes it, with full history)";
     else if (lat->layers_ok && !lat->h_layers.loop) why = "a K-layer word lattice";
     else if (!lat->layers_ok || lat->h_layers.loop != 1) why = "a graph that is not in loop form";
     else if (lat->h_layers.W > GH_LAYERS_ROWW) why = "more than 16 words";
     if (why) {
-        gh_set_error("%s: online decoding takes the word-loop grammar with up to %d words, not %s", who, GH_LAYERS_ROWW, why);
+        gh_set_error("%s: online decoding takes the %s grammar with up to %d words, not %s", who, bigram ? "bigram" : "word-loop",
+                     GH_LAYERS_ROWW, why);
         return GH_ERR_UNSUPPORTED;
     }
     GH_HIP(hipSetDevice(ctx->device));
     const gh_layerform& f = lat->h_layers;
     gh_online* on = new gh_online();
-    on->ctx = ctx; on->lat = lat; on->n_streams = n_streams;
+    on->ctx = ctx; on->lat = lat; on->bigram = bigram; on->n_streams = n_streams;
     // a window: whole decision words, one more for the word the anchor lies in; the stream itself ends with the 32-bit column
-    const int cpw = gh_loop_cpw(f.N, f.skip != 0);
+    const int cpw = bigram ? gh_bigram_cpw(f.N, f.skip != 0) : gh_loop_cpw(f.N, f.skip != 0);
     on->max_frames = window ? 0x7fffffff : frames;
     on->window = window ? frames : 0;
     on->ring_words = (int32_t)((frames + cpw - 1) / cpw + (window ? 1 : 0));
@@ -274,11 +273,15 @@ int gh_launch_online_end(gh_ctx* ctx, const gh_online* on, const int64_t* d_ids,
 
 // --------------------------------------------------------------------------------------------------------------- C ABI
 extern "C" int gh_online_create(gh_ctx* ctx, const gh_lattices* lat, int64_t n_streams, int64_t max_frames, gh_online** out) {
-    return online_create(ctx, lat, n_streams, max_frames, false, out);
+    return online_create(ctx, lat, n_streams, max_frames, false, false, out);
+}
+
+extern "C" int gh_online_create_bigram(gh_ctx* ctx, const gh_lattices* lat, int64_t n_streams, int64_t max_frames, gh_online** out) {
+    return online_create(ctx, lat, n_streams, max_frames, false, true, out);
 }
 
 extern "C" int gh_online_create_window(gh_ctx* ctx, const gh_lattices* lat, int64_t n_streams, int64_t window_frames, gh_online** out) {
-    return online_create(ctx, lat, n_streams, window_frames, true, out);
+    return online_create(ctx, lat, n_streams, window_frames, true, false, out);
 }
 
 extern "C" void gh_online_destroy(gh_online* on) {
@@ -354,7 +357,7 @@ extern "C" int gh_online_push(gh_ctx* ctx, gh_online* on, const gh_batch* b, con
     GH_REQUIRE(b->nll, "gh_online_push: gh_loglik has not been run on this batch");
     GH_REQUIRE(on->lat->lat[0].max_state < b->nll_S, "gh_online_push: the graph uses state %d but the model has %d", on->lat->lat[0].max_state,
                b->nll_S);
-    GH_REQUIRE(gh_seq_n_ok(f.N), "gh_online_push: loop form with %d states per word", f.N);
+    GH_REQUIRE(gh_seq_n_ok(f.N), "gh_online_push: %s form with %d states per word", on->bigram ? "bigram" : "loop", f.N);
     GH_HIP(hipSetDevice(ctx->device));
     // longest chunks first: the four rows of a wave then end close to each other
     std::stable_sort(slots.begin(), slots.end(), [](const gh_online_slot& x, const gh_online_slot& y) { return x.count > y.count; });
@@ -367,7 +370,7 @@ extern "C" int gh_online_push(gh_ctx* ctx, gh_online* on, const gh_batch* b, con
     memset(&a, 0, sizeof a);
     a.lf = on->lat->d_layers; a.nll = b->nll; a.S = b->nll_S; a.slots = on->d_slots; a.n_slots = (int64_t)slots.size();
     a.prev = on->d_prev; a.open = on->d_open; a.hist = on->d_hist; a.hist_stride = on->hist_stride; a.ring_words = on->ring_words;
-    const int rc = launch_online(ctx, a, f, b->dtype == GH_F64);
+    const int rc = on->bigram ? gh_launch_online_bigram(ctx, a, f, b->dtype == GH_F64) : launch_online(ctx, a, f, b->dtype == GH_F64);
     if (rc) return rc;
     for (const gh_online_slot& s : slots) on->frames[(size_t)s.stream] += s.count;
     return GH_OK;
@@ -424,7 +427,8 @@ extern "C" int gh_online_result_timed(gh_ctx* ctx, gh_online* on, int64_t n, con
         GH_HIP(hipMemcpyAsync(d_labeloff, label_off, (size_t)(n + 1) * 8, hipMemcpyHostToDevice, st));
     }
     if (path) GH_HIP(hipMemcpyAsync(d_pathoff, path_off, (size_t)(n + 1) * 8, hipMemcpyHostToDevice, st));
-    rc = gh_launch_online_end(ctx, on, d_ids, d_uttoff, n, d_endcost, d_best);
+    rc = on->bigram ? gh_launch_online_bigram_end(ctx, on, d_ids, d_uttoff, n, d_endcost, d_best)
+                    : gh_launch_online_end(ctx, on, d_ids, d_uttoff, n, d_endcost, d_best);
     if (rc) return rc;
     // the one-shot decode's own back-trace on the history: utterance i = stream ids[i], its decision words at bp_off[i]
     gh_layers_args c;
@@ -433,13 +437,14 @@ extern "C" int gh_online_result_timed(gh_ctx* ctx, gh_online* on, int64_t n, con
     c.utt_off = d_uttoff; c.bp = on->d_hist; c.bp_off = d_bpoff; c.best_end = d_best; c.flag = d_flag;
     if (path) {
         c.path = d_path; c.path_off = d_pathoff; c.path_len = d_pathlen;
-        rc = gh_launch_lattice_backtrace(ctx, c, f, 0, n);
+        rc = on->bigram ? gh_launch_bigram_backtrace(ctx, c, f, 0, n) : gh_launch_lattice_backtrace(ctx, c, f, 0, n);
         if (rc) return rc;
     }
     if (labels) {
         c.row_label = d_rowlabel; c.labels = d_labels; c.label_off = d_labeloff; c.n_labels = d_nlabels;
         if (d_begins) c.path = d_begins;                    // timed label mode: the begins go where a path launch has its path
-        rc = gh_launch_lattice_backtrace(ctx, c, f, 0, n, d_begins != nullptr);
+        rc = on->bigram ? gh_launch_bigram_backtrace(ctx, c, f, 0, n, d_begins != nullptr)
+                        : gh_launch_lattice_backtrace(ctx, c, f, 0, n, d_begins != nullptr);
         if (rc) return rc;
     }
     int flag = 0;

@@ -176,6 +176,7 @@ SIGNATURES = {
     "gh_online_result_timed": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, _c_i64p, _c_f64p, _c_i32p, _c_i32p, _c_i32p, _c_i64p, _c_i32p,
                                    _c_i32p, _c_i64p, _c_i32p, _c_i32p]),
     "gh_online_create_window": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.POINTER(C.c_void_p)]),
+    "gh_online_create_bigram": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.POINTER(C.c_void_p)]),
     "gh_online_commit": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, _c_i64p, _c_i64p, _c_i32p, _c_i32p, _c_i64p, _c_i32p]),
     "gh_online_commit_timed": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, _c_i64p, _c_i64p, _c_i32p, _c_i32p, _c_i64p, _c_i32p, _c_i32p]),
     "gh_online_tail": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, _c_i64p, _c_f64p, _c_i32p, _c_i32p, _c_i32p, _c_i64p, _c_i32p]),
@@ -1616,6 +1617,32 @@ class OnlineSession:
             self.close()
         except Exception:
             pass
+
+
+class OnlineBigramSession(OnlineSession):
+    """Online decode over ONE graph in bigram form (gh_online_create_bigram): the `OnlineSession` of a grammar with
+    word-to-word costs.  `push`, `result` (labels, begins, paths), `reset` and `frames` are the parent's, and `result` is
+    bitwise the one-shot bigram decode of the frames a stream has taken.  Full history only (`max_frames`); `commit` and
+    `tail` raise `Unsupported` -- there is no settled prefix yet.  A loop graph, a K-layer lattice, a beam or a word size
+    the bigram sweep is not built for raise `Unsupported`."""
+
+    def __init__(self, ctx, lat, n_streams, max_frames):
+        self.ctx, self.lat = ctx, lat
+        self.n_streams, self.max_frames, self.window = int(n_streams), int(max_frames), None
+        h = C.c_void_p()
+        rc = ctx.lib.gh_online_create_bigram(ctx.h, lat.h, self.n_streams, self.max_frames, C.byref(h))
+        if rc == GH_ERR_UNSUPPORTED:
+            raise Unsupported(ctx.lib.gh_last_error().decode("utf-8", "replace"))
+        _check(ctx.lib, rc)
+        self.h = h
+        self.n_end, self.R = int(lat.n_end[0]), int(lat.R[0])
+        self._nlev = lat.path_cap(0, 1)
+
+    def commit(self, ids=None, row_label=None, max_labels=None, want_begin=False):
+        raise Unsupported("a bigram session has no settled prefix: result() gives the running hypothesis")
+
+    def tail(self, ids=None, row_label=None, max_labels=None, want_begin=False):
+        raise Unsupported("a bigram session has no settled prefix: result() gives the running hypothesis")
 
 
 class WordStreamSession:

@@ -439,6 +439,15 @@ class ContinuousDecoder:
         return OnlineDecoder(self, n_streams, max_frames, window, frontend, endpointer, times)
 
 
+    def online_bigram(self, n_streams, max_frames, frontend=None, endpointer=None, times=False):
+        """An `OnlineBigramDecoder` of `n_streams` live utterances sharing this decoder's packed mixtures and bigram graph
+        (grammar="bigram" only: anything else raises `_hip.Unsupported` before the GPU is touched).  `max_frames`:
+        utterances of up to that many frames, whole history kept -- there is no `window=` for a bigram grammar yet.
+        frontend / endpointer / times: as in `online`.  The language-model costs (`bigram`, `initial`, `lm_scale`) are
+        in the graph; nothing is passed again."""
+        return OnlineBigramDecoder(self, n_streams, max_frames, frontend, endpointer, times)
+
+
 class _OnlineStreams:
     """The stream plumbing `OnlineDecoder` and `OnlineWordRecognizer` share: `n_streams` live utterances that take feature
     frames (`push`, `push_batch`), audio through a `StreamingFrontend` (`push_audio`) or recordings through a
@@ -665,7 +674,8 @@ class OnlineDecoder(_OnlineStreams):
 
     def __init__(self, decoder, n_streams, max_frames=None, window=None, frontend=None, endpointer=None, times=False):
         if decoder.grammar != "loop":
-            raise _hip.Unsupported("online decoding takes the word-loop grammar (grammar='loop'), not %r" % (decoder.grammar,))
+            raise _hip.Unsupported("online decoding takes the word-loop grammar (grammar='loop'), not %r%s"
+                                   % (decoder.grammar, " (online_bigram takes it)" if decoder.grammar == "bigram" else ""))
         if (max_frames is None) == (window is None):
             raise ValueError("exactly one of max_frames and window must be given")
         if int(n_streams) < 1 or int(window if max_frames is None else max_frames) < 1:
@@ -678,6 +688,9 @@ class OnlineDecoder(_OnlineStreams):
             self.session = _hip.OnlineSession(decoder.ctx, decoder.lat, self.n_streams, self.max_frames)
         else:
             self.session = _hip.OnlineSession(decoder.ctx, decoder.lat, self.n_streams, window=self.window)
+        self._init_words(decoder, times)
+
+    def _init_words(self, decoder, times):
         self._settled = np.zeros(self.n_streams, dtype=np.int64)      # settled frames (anchor column + 1) of every stream
         self._words = [[] for _ in range(self.n_streams)]             # ... and its settled words
         self.times = bool(times)
@@ -795,6 +808,42 @@ class OnlineDecoder(_OnlineStreams):
         out = self.result(ids, want_path=want_path)
         self._reset_utterance(None if ids is None else self._ids(ids, distinct=False))
         return out
+
+
+class OnlineBigramDecoder(OnlineDecoder):
+    """`OnlineDecoder` for a decoder with a bigram grammar: the same streams, the same `push` / `push_batch` /
+    `push_audio` / `push_recording` / `result` / `finish` / `reset` / `frames` and word times, over the carried bigram
+    sweep (gh_online_create_bigram).  `result` gives at any time what `decode_batch` gives for the frames pushed so far.
+
+        dec = ContinuousDecoder(models, grammar="bigram", bigram=BigramModel(...), lm_scale=8.0)
+        on = dec.online_bigram(n_streams=64, max_frames=3000, times=True)
+        on.push([3, 7], [frames_of_3, frames_of_7])
+        words, info = on.result([3]); info["begins"][0]
+
+    It has the surface of an `OnlineDecoder` made with `max_frames=`: the whole history is kept and `max_frames` is a hard
+    capacity.  NOT offered yet: `window=` and the settled prefix -- `commit`, `settled` and `settled_times` raise
+    `_hip.Unsupported` (the settle walk needs its own kernels for the bigram records)."""
+
+    def __init__(self, decoder, n_streams, max_frames, frontend=None, endpointer=None, times=False):
+        if decoder.grammar != "bigram":
+            raise _hip.Unsupported("online_bigram takes the bigram grammar (grammar='bigram'), not %r%s"
+                                   % (decoder.grammar, " (online takes it)" if decoder.grammar == "loop" else ""))
+        if max_frames is None or int(n_streams) < 1 or int(max_frames) < 1:
+            raise ValueError("n_streams and max_frames must be positive")
+        self._attach(decoder.ctx, decoder.dtype, decoder.gmm, n_streams, frontend, endpointer)
+        self.decoder = decoder
+        self.max_frames, self.window = int(max_frames), None
+        self.session = _hip.OnlineBigramSession(decoder.ctx, decoder.lat, self.n_streams, self.max_frames)
+        self._init_words(decoder, times)                              # (nothing settles: the settled words stay empty)
+
+    def commit(self, ids=None, want_times=False):
+        raise _hip.Unsupported("a bigram decoder has no settled prefix: result() gives the running hypothesis")
+
+    def settled(self, ids=None):
+        raise _hip.Unsupported("a bigram decoder has no settled prefix: result() gives the running hypothesis")
+
+    def settled_times(self, ids=None):
+        raise _hip.Unsupported("a bigram decoder has no settled prefix: result() gives the running hypothesis")
 
 
 class OnlineWordRecognizer(_OnlineStreams):
