@@ -72,6 +72,7 @@ struct gh_chain_args {
     int* flag;
     int unit_chains;          // lane = chain form: chains per utterance (R / rows per chain)
     int64_t n_slots;          // lane = chain form: launch slots of this launch (slot0 .. slot0 + n_slots - 1)
+    int64_t n_lane_waves;     // lane = chain form: grid positions of this launch (the grid may be smaller: strided walk)
 };
 int gh_launch_viterbi_chain(gh_ctx* ctx, const gh_chain_args& a, int64_t u_begin, int64_t n_utts, bool f64,
                             bool want_bp, bool want_costs, bool skip);

@@ -10,6 +10,8 @@
 // strided walk through the resident [N,S] matrix, prefetched PF columns ahead in a register
 // ring.  A column is ~15 VALU instructions, so the kernel runs at the rate HBM delivers the
 // likelihood matrix.  Back-pointers are 1 byte per cell (which of the three arcs won).
+#include <stdlib.h>
+#include <string.h>
 #include "gh_internal.h"
 #include "gh_viterbi.h"
 #include "gh_wave.h"
@@ -17,6 +19,12 @@
 namespace {
 
 constexpr int PF = 8;  // emission prefetch depth (columns)
+// The lane = chain form exists with two ring depths (template parameter LPF): PF, and the shallow ring LANE_PF with which
+// the headline instantiation is allocated 80 registers and fits beside two likelihood waves (see the kernel).
+#ifndef GH_VL_PF
+#define GH_VL_PF 2
+#endif
+constexpr int LANE_PF = GH_VL_PF;
 
 template <typename ET, bool WANT_BP, bool WANT_COSTS, bool SKIP>
 __global__ __launch_bounds__(64) void viterbi_chain_kernel(gh_chain_args a) {
@@ -112,10 +120,11 @@ __global__ __launch_bounds__(64) void viterbi_chain_kernel(gh_chain_args a) {
 // definition of a chain and is left out.  Column 0 (start rows take e, the others +inf) is peeled.
 // SELECT (no back-pointers and the whole utterance in one wave): the end selection of chain_end_select_kernel happens
 // here, on the end costs parked in LDS.
-template <typename ET, int N, bool WANT_BP, bool WANT_COSTS, bool SKIP>
-__global__ __launch_bounds__(64) void viterbi_chain_lanes_kernel(gh_chain_args a) {
+// chain_lanes_wave: what one wave does for position `wv` of the one-wave-per-group grid (s_end: 64 * N doubles of LDS when
+// SELECT).  The kernel below calls it once (grid = every position) or in a strided loop (a capped grid).
+template <typename ET, int N, bool WANT_BP, bool WANT_COSTS, bool SKIP, int LPF>
+__device__ __forceinline__ void chain_lanes_wave(const gh_chain_args& a, const int64_t wv, double* s_end) {
     constexpr bool SELECT = !WANT_BP;
-    __shared__ double s_end[SELECT ? 64 * N : 1];
     const int lane = threadIdx.x;
     const int C = a.unit_chains;               // chains per utterance
     const bool one_wave = C <= 64;             // (then SELECT applies)
@@ -126,13 +135,13 @@ __global__ __launch_bounds__(64) void viterbi_chain_lanes_kernel(gh_chain_args a
         const int upw = 64 / C;
         ul = lane / C;
         chain = lane - ul * C;
-        slot = a.slot0 + (int64_t)blockIdx.x * upw + ul;
+        slot = a.slot0 + wv * upw + ul;
         act = ul < upw && slot < a.slot0 + a.n_slots;
-        if (!act) { ul = 0; chain = 0; slot = a.slot0 + (int64_t)blockIdx.x * upw; }   // an idle lane shadows lane 0: same loads, no stores
+        if (!act) { ul = 0; chain = 0; slot = a.slot0 + wv * upw; }   // an idle lane shadows lane 0: same loads, no stores
     } else {
         const int wpu = (C + 63) >> 6;
-        slot = a.slot0 + blockIdx.x / wpu;
-        chain = (blockIdx.x % wpu) * 64 + lane;
+        slot = a.slot0 + wv / wpu;
+        chain = (int)(wv % wpu) * 64 + lane;
         act = chain < C;
         if (!act) chain = 0;
     }
@@ -185,7 +194,7 @@ __global__ __launch_bounds__(64) void viterbi_chain_lanes_kernel(gh_chain_args a
         for (int i = 0; i < N; ++i) prev[i] = INF;
     }
 
-    ET ring[PF][N];
+    ET ring[LPF][N];
     const ET* lp = ep + S;
 
     auto column = [&](const ET (&ev)[N]) {
@@ -228,40 +237,46 @@ __global__ __launch_bounds__(64) void viterbi_chain_lanes_kernel(gh_chain_args a
     // The loop without guards has its own ring fill in front of it: reached over the guarded fill, the wait for a ring slot
     // at the top of the loop becomes a wait for every load in flight (the compiler cannot count loads behind branches).
     int t = 1;
-    if (1 + 2 * PF <= tmin) {
+#ifdef GH_VL_PRIO
+    __builtin_amdgcn_s_setprio(3);
+#endif
+    if (1 + 2 * LPF <= tmin) {
 #pragma unroll
-        for (int k = 0; k < PF; ++k) {
+        for (int k = 0; k < LPF; ++k) {
 #pragma unroll
             for (int i = 0; i < N; ++i) ring[k][i] = lp[i];
             lp += S;
         }
-        do {                                        // every lane: columns t .. t+PF-1 exist, loads t+PF .. t+2PF-1 are inside
+        do {                                        // every lane: columns t .. t+LPF-1 exist, loads t+LPF .. t+2LPF-1 are inside
 #pragma unroll
-            for (int k = 0; k < PF; ++k) {
+            for (int k = 0; k < LPF; ++k) {
                 column(ring[k]);      // (consumed before the slot's refill is issued: the ring stays in its registers)
 #pragma unroll
                 for (int i = 0; i < N; ++i) ring[k][i] = lp[i];
                 lp += S;
             }
-            t += PF;
-        } while (t + 2 * PF <= tmin);
+            t += LPF;
+        } while (t + 2 * LPF <= tmin);
     } else {
 #pragma unroll
-        for (int k = 0; k < PF; ++k) {
+        for (int k = 0; k < LPF; ++k) {
 #pragma unroll
             for (int i = 0; i < N; ++i) ring[k][i] = (1 + k < T) ? lp[i] : ET(0);
             lp += S;
         }
     }
-    for (; t < tmax; t += PF) {
+    for (; t < tmax; t += LPF) {
 #pragma unroll
-        for (int k = 0; k < PF; ++k) {
+        for (int k = 0; k < LPF; ++k) {
             if (t + k < T) column(ring[k]);
 #pragma unroll
-            for (int i = 0; i < N; ++i) ring[k][i] = (t + k + PF < T) ? lp[i] : ET(0);
+            for (int i = 0; i < N; ++i) ring[k][i] = (t + k + LPF < T) ? lp[i] : ET(0);
             lp += S;
         }
     }
+#ifdef GH_VL_PRIO
+    __builtin_amdgcn_s_setprio(0);
+#endif
 
     // end costs: every end row knows its slot in the graph's end list
     if (T > 0) {
@@ -287,6 +302,26 @@ __global__ __launch_bounds__(64) void viterbi_chain_lanes_kernel(gh_chain_args a
             a.best_end[u] = bi;
             if (a.path_len) a.path_len[u] = 0;
         }
+    }
+}
+
+// Registers of the headline instantiation (fp64, n = 5, no back-pointers, no skip arcs) with the shallow ring: a SIMD has
+// 512, two waves of loglik_mfma_kernel<double,20,8> hold 2 x 216, so a decode wave of at most 80 starts beside them
+// instead of waiting for one of them to retire and then keeping its successor out.  waves_per_eu(6) is that
+// budget (512 / 6 -> 80); tools/headline_registers.py checks the sum and that nothing spills.  1 = the default.
+template <typename ET, int N, bool WANT_BP, bool WANT_COSTS, bool SKIP, int LPF>
+__global__ __launch_bounds__(64)
+__attribute__((amdgpu_waves_per_eu((LPF == LANE_PF && sizeof(ET) == 8 && N == 5 && !WANT_BP && !SKIP) ? 6 : 1)))
+void viterbi_chain_lanes_kernel(gh_chain_args a) {
+    constexpr bool SELECT = !WANT_BP;
+    __shared__ double s_end[SELECT ? 64 * N : 1];
+    if (LPF != LANE_PF) {                   // "alone": the grid is every position (the walk below costs ~25 registers)
+        chain_lanes_wave<ET, N, WANT_BP, WANT_COSTS, SKIP, LPF>(a, blockIdx.x, s_end);
+        return;
+    }
+    for (int64_t wv = blockIdx.x; wv < a.n_lane_waves; wv += gridDim.x) {
+        chain_lanes_wave<ET, N, WANT_BP, WANT_COSTS, SKIP, LPF>(a, wv, s_end);
+        if (SELECT) __syncthreads();        // (the end selection has read s_end before the next position writes it)
     }
 }
 
@@ -379,9 +414,24 @@ int gh_launch_viterbi_chain_lanes(gh_ctx* ctx, const gh_chain_args& a, int unit,
     b.unit_chains = a.R / unit;
     const int C = b.unit_chains;
     const int64_t n_waves = C <= 64 ? (n_utts + 64 / C - 1) / (64 / C) : n_utts * ((C + 63) / 64);
-    dim3 grid((unsigned)n_waves), blk(64);
+    b.n_lane_waves = n_waves;
+    // Two forms of the launch.  "alone": the ring of PF columns and one wave per position.  "beside": the shallow ring and
+    // at most one wave per SIMD, the waves walking the positions in a strided loop -- the form for a decode that runs
+    // under another stream's likelihood kernel (two batches in flight): it starts in the registers two likelihood waves
+    // leave free and never puts a second decode wave on a SIMD.  Measured at the headline's 1.5 waves per SIMD (DESIGN
+    // section 6); taken from half a wave to two waves per SIMD, outside of that the launch stays as it was.
+    // GMMHMM_CHAIN_FORM=alone|beside and GMMHMM_CHAIN_WAVES=n (the cap of "beside") override, both read at every call.
+    const int64_t simds = 4 * (int64_t)(ctx->n_cu > 0 ? ctx->n_cu : 256);
+    bool beside = 2 * n_waves > simds && n_waves <= 2 * simds;
+    if (const char* e = getenv("GMMHMM_CHAIN_FORM")) beside = !strcmp(e, "beside") ? true : !strcmp(e, "alone") ? false : beside;
+    int64_t cap = beside ? simds : n_waves;
+    if (const char* e = getenv("GMMHMM_CHAIN_WAVES")) { const long v = atol(e); if (v > 0 && beside) cap = v; }
+    dim3 grid((unsigned)(n_waves < cap ? n_waves : cap)), blk(64);
+    if (const char* e = getenv("GMMHMM_HOST_TRACE"))
+        if (atoi(e)) fprintf(stderr, "[gh_viterbi chain lanes] %s grid %u of %lld positions\n", beside ? "beside" : "alone", grid.x, (long long)n_waves);
     if (unit < 3) skip = false;   // (no r-2 arc inside a chain of two rows)
-#define GH_VL(ET, NN, BP, CO, SK) hipLaunchKernelGGL((viterbi_chain_lanes_kernel<ET, NN, BP, CO, SK>), grid, blk, 0, ctx->stream, b)
+#define GH_VL_L(ET, NN, BP, CO, SK, LPF) hipLaunchKernelGGL((viterbi_chain_lanes_kernel<ET, NN, BP, CO, SK, LPF>), grid, blk, 0, ctx->stream, b)
+#define GH_VL(ET, NN, BP, CO, SK) do { if (beside) GH_VL_L(ET, NN, BP, CO, SK, LANE_PF); else GH_VL_L(ET, NN, BP, CO, SK, PF); } while (0)
 #define GH_VL_S(ET, NN, BP, CO) do { if (NN >= 3 && skip) GH_VL(ET, NN, BP, CO, (NN >= 3)); else GH_VL(ET, NN, BP, CO, false); } while (0)
 #define GH_VL_T(ET, NN) do { if (want_costs) GH_VL_S(ET, NN, true, true); else if (want_bp) GH_VL_S(ET, NN, true, false); else GH_VL_S(ET, NN, false, false); } while (0)
 #define GH_VL_N(ET) switch (unit) { case 1: GH_VL_T(ET, 1); break; case 2: GH_VL_T(ET, 2); break; case 3: GH_VL_T(ET, 3); break; \
@@ -392,6 +442,7 @@ int gh_launch_viterbi_chain_lanes(gh_ctx* ctx, const gh_chain_args& a, int unit,
 #undef GH_VL_T
 #undef GH_VL_S
 #undef GH_VL
+#undef GH_VL_L
     GH_HIP(hipGetLastError());
     if (selected) *selected = !want_bp && !want_costs && C <= 64;
     return GH_OK;
