@@ -29,6 +29,7 @@
 //     a wave walks several blocks with the operand ring kept primed (closed loop over the tiles),
 //     optionally driven by a block table that restricts every utterance to its own state range
 //     (gh_loglik_subset).
+#include <type_traits>
 #include "gh_internal.h"
 #include "gh_wave.h"
 
@@ -231,7 +232,12 @@ template <typename T> __device__ __forceinline__ global_ptr<T> uniform_ptr(const
 // write to a per-lane dummy slot behind the tile.  When a state spans two or four lane groups
 // every group ends up with the same (max, sum) pair, so the even group finishes column tile 0
 // and the odd group column tile 1: ONE logarithm per lane instead of two.
-template <typename T, typename V, int MP, bool FE = false>
+// CHK: test the state index against S before the store.  Only the LAST tile of the model can hold padding states
+// (n_tiles = ceil(S * M_pad / 16): every state of an earlier tile is below S; with several tiles per state n_tiles =
+// S * tiles_per_state and no tile has any), so the tile loop runs without the test -- the compare, a select and part
+// of the slot address leave the pipe the MFMAs share: 155 -> 151 / 152 vector instructions per tile in <double,20,8>,
+// 61 -> 38 for M_pad = 1 -- and only the epilogue after it, which may see the model's last tile, keeps it.
+template <typename T, typename V, int MP, bool FE = false, bool CHK = true>
 __device__ __forceinline__ void tile_epilogue(const V& acc0, const V& acc1, int t, int f, int q, int S, int RS,
                                               int chunk_s0, int tiles_per_state, T* lds, T* dummy,
                                               const double* tab, T (&run_mx)[2], T (&run_sm)[2], T inf_below, const LseK& k) {
@@ -245,7 +251,7 @@ __device__ __forceinline__ void tile_epilogue(const V& acc0, const V& acc1, int 
             T* orow = c ? orow1 : orow0;
 #pragma unroll
             for (int r = 0; r < 4; ++r)
-                *((s + r < S) ? orow + s + r : dummy) = (acc[r] < inf_below) ? T(INFINITY) : acc[r] * -Dom<T>::inv_k;
+                *((!CHK || s + r < S) ? orow + s + r : dummy) = (acc[r] < inf_below) ? T(INFINITY) : acc[r] * -Dom<T>::inv_k;
         }
     } else if (MP == 2) {
         const int s = 8 * t + 2 * q;
@@ -258,23 +264,23 @@ __device__ __forceinline__ void tile_epilogue(const V& acc0, const V& acc1, int 
                 const T x0 = acc[2 * h], x1 = acc[2 * h + 1];
                 const T m = vmax(x0, x1);
                 const T e = exp2s(x0 - m, tab, k.e3) + exp2s(x1 - m, tab, k.e3);
-                *((s + h < S) ? orow + s + h : dummy) = nll_of<T>(m, e, tab, inf_below, k);
+                *((!CHK || s + h < S) ? orow + s + h : dummy) = nll_of<T>(m, e, tab, inf_below, k);
             }
         }
 #ifdef GH_MF_NOEPI  // diagnostic build: MFMAs + loads only (tools/variant_bench.sh)
     } else if (MP <= 16) {
         const int s = (16 / MP) * t + q / (MP / 4);
-        *(((q & (MP / 4 - 1)) == 0 && s < S) ? orow0 + s : dummy) = -((acc0[0] + acc0[1]) + (acc0[2] + acc0[3]));
-        *(((q & (MP / 4 - 1)) == 0 && s < S) ? orow1 + s : dummy) = -((acc1[0] + acc1[1]) + (acc1[2] + acc1[3]));
+        *(((q & (MP / 4 - 1)) == 0 && (!CHK || s < S)) ? orow0 + s : dummy) = -((acc0[0] + acc0[1]) + (acc0[2] + acc0[3]));
+        *(((q & (MP / 4 - 1)) == 0 && (!CHK || s < S)) ? orow1 + s : dummy) = -((acc1[0] + acc1[1]) + (acc1[2] + acc1[3]));
 #endif
     } else if (FE && MP == 4) {
         if constexpr (FE) {
             double mx; float sm;
             const int s = 4 * t + q;
             tile_lse_fe<V>(acc0, 1, mx, sm);
-            *((s < S) ? orow0 + s : dummy) = nll_of_fe(mx, sm, inf_below);
+            *((!CHK || s < S) ? orow0 + s : dummy) = nll_of_fe(mx, sm, inf_below);
             tile_lse_fe<V>(acc1, 1, mx, sm);
-            *((s < S) ? orow1 + s : dummy) = nll_of_fe(mx, sm, inf_below);
+            *((!CHK || s < S) ? orow1 + s : dummy) = nll_of_fe(mx, sm, inf_below);
         }
     } else if (FE && MP <= 16) {
         if constexpr (FE) {
@@ -285,7 +291,7 @@ __device__ __forceinline__ void tile_epilogue(const V& acc0, const V& acc1, int 
             const bool odd = q & 1;
             const int s = (16 / MP) * t + q / width;
             const double v = nll_of_fe(odd ? mx1 : mx0, odd ? sm1 : sm0, inf_below);
-            *(((q & (width - 1)) < 2 && s < S) ? (odd ? orow1 : orow0) + s : dummy) = v;
+            *(((q & (width - 1)) < 2 && (!CHK || s < S)) ? (odd ? orow1 : orow0) + s : dummy) = v;
         }
     } else if (FE) {
         if constexpr (FE) {
@@ -303,7 +309,7 @@ __device__ __forceinline__ void tile_epilogue(const V& acc0, const V& acc1, int 
             }
             const bool odd = q & 1;
             const double v = nll_of_fe(odd ? run_mx[1] : run_mx[0], (float)(odd ? run_sm[1] : run_sm[0]), inf_below);
-            *((last && q < 2 && s < S) ? (odd ? orow1 : orow0) + s : dummy) = v;
+            *((last && q < 2) ? (odd ? orow1 : orow0) + s : dummy) = v;
 #pragma unroll
             for (int c = 0; c < 2; ++c) {
                 run_mx[c] = last ? Dom<T>::off : run_mx[c];
@@ -314,9 +320,9 @@ __device__ __forceinline__ void tile_epilogue(const V& acc0, const V& acc1, int 
         T mx, sm;
         const int s = 4 * t + q;
         tile_lse<T, V>(acc0, 1, mx, sm, tab, k);
-        *((s < S) ? orow0 + s : dummy) = nll_of<T>(mx, sm, tab, inf_below, k);
+        *((!CHK || s < S) ? orow0 + s : dummy) = nll_of<T>(mx, sm, tab, inf_below, k);
         tile_lse<T, V>(acc1, 1, mx, sm, tab, k);
-        *((s < S) ? orow1 + s : dummy) = nll_of<T>(mx, sm, tab, inf_below, k);
+        *((!CHK || s < S) ? orow1 + s : dummy) = nll_of<T>(mx, sm, tab, inf_below, k);
     } else if (MP <= 16) {
         constexpr int width = MP / 4;  // lane groups per state: 2 or 4
         // The even group finishes column tile 0, the odd group column tile 1, so both butterflies run on the PAIR of
@@ -332,7 +338,7 @@ __device__ __forceinline__ void tile_epilogue(const V& acc0, const V& acc1, int 
         const bool odd = q & 1;
         const int s = (16 / MP) * t + q / width;
         const T v = nll_of<T>(mxs, sm, tab, inf_below, k);
-        *(((q & (width - 1)) < 2 && s < S) ? (odd ? orow1 : orow0) + s : dummy) = v;
+        *(((q & (width - 1)) < 2 && (!CHK || s < S)) ? (odd ? orow1 : orow0) + s : dummy) = v;
     } else {
         const bool last = (t + 1) % tiles_per_state == 0;
         const int s = t / tiles_per_state;
@@ -348,7 +354,7 @@ __device__ __forceinline__ void tile_epilogue(const V& acc0, const V& acc1, int 
         }
         const bool odd = q & 1;
         const T v = nll_of<T>(odd ? run_mx[1] : run_mx[0], odd ? run_sm[1] : run_sm[0], tab, inf_below, k);
-        *((last && q < 2 && s < S) ? (odd ? orow1 : orow0) + s : dummy) = v;
+        *((last && q < 2) ? (odd ? orow1 : orow0) + s : dummy) = v;
 #pragma unroll
         for (int c = 0; c < 2; ++c) {
             run_mx[c] = last ? Dom<T>::off : run_mx[c];
@@ -573,8 +579,9 @@ __global__ __launch_bounds__(64, (sizeof(T) == 4 ? 3 : 1)) void loglik_mfma_kern
 #endif
         // Two tiles per iteration with the accumulator pairs swapping roles: the epilogue of tile t-1 is scheduled
         // with the MFMAs of tile t without copying accumulators (16 v_mov per tile otherwise).
-        auto epi = [&](const V& e0, const V& e1, int t) {
-            tile_epilogue<T, V, MP, FE>(e0, e1, t, f, q, S, RS, chunk_s0, tiles_per_state, lds, dummy, tab, run_mx, run_sm, inf_below, lse_k);
+        // (chk: std::true_type for the block's last tile, the only one that may hold padding states -- see tile_epilogue)
+        auto epi = [&](const V& e0, const V& e1, int t, auto chk) {
+            tile_epilogue<T, V, MP, FE, decltype(chk)::value>(e0, e1, t, f, q, S, RS, chunk_s0, tiles_per_state, lds, dummy, tab, run_mx, run_sm, inf_below, lse_k);
 #pragma unroll
             for (int i = 0; i < (GH_MF_SGB ? 2 * KS : 0); ++i) {   // (forced MFMA / VALU interleave: measured slower)
                 __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
@@ -591,27 +598,27 @@ __global__ __launch_bounds__(64, (sizeof(T) == 4 ? 3 : 1)) void loglik_mfma_kern
             int t = tb + 1;
             for (; t + 1 < te; t += 2) {
                 mfma_tile(t, r0, r1, c_b, c_a);
-                epi(p0, p1, t - 1);
+                epi(p0, p1, t - 1, std::false_type());
                 mfma_tile(t + 1, p0, p1, c_a, c_b);
-                epi(r0, r1, t);
+                epi(r0, r1, t, std::false_type());          // (t + 1 < te: not the last tile)
             }
             if (t < te) {
                 mfma_tile(t, r0, r1, c_b, c_a);
-                epi(p0, p1, t - 1);
-                epi(r0, r1, t);
+                epi(p0, p1, t - 1, std::false_type());
+                epi(r0, r1, t, std::true_type());
             } else {
-                epi(p0, p1, te - 1);
+                epi(p0, p1, te - 1, std::true_type());
                 if (MULTI) c_a = c_b;
             }
         } else {   // fp32: the copying loop schedules better (measured 0.65 vs 0.67 ms)
             for (int t = tb + 1; t < te; ++t) {
                 mfma_tile(t, r0, r1, c_b, c_a);
-                epi(p0, p1, t - 1);
+                epi(p0, p1, t - 1, std::false_type());
                 p0 = r0;
                 p1 = r1;
                 c_b = c_a;
             }
-            epi(p0, p1, te - 1);
+            epi(p0, p1, te - 1, std::true_type());
             if (MULTI) c_a = c_b;
         }
 #ifdef GH_MF_TIMING
