@@ -775,10 +775,21 @@ int gh_online_tail_timed(gh_ctx* ctx, gh_online* on, int64_t n, const int64_t* i
  * K-layer lattice, a graph that is in no bigram form, several graphs or a beam are GH_ERR_UNSUPPORTED.  Per stream: 128 N B
  * of state, 64 B of open record word and 64 ceil(max_frames / columns per record word) B of history (the records carry a
  * 4-bit predecessor word: 64 B per 3 frames at N = 5, against 4 frames of the loop form).  max_frames is a hard capacity
- * as in gh_online_create.  FULL HISTORY ONLY: there is no window variant, and gh_online_commit* / gh_online_tail* on such
- * a session are GH_ERR_UNSUPPORTED (the settle walk does not read the wider records).  gh_online_push, gh_online_result*,
- * gh_online_reset, gh_online_frames and gh_online_destroy serve it as they serve a loop session. */
+ * as in gh_online_create.  A session made by gh_online_create_bigram keeps its FULL HISTORY and does not settle:
+ * gh_online_commit* / gh_online_tail* on it are GH_ERR_UNSUPPORTED (gh_online_create_bigram_settle makes one that does).
+ * gh_online_push, gh_online_result*, gh_online_reset, gh_online_frames and gh_online_destroy serve it as they serve a loop
+ * session. */
 int gh_online_create_bigram(gh_ctx* ctx, const gh_lattices* lat, int64_t n_streams, int64_t max_frames, gh_online** out);
+/* A bigram session WITH A SETTLED PREFIX: the same graph checks as gh_online_create_bigram, and gh_online_commit* /
+ * gh_online_tail* serve it as they serve a loop session (the settle walk and the segment walk over the bigram records: an
+ * entry row is left through the predecessor word its own record names).  window == 0: history for `frames` frames per stream,
+ * a hard capacity as above; gh_online_result* goes on covering the whole history.  window != 0: history for `frames`
+ * UNSETTLED frames per stream in a ring of ceil(frames / columns per record word) + 1 record words, as
+ * gh_online_create_window: a stream may run for any length, a push past the window is refused as a whole, there is no
+ * forced commit, and gh_online_result* is GH_ERR_UNSUPPORTED (gh_online_tail*).  A commit reads one 64 B record row per
+ * `columns per record word` unsettled frames of a stream (N = 5: 3 frames) and the stream's 128 N B column. */
+int gh_online_create_bigram_settle(gh_ctx* ctx, const gh_lattices* lat, int64_t n_streams, int64_t frames, int window,
+                                   gh_online** out);
 
 /* ------------------------------------------------ online isolated-word recognition: A5 while the audio is still arriving
  * HMM.evaluate (hmm.py:126-135) of every word model, carried across the chunks of n_streams live utterances: the cost of a

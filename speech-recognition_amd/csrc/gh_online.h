@@ -27,13 +27,15 @@ struct gh_online_args {
     uint32_t* open;        // [n_streams][16]
     uint16_t* hist;        // decision words, stream k at k * hist_stride (uint16 units, as gh_layers_args::bp)
     int64_t hist_stride;
-    int ring_words;        // word index i of a stream lives at i % ring_words (bigram form: never wraps, not read)
+    int ring_words;        // word index i of a stream lives at i % ring_words (both forms)
 };
 
 struct gh_online {
     gh_ctx* ctx;
     const gh_lattices* lat;        // must outlive the session
-    bool bigram;                   // the graph is in bigram form (gh_online_create_bigram): wider records, full history only
+    bool bigram;                   // the graph is in bigram form (gh_online_create_bigram[_settle]): wider records
+    bool settles;                  // gh_online_commit / gh_online_tail serve the session (a loop session always; a bigram one
+                                   // only from gh_online_create_bigram_settle, which alone may give it a window)
     int64_t n_streams, max_frames, hist_stride;
     int64_t window;                // > 0: the history is a ring that holds `window` unsettled frames (gh_online_create_window)
     int32_t ring_words;            // decision words per lane in a stream's history: word index i lives at i % ring_words
@@ -54,7 +56,8 @@ struct gh_online {
 // End costs and end selection of n streams from their carried columns (gh_viterbi_online.hip)
 int gh_launch_online_end(gh_ctx* ctx, const gh_online* on, const int64_t* d_ids, const int64_t* d_utt_off, int64_t n, double* d_end_cost,
                          int32_t* d_best_end);
-// The same for a bigram session, and its carried sweep (gh_viterbi_bigram_online.hip)
+// The same for a bigram session, and its carried sweep (gh_viterbi_bigram_online.hip); the sweep writes the history through
+// the ring like viterbi_online_kernel
 int gh_launch_online_bigram_end(gh_ctx* ctx, const gh_online* on, const int64_t* d_ids, const int64_t* d_utt_off, int64_t n,
                                 double* d_end_cost, int32_t* d_best_end);
 int gh_launch_online_bigram(gh_ctx* ctx, const gh_online_args& a, const gh_layerform& f, bool f64);

@@ -4,9 +4,9 @@
 //   * the previous column: the N state costs of its 16 word lanes               [stream][N][16] doubles,
 //   * the decision word that is still open (pushed bits, right aligned)         [stream][16] uint32,
 //   * the number of frames it has taken (host side: the absolute column of the next frame),
-// and its decision history, written at the ABSOLUTE word index in exactly the layout viterbi_bigram_kernel writes for a whole
-// utterance of the same frames (gh_bigram_hb / gh_bigram_cpw, 16 lanes x 4 B per CPW columns, the last open word left
-// aligned).  bigram_backtrace_kernel reads nothing but those records, so gh_launch_bigram_backtrace runs UNCHANGED on the
+// and its decision history, in exactly the layout viterbi_bigram_kernel writes for a whole utterance of the same frames
+// (gh_bigram_hb / gh_bigram_cpw, 16 lanes x 4 B per CPW columns, the last open word left aligned), record word index i at
+// i % ring_words: in a session with full history the ring is as long as the last word index and nothing ever wraps.  bigram_backtrace_kernel reads nothing but those records, so gh_launch_bigram_backtrace runs UNCHANGED on the
 // history (path, label and timed-label mode) and "the result after k frames" is bitwise the whole decode of the first k
 // frames.
 //
@@ -15,8 +15,8 @@
 // refill.  The column step is a COPY of viterbi_bigram_kernel's (in-word candidates in ascending origin order with a strict
 // '<', row_lane<v>(last) + bc[v] for v ascending, the GH_BG_MERGE tree whose left operand is always the lower word, the
 // predecessor nibble, then the two state-0 bits); what differs is where `prev` and `word` come from and go to, and that the
-// start-row term and the record word index use the absolute column.  The history is never a ring here: a bigram session
-// keeps the whole history (no window, nothing settles; gh_online.h).
+// start-row term uses the absolute column and the record word goes to its ring position (carried beside the column and wrapped
+// when a word fills, as in viterbi_online_kernel; a session with a window, gh_online_create_bigram_settle, makes it wrap).
 #include "gh_online.h"
 #include "gh_viterbi.h"
 #include "gh_wave.h"
@@ -76,7 +76,8 @@ __global__ __launch_bounds__(64) void viterbi_bigram_online_kernel(gh_online_arg
     for (int s = 0; s < N; ++s) prev[s] = carried ? st[s * 16] : INF;
     uint32_t word = (carried && tb % CPW != 0) ? *op : 0u;
     uint32_t* bp = reinterpret_cast<uint32_t*>(a.hist + (int64_t)sl.stream * a.hist_stride) + w;
-    int wi = tb / CPW;                                          // index of the open record word: ta / CPW, moved on as words fill
+    const int n_ring = a.ring_words;
+    int wr = (tb / CPW) % n_ring;                               // ring position of the open record word; it moves on as words fill
 
     for (int t0 = 0; t0 < Tmax; t0 += PF) {
 #pragma unroll
@@ -133,13 +134,13 @@ __global__ __launch_bounds__(64) void viterbi_bigram_online_kernel(gh_online_arg
                 prev[0] = vmin(vmin(base0, m2) + e[0], INF);
                 const int ci = ta % CPW;
                 if (ci == CPW - 1) {
-                    bp[(int64_t)wi * 16] = word;
+                    bp[(int64_t)wr * 16] = word;
                     word = 0;
-                    ++wi;
+                    wr = wr + 1 == n_ring ? 0 : wr + 1;
                 } else if (t == T - 1) {
                     // the chunk ends inside a word: the history shows it left aligned (what the one-shot sweep leaves behind
                     // its last column), the state keeps the pushed bits for the next chunk
-                    bp[(int64_t)wi * 16] = word << (HB * (CPW - 1 - ci));
+                    bp[(int64_t)wr * 16] = word << (HB * (CPW - 1 - ci));
                 }
             }
             {   // the slot's refill: unconditional, from a clamped column, outside the divergent region (viterbi_bigram_kernel)

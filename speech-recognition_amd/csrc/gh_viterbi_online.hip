@@ -23,7 +23,9 @@
 //
 // The same session object serves the BIGRAM form (gh_online_create_bigram, on->bigram): push, result, reset, frames and
 // destroy below dispatch on it -- the carried sweep and the end kernel of gh_viterbi_bigram_online.hip, the back-trace of
-// gh_viterbi_bigram.hip -- with every host-side check unchanged.  Such a session keeps its full history: no window, no commit.
+// gh_viterbi_bigram.hip -- with every host-side check unchanged.  One made by gh_online_create_bigram keeps its full history
+// and has no commit; gh_online_create_bigram_settle makes one that settles (gh_online_settle.hip: the walk over the bigram
+// records) and, with a window, keeps the unsettled tail in the same ring.
 #include "gh_online.h"
 #include "gh_viterbi.h"
 #include "gh_wave.h"
@@ -199,9 +201,12 @@ int launch_online(gh_ctx* ctx, const gh_online_args& a, const gh_layerform& f, b
 }
 
 // a session with history for `frames` frames per stream: all a stream will ever take, or (window) its unsettled tail
-// (bigram: the graph must be in bigram form instead, gh_online_create_bigram; full history only)
-int online_create(gh_ctx* ctx, const gh_lattices* lat, int64_t n_streams, int64_t frames, bool window, bool bigram, gh_online** out) {
-    const char* const who = bigram ? "gh_online_create_bigram" : window ? "gh_online_create_window" : "gh_online_create";
+// (bigram: the graph must be in bigram form instead; settles: commit and tail serve the session -- a loop session always, a
+//  bigram one from gh_online_create_bigram_settle only, and only such a bigram session may have a window)
+int online_create(gh_ctx* ctx, const gh_lattices* lat, int64_t n_streams, int64_t frames, bool window, bool bigram, bool settles,
+                  gh_online** out) {
+    const char* const who = bigram ? (settles ? "gh_online_create_bigram_settle" : "gh_online_create_bigram")
+                                   : window ? "gh_online_create_window" : "gh_online_create";
     GH_REQUIRE(ctx && lat && out, "%s: NULL argument", who);
     *out = nullptr;
     GH_REQUIRE(n_streams >= 1 && n_streams <= 0x7fffffff, "%s: n_streams=%lld", who, (long long)n_streams);
@@ -227,7 +232,7 @@ int online_create(gh_ctx* ctx, const gh_lattices* lat, int64_t n_streams, int64_
     GH_HIP(hipSetDevice(ctx->device));
     const gh_layerform& f = lat->h_layers;
     gh_online* on = new gh_online();
-    on->ctx = ctx; on->lat = lat; on->bigram = bigram; on->n_streams = n_streams;
+    on->ctx = ctx; on->lat = lat; on->bigram = bigram; on->settles = settles; on->n_streams = n_streams;
     // a window: whole decision words, one more for the word the anchor lies in; the stream itself ends with the 32-bit column
     const int cpw = bigram ? gh_bigram_cpw(f.N, f.skip != 0) : gh_loop_cpw(f.N, f.skip != 0);
     on->max_frames = window ? 0x7fffffff : frames;
@@ -273,15 +278,20 @@ int gh_launch_online_end(gh_ctx* ctx, const gh_online* on, const int64_t* d_ids,
 
 // --------------------------------------------------------------------------------------------------------------- C ABI
 extern "C" int gh_online_create(gh_ctx* ctx, const gh_lattices* lat, int64_t n_streams, int64_t max_frames, gh_online** out) {
-    return online_create(ctx, lat, n_streams, max_frames, false, false, out);
+    return online_create(ctx, lat, n_streams, max_frames, false, false, true, out);
 }
 
 extern "C" int gh_online_create_bigram(gh_ctx* ctx, const gh_lattices* lat, int64_t n_streams, int64_t max_frames, gh_online** out) {
-    return online_create(ctx, lat, n_streams, max_frames, false, true, out);
+    return online_create(ctx, lat, n_streams, max_frames, false, true, false, out);
 }
 
 extern "C" int gh_online_create_window(gh_ctx* ctx, const gh_lattices* lat, int64_t n_streams, int64_t window_frames, gh_online** out) {
-    return online_create(ctx, lat, n_streams, window_frames, true, false, out);
+    return online_create(ctx, lat, n_streams, window_frames, true, false, true, out);
+}
+
+extern "C" int gh_online_create_bigram_settle(gh_ctx* ctx, const gh_lattices* lat, int64_t n_streams, int64_t frames, int window,
+                                              gh_online** out) {
+    return online_create(ctx, lat, n_streams, frames, window != 0, true, true, out);
 }
 
 extern "C" void gh_online_destroy(gh_online* on) {

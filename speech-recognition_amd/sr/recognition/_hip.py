@@ -177,6 +177,7 @@ SIGNATURES = {
                                    _c_i32p, _c_i64p, _c_i32p, _c_i32p]),
     "gh_online_create_window": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.POINTER(C.c_void_p)]),
     "gh_online_create_bigram": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.POINTER(C.c_void_p)]),
+    "gh_online_create_bigram_settle": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.POINTER(C.c_void_p)]),
     "gh_online_commit": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, _c_i64p, _c_i64p, _c_i32p, _c_i32p, _c_i64p, _c_i32p]),
     "gh_online_commit_timed": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, _c_i64p, _c_i64p, _c_i32p, _c_i32p, _c_i64p, _c_i32p, _c_i32p]),
     "gh_online_tail": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, _c_i64p, _c_f64p, _c_i32p, _c_i32p, _c_i32p, _c_i64p, _c_i32p]),
@@ -1622,15 +1623,27 @@ class OnlineSession:
 class OnlineBigramSession(OnlineSession):
     """Online decode over ONE graph in bigram form (gh_online_create_bigram): the `OnlineSession` of a grammar with
     word-to-word costs.  `push`, `result` (labels, begins, paths), `reset` and `frames` are the parent's, and `result` is
-    bitwise the one-shot bigram decode of the frames a stream has taken.  Full history only (`max_frames`); `commit` and
-    `tail` raise `Unsupported` -- there is no settled prefix yet.  A loop graph, a K-layer lattice, a beam or a word size
-    the bigram sweep is not built for raise `Unsupported`."""
+    bitwise the one-shot bigram decode of the frames a stream has taken.  A loop graph, a K-layer lattice, a beam or a word
+    size the bigram sweep is not built for raise `Unsupported`.
+    By default the session keeps its full history (`max_frames`) and does not settle: `commit` and `tail` raise
+    `Unsupported`.  `settle=True` (gh_online_create_bigram_settle) gives it the parent's `commit` and `tail`; `window=`
+    instead of `max_frames=` implies it and keeps history for that many UNSETTLED frames per stream in a ring, so a stream
+    may run for any length (`result` is then `Unsupported`: no paths, use `tail`)."""
 
-    def __init__(self, ctx, lat, n_streams, max_frames):
+    def __init__(self, ctx, lat, n_streams, max_frames=None, window=None, settle=False):
+        if (max_frames is None) == (window is None):
+            raise ValueError("exactly one of max_frames and window must be given")
         self.ctx, self.lat = ctx, lat
-        self.n_streams, self.max_frames, self.window = int(n_streams), int(max_frames), None
+        self.n_streams = int(n_streams)
+        self.max_frames = None if max_frames is None else int(max_frames)
+        self.window = None if window is None else int(window)
+        self.settles = bool(settle) or window is not None
         h = C.c_void_p()
-        rc = ctx.lib.gh_online_create_bigram(ctx.h, lat.h, self.n_streams, self.max_frames, C.byref(h))
+        if self.settles:
+            rc = ctx.lib.gh_online_create_bigram_settle(ctx.h, lat.h, self.n_streams, self.max_frames if window is None else self.window,
+                                                        int(window is not None), C.byref(h))
+        else:
+            rc = ctx.lib.gh_online_create_bigram(ctx.h, lat.h, self.n_streams, self.max_frames, C.byref(h))
         if rc == GH_ERR_UNSUPPORTED:
             raise Unsupported(ctx.lib.gh_last_error().decode("utf-8", "replace"))
         _check(ctx.lib, rc)
@@ -1639,10 +1652,16 @@ class OnlineBigramSession(OnlineSession):
         self._nlev = lat.path_cap(0, 1)
 
     def commit(self, ids=None, row_label=None, max_labels=None, want_begin=False):
-        raise Unsupported("a bigram session has no settled prefix: result() gives the running hypothesis")
+        if not self.settles:
+            raise Unsupported("a bigram session has no settled prefix: result() gives the running hypothesis (settle=True or window= "
+                              "makes one that has)")
+        return super().commit(ids, row_label, max_labels, want_begin)
 
     def tail(self, ids=None, row_label=None, max_labels=None, want_begin=False):
-        raise Unsupported("a bigram session has no settled prefix: result() gives the running hypothesis")
+        if not self.settles:
+            raise Unsupported("a bigram session has no settled prefix: result() gives the running hypothesis (settle=True or window= "
+                              "makes one that has)")
+        return super().tail(ids, row_label, max_labels, want_begin)
 
 
 class WordStreamSession:

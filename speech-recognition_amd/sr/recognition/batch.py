@@ -439,13 +439,15 @@ class ContinuousDecoder:
         return OnlineDecoder(self, n_streams, max_frames, window, frontend, endpointer, times)
 
 
-    def online_bigram(self, n_streams, max_frames, frontend=None, endpointer=None, times=False):
+    def online_bigram(self, n_streams, max_frames=None, window=None, frontend=None, endpointer=None, times=False, settle=False):
         """An `OnlineBigramDecoder` of `n_streams` live utterances sharing this decoder's packed mixtures and bigram graph
-        (grammar="bigram" only: anything else raises `_hip.Unsupported` before the GPU is touched).  `max_frames`:
-        utterances of up to that many frames, whole history kept -- there is no `window=` for a bigram grammar yet.
-        frontend / endpointer / times: as in `online`.  The language-model costs (`bigram`, `initial`, `lm_scale`) are
-        in the graph; nothing is passed again."""
-        return OnlineBigramDecoder(self, n_streams, max_frames, frontend, endpointer, times)
+        (grammar="bigram" only: anything else raises `_hip.Unsupported` before the GPU is touched).  Exactly one of
+        `max_frames` (utterances of up to that many frames, whole history kept) and `window` (utterances of any length,
+        history for that many unsettled frames) must be given.  The settled prefix (`commit`, `settled`,
+        `settled_times`) is opt-in: `window=` implies it, `max_frames=..., settle=True` asks for it; without either the
+        decoder refuses those three calls.  frontend / endpointer / times: as in `online`.  The language-model costs
+        (`bigram`, `initial`, `lm_scale`) are in the graph; nothing is passed again."""
+        return OnlineBigramDecoder(self, n_streams, max_frames, window, frontend, endpointer, times, settle)
 
 
 class _OnlineStreams:
@@ -820,30 +822,63 @@ class OnlineBigramDecoder(OnlineDecoder):
         on.push([3, 7], [frames_of_3, frames_of_7])
         words, info = on.result([3]); info["begins"][0]
 
-    It has the surface of an `OnlineDecoder` made with `max_frames=`: the whole history is kept and `max_frames` is a hard
-    capacity.  NOT offered yet: `window=` and the settled prefix -- `commit`, `settled` and `settled_times` raise
-    `_hip.Unsupported` (the settle walk needs its own kernels for the bigram records)."""
+    Made like this it has the surface of an `OnlineDecoder` made with `max_frames=`: the whole history is kept,
+    `max_frames` is a hard capacity, and NOTHING SETTLES -- `commit`, `settled` and `settled_times` raise
+    `_hip.Unsupported`.  The settled prefix is opt-in (gh_online_create_bigram_settle: the settle walk over the bigram
+    records, where a first state is left through the predecessor word its own record names):
 
-    def __init__(self, decoder, n_streams, max_frames, frontend=None, endpointer=None, times=False):
+        on = dec.online_bigram(n_streams=64, window=400, times=True)      # history for 400 UNSETTLED frames per stream
+        on.push(ids, chunks); new_words, new_begins = on.commit(ids, want_times=True)
+        words, info = on.result([3])                                      # settled words + the words of the unsettled tail
+        on = dec.online_bigram(n_streams=64, max_frames=3000, settle=True)   # full history (paths), with `commit`
+
+    With `window=`, or with `max_frames=..., settle=True`, `commit`, `settled`, `settled_times`, the windowed `result`
+    (no paths), the window check of a push and `push_recording`'s commit after every tick are `OnlineDecoder`'s own,
+    unchanged; there is no forced commit either."""
+
+    def __init__(self, decoder, n_streams, max_frames=None, window=None, frontend=None, endpointer=None, times=False, settle=False):
         if decoder.grammar != "bigram":
             raise _hip.Unsupported("online_bigram takes the bigram grammar (grammar='bigram'), not %r%s"
                                    % (decoder.grammar, " (online takes it)" if decoder.grammar == "loop" else ""))
-        if max_frames is None or int(n_streams) < 1 or int(max_frames) < 1:
-            raise ValueError("n_streams and max_frames must be positive")
+        if (max_frames is None) == (window is None):
+            raise ValueError("exactly one of max_frames and window must be given")
+        if int(n_streams) < 1 or int(window if max_frames is None else max_frames) < 1:
+            raise ValueError("n_streams and max_frames / window must be positive")
         self._attach(decoder.ctx, decoder.dtype, decoder.gmm, n_streams, frontend, endpointer)
         self.decoder = decoder
-        self.max_frames, self.window = int(max_frames), None
-        self.session = _hip.OnlineBigramSession(decoder.ctx, decoder.lat, self.n_streams, self.max_frames)
-        self._init_words(decoder, times)                              # (nothing settles: the settled words stay empty)
+        self.max_frames = None if max_frames is None else int(max_frames)
+        self.window = None if window is None else int(window)
+        self.settles = bool(settle) or window is not None
+        # a ONE-WORD bigram grammar is a word loop -- one entry row, fed by the word's own last state -- and the library
+        # recognises its graph in the loop form: the loop session serves it, with the same rows and the same results
+        if int(decoder.lat.n_end[0]) == 1 and "bigram" not in decoder.lat.forms():
+            self.session = _hip.OnlineSession(decoder.ctx, decoder.lat, self.n_streams, self.max_frames, self.window)
+        elif not self.settles:
+            self.session = _hip.OnlineBigramSession(decoder.ctx, decoder.lat, self.n_streams, self.max_frames)
+        elif window is None:
+            self.session = _hip.OnlineBigramSession(decoder.ctx, decoder.lat, self.n_streams, self.max_frames, settle=True)
+        else:
+            self.session = _hip.OnlineBigramSession(decoder.ctx, decoder.lat, self.n_streams, window=self.window)
+        self._init_words(decoder, times)                              # (a decoder that does not settle: the settled words stay empty)
+
+    def _refuse(self):
+        raise _hip.Unsupported("this bigram decoder has no settled prefix: result() gives the running hypothesis "
+                               "(online_bigram(..., window=) or (..., max_frames=, settle=True) makes one that has)")
 
     def commit(self, ids=None, want_times=False):
-        raise _hip.Unsupported("a bigram decoder has no settled prefix: result() gives the running hypothesis")
+        if not self.settles:
+            self._refuse()
+        return super().commit(ids, want_times)
 
     def settled(self, ids=None):
-        raise _hip.Unsupported("a bigram decoder has no settled prefix: result() gives the running hypothesis")
+        if not self.settles:
+            self._refuse()
+        return super().settled(ids)
 
     def settled_times(self, ids=None):
-        raise _hip.Unsupported("a bigram decoder has no settled prefix: result() gives the running hypothesis")
+        if not self.settles:
+            self._refuse()
+        return super().settled_times(ids)
 
 
 class OnlineWordRecognizer(_OnlineStreams):
