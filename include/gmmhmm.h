@@ -791,6 +791,20 @@ int gh_online_create_bigram(gh_ctx* ctx, const gh_lattices* lat, int64_t n_strea
 int gh_online_create_bigram_settle(gh_ctx* ctx, const gh_lattices* lat, int64_t n_streams, int64_t frames, int window,
                                    gh_online** out);
 
+/* ------------------------------------------------ online decode for vocabularies of 17 to 64 words
+ * The same session object over ONE graph in the WIDE loop form (gh_lattices_forms bit 2 with 17 .. 64 words of 2 .. 8 states)
+ * without a beam: the carried form of the wide loop sweep, one wave per stream, lane = word.  CONTRACT as gh_online_create:
+ * after k frames gh_online_result / gh_online_result_timed return bitwise what gh_viterbi / gh_viterbi_labels /
+ * gh_viterbi_labels_timed return for those k frames.  A loop graph of 16 words or fewer (gh_online_create takes it), a
+ * bigram graph (gh_online_create_bigram takes it), a K-layer lattice, several graphs or a beam are GH_ERR_UNSUPPORTED.
+ * Per stream: 512 N B of state and 256 B of history PER FRAME (one complete 32-bit decision word per column and word lane;
+ * no open word) -- 4 096 streams x 6 000 frames are 6.3 GB; a size the device cannot give is GH_ERR_NOMEM, the message
+ * holds the byte count.  max_frames is a hard capacity as in gh_online_create.  gh_online_push, gh_online_result*,
+ * gh_online_reset, gh_online_frames and gh_online_destroy serve the session as they serve a narrow one, with the same
+ * checks.  A wide session keeps its FULL HISTORY and DOES NOT SETTLE: gh_online_commit* / gh_online_tail* on it are
+ * GH_ERR_UNSUPPORTED.  A settle walk over 64 word lanes and a windowed wide session are not built. */
+int gh_online_create_wide(gh_ctx* ctx, const gh_lattices* lat, int64_t n_streams, int64_t max_frames, gh_online** out);
+
 /* ------------------------------------------------ online isolated-word recognition: A5 while the audio is still arriving
  * HMM.evaluate (hmm.py:126-135) of every word model, carried across the chunks of n_streams live utterances: the cost of a
  * word is the last state's cell of the last column, and a column depends on the previous column only, so a stream keeps

@@ -1,5 +1,5 @@
 // The online session (gh_online_*): what gh_viterbi_online.hip (create, push, result), gh_viterbi_bigram_online.hip (the carried
-// bigram sweep) and gh_online_settle.hip (commit, tail) share.
+// bigram sweep), gh_viterbi_online_wide.hip (the carried wide loop sweep) and gh_online_settle.hip (commit, tail) share.
 #pragma once
 #include "gh_internal.h"
 #include "gh_host.h"
@@ -16,18 +16,18 @@ struct gh_online_anchor {
     int32_t col, word, state, pad;
 };
 
-// argument block of the carried sweeps (viterbi_online_kernel, viterbi_bigram_online_kernel)
+// argument block of the carried sweeps (viterbi_online_kernel, viterbi_bigram_online_kernel, viterbi_online_wide_kernel)
 struct gh_online_args {
     const gh_layerform* lf;
     const void* nll;
     int S;
     const gh_online_slot* slots;
     int64_t n_slots;
-    double* prev;          // [n_streams][N][16]
-    uint32_t* open;        // [n_streams][16]
+    double* prev;          // [n_streams][N][16] (wide session: [n_streams][N][64])
+    uint32_t* open;        // [n_streams][16] (wide session: none, null)
     uint16_t* hist;        // decision words, stream k at k * hist_stride (uint16 units, as gh_layers_args::bp)
     int64_t hist_stride;
-    int ring_words;        // word index i of a stream lives at i % ring_words (both forms)
+    int ring_words;        // word index i of a stream lives at i % ring_words (both narrow forms; a wide session has no ring)
 };
 
 struct gh_online {
@@ -36,12 +36,14 @@ struct gh_online {
     bool bigram;                   // the graph is in bigram form (gh_online_create_bigram[_settle]): wider records
     bool settles;                  // gh_online_commit / gh_online_tail serve the session (a loop session always; a bigram one
                                    // only from gh_online_create_bigram_settle, which alone may give it a window)
+    bool wide;                     // the graph is a word loop of 17 .. 64 words (gh_online_create_wide): lane = word, a wave per
+                                   // stream, one 32-bit decision word per column and lane, full history, no settled prefix
     int64_t n_streams, max_frames, hist_stride;
     int64_t window;                // > 0: the history is a ring that holds `window` unsettled frames (gh_online_create_window)
     int32_t ring_words;            // decision words per lane in a stream's history: word index i lives at i % ring_words
     void* d_arena;
     double* d_prev;
-    uint32_t* d_open;
+    uint32_t* d_open;              // (null in a wide session: it has no open word)
     uint16_t* d_hist;
     gh_online_anchor* d_anchor;    // [n_streams], valid where settled[stream] > 0
     gh_online_slot* d_slots;       // [n_streams]: the table of the push in flight
@@ -61,3 +63,8 @@ int gh_launch_online_end(gh_ctx* ctx, const gh_online* on, const int64_t* d_ids,
 int gh_launch_online_bigram_end(gh_ctx* ctx, const gh_online* on, const int64_t* d_ids, const int64_t* d_utt_off, int64_t n,
                                 double* d_end_cost, int32_t* d_best_end);
 int gh_launch_online_bigram(gh_ctx* ctx, const gh_online_args& a, const gh_layerform& f, bool f64);
+// ... and for a wide session (gh_viterbi_online_wide.hip): one wave per stream; the sweep writes column ta of a stream at word
+// index ta * 64 + lane of its history, no ring
+int gh_launch_online_wide_end(gh_ctx* ctx, const gh_online* on, const int64_t* d_ids, const int64_t* d_utt_off, int64_t n,
+                              double* d_end_cost, int32_t* d_best_end);
+int gh_launch_online_wide(gh_ctx* ctx, const gh_online_args& a, const gh_layerform& f, bool f64);

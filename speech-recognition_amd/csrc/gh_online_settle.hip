@@ -578,6 +578,11 @@ extern "C" int gh_online_commit_timed(gh_ctx* ctx, gh_online* on, int64_t n, con
     GH_REQUIRE(ctx && on, "gh_online_commit: NULL argument");
     GH_REQUIRE(!out_begin || labels, "gh_online_commit_timed: out_begin needs labels");
     GH_REQUIRE(ctx == on->ctx, "gh_online_commit: the session belongs to another context");
+    if (on->wide) {
+        gh_set_error("gh_online_commit: a wide session (more than 16 words) keeps its full history and does not settle; gh_online_result "
+                     "gives the running hypothesis");
+        return GH_ERR_UNSUPPORTED;
+    }
     if (on->bigram && !on->settles) {
         gh_set_error("gh_online_commit: a bigram session has no settled prefix (its records need their own settle walk); gh_online_result gives the "
                      "running hypothesis");
@@ -655,6 +660,11 @@ extern "C" int gh_online_tail_timed(gh_ctx* ctx, gh_online* on, int64_t n, const
     GH_REQUIRE(ctx && on, "gh_online_tail: NULL argument");
     GH_REQUIRE(!out_begin || labels, "gh_online_tail_timed: out_begin needs labels");
     GH_REQUIRE(ctx == on->ctx, "gh_online_tail: the session belongs to another context");
+    if (on->wide) {
+        gh_set_error("gh_online_tail: a wide session (more than 16 words) keeps its full history and does not settle; gh_online_result "
+                     "gives the running hypothesis");
+        return GH_ERR_UNSUPPORTED;
+    }
     if (on->bigram && !on->settles) {
         gh_set_error("gh_online_tail: a bigram session has no settled prefix (its records need their own settle walk); gh_online_result gives the "
                      "running hypothesis");

@@ -26,6 +26,11 @@
 // gh_viterbi_bigram.hip -- with every host-side check unchanged.  One made by gh_online_create_bigram keeps its full history
 // and has no commit; gh_online_create_bigram_settle makes one that settles (gh_online_settle.hip: the walk over the bigram
 // records) and, with a window, keeps the unsettled tail in the same ring.
+//
+// ... and the WIDE loop form (gh_online_create_wide, on->wide: 17 .. 64 words): the carried sweep and the end kernel of
+// gh_viterbi_online_wide.hip, a wave per stream, the history in the one-shot wide kernel's layout -- the back-trace hands
+// over to the wide one by itself.  Full history only: a settle walk over 64 word lanes and a windowed wide session are not
+// built, commit and tail refuse such a session.
 #include "gh_online.h"
 #include "gh_viterbi.h"
 #include "gh_wave.h"
@@ -266,6 +271,71 @@ int online_create(gh_ctx* ctx, const gh_lattices* lat, int64_t n_streams, int64_
     return GH_OK;
 }
 
+// a WIDE session (gh_viterbi_online_wide.hip): the word loop with 17 .. 64 words, a wave per stream.  State [stream][N][64]
+// doubles, no open word, and the full history in the one-shot wide kernel's layout -- gh_loop_wide_bp_entries(max_frames)
+// uint16 units, 256 B per frame, per stream; no ring, no anchors
+int online_create_wide(gh_ctx* ctx, const gh_lattices* lat, int64_t n_streams, int64_t max_frames, gh_online** out) {
+    const char* const who = "gh_online_create_wide";
+    GH_REQUIRE(ctx && lat && out, "%s: NULL argument", who);
+    *out = nullptr;
+    GH_REQUIRE(n_streams >= 1 && n_streams <= 0x7fffffff, "%s: n_streams=%lld", who, (long long)n_streams);
+    GH_REQUIRE(max_frames >= 1 && max_frames <= 0x7fffffff, "%s: max_frames=%lld", who, (long long)max_frames);
+    const char* why = nullptr;
+    if (lat->L != 1 || lat->deferred_src) why = "several graphs (one graph serves all streams)";
+    else if (lat->beam > 0) why = "a rank beam is set on the graph";
+    else if (lat->bigram_ok) why = "a bigram grammar (gh_online_create_bigram takes it)";
+    else if (lat->layers_ok && !lat->h_layers.loop) why = "a K-layer word lattice";
+    else if (!lat->layers_ok || lat->h_layers.loop != 1) why = "a graph that is not in loop form";
+    else if (lat->h_layers.W <= GH_LAYERS_ROWW) why = "16 words or fewer (gh_online_create takes it)";
+    else if (lat->h_layers.W > GH_LAYERS_MAXW) why = "more than 64 words";
+    else if (lat->h_layers.N > 8) why = "more than 8 states per word";
+    if (why) {
+        gh_set_error("%s: wide online decoding takes the word-loop grammar with %d to %d words of up to 8 states, not %s", who,
+                     GH_LAYERS_ROWW + 1, GH_LAYERS_MAXW, why);
+        return GH_ERR_UNSUPPORTED;
+    }
+    const gh_layerform& f = lat->h_layers;
+    auto pad = [](size_t b) { return (b + 255) & ~size_t(255); };
+    // max_frames < 2^31: the stride (128 uint16 units per frame) fits gh_layers_args::bp_off with room to spare; streams x
+    // stride is checked before anything is allocated
+    const int64_t stride = (int64_t)gh_loop_wide_bp_entries(max_frames);
+    const size_t stream_bytes = (size_t)stride * 2 + (size_t)f.N * 64 * sizeof(double) + sizeof(gh_online_slot);
+    if ((size_t)n_streams > (SIZE_MAX / 2 - 1024) / stream_bytes) {
+        gh_set_error("%s: %lld streams x %lld frames (%.0f bytes): the size does not fit a size_t", who, (long long)n_streams,
+                     (long long)max_frames, (double)n_streams * (double)stream_bytes);
+        return GH_ERR_NOMEM;
+    }
+    GH_HIP(hipSetDevice(ctx->device));
+    gh_online* on = new gh_online();
+    on->ctx = ctx; on->lat = lat; on->bigram = false; on->settles = false; on->wide = true; on->n_streams = n_streams;
+    on->max_frames = max_frames;
+    on->window = 0;
+    on->ring_words = 0x7fffffff;                              // (no ring: nothing reads it in a wide session)
+    on->hist_stride = stride;
+    on->d_arena = nullptr; on->h_slots = nullptr; on->copied = nullptr; on->copy_pending = false;
+    on->d_open = nullptr; on->d_anchor = nullptr;
+    on->frames.assign((size_t)n_streams, 0);
+    on->settled.assign((size_t)n_streams, 0);
+    on->seen.assign((size_t)n_streams, 0);
+    const size_t b_prev = pad((size_t)n_streams * f.N * 64 * sizeof(double));
+    const size_t b_hist = pad((size_t)n_streams * (size_t)stride * 2), b_slots = pad((size_t)n_streams * sizeof(gh_online_slot));
+    hipError_t e = hipMalloc(&on->d_arena, b_prev + b_hist + b_slots);
+    if (e == hipSuccess) e = hipHostMalloc((void**)&on->h_slots, b_slots, hipHostMallocDefault);
+    if (e == hipSuccess) e = hipEventCreateWithFlags(&on->copied, hipEventDisableTiming);
+    if (e != hipSuccess) {
+        gh_set_error("%s: %lld streams x %lld frames (%zu bytes): %s", who, (long long)n_streams, (long long)max_frames,
+                     b_prev + b_hist + b_slots, hipGetErrorString(e));
+        gh_online_destroy(on);
+        return e == hipErrorOutOfMemory ? GH_ERR_NOMEM : GH_ERR_HIP;
+    }
+    char* p = static_cast<char*>(on->d_arena);
+    on->d_prev = reinterpret_cast<double*>(p); p += b_prev;
+    on->d_hist = reinterpret_cast<uint16_t*>(p); p += b_hist;
+    on->d_slots = reinterpret_cast<gh_online_slot*>(p);
+    *out = on;
+    return GH_OK;
+}
+
 }  // namespace
 
 int gh_launch_online_end(gh_ctx* ctx, const gh_online* on, const int64_t* d_ids, const int64_t* d_utt_off, int64_t n, double* d_end_cost,
@@ -283,6 +353,10 @@ extern "C" int gh_online_create(gh_ctx* ctx, const gh_lattices* lat, int64_t n_s
 
 extern "C" int gh_online_create_bigram(gh_ctx* ctx, const gh_lattices* lat, int64_t n_streams, int64_t max_frames, gh_online** out) {
     return online_create(ctx, lat, n_streams, max_frames, false, true, false, out);
+}
+
+extern "C" int gh_online_create_wide(gh_ctx* ctx, const gh_lattices* lat, int64_t n_streams, int64_t max_frames, gh_online** out) {
+    return online_create_wide(ctx, lat, n_streams, max_frames, out);
 }
 
 extern "C" int gh_online_create_window(gh_ctx* ctx, const gh_lattices* lat, int64_t n_streams, int64_t window_frames, gh_online** out) {
@@ -369,7 +443,7 @@ extern "C" int gh_online_push(gh_ctx* ctx, gh_online* on, const gh_batch* b, con
                b->nll_S);
     GH_REQUIRE(gh_seq_n_ok(f.N), "gh_online_push: %s form with %d states per word", on->bigram ? "bigram" : "loop", f.N);
     GH_HIP(hipSetDevice(ctx->device));
-    // longest chunks first: the four rows of a wave then end close to each other
+    // longest chunks first: the four rows of a wave then end close to each other (a wide session: the long waves start first)
     std::stable_sort(slots.begin(), slots.end(), [](const gh_online_slot& x, const gh_online_slot& y) { return x.count > y.count; });
     if (on->copy_pending) GH_HIP(hipEventSynchronize(on->copied));          // (the staging buffer is free again)
     memcpy(on->h_slots, slots.data(), slots.size() * sizeof(gh_online_slot));
@@ -380,7 +454,8 @@ extern "C" int gh_online_push(gh_ctx* ctx, gh_online* on, const gh_batch* b, con
     memset(&a, 0, sizeof a);
     a.lf = on->lat->d_layers; a.nll = b->nll; a.S = b->nll_S; a.slots = on->d_slots; a.n_slots = (int64_t)slots.size();
     a.prev = on->d_prev; a.open = on->d_open; a.hist = on->d_hist; a.hist_stride = on->hist_stride; a.ring_words = on->ring_words;
-    const int rc = on->bigram ? gh_launch_online_bigram(ctx, a, f, b->dtype == GH_F64) : launch_online(ctx, a, f, b->dtype == GH_F64);
+    const int rc = on->wide ? gh_launch_online_wide(ctx, a, f, b->dtype == GH_F64)
+                 : on->bigram ? gh_launch_online_bigram(ctx, a, f, b->dtype == GH_F64) : launch_online(ctx, a, f, b->dtype == GH_F64);
     if (rc) return rc;
     for (const gh_online_slot& s : slots) on->frames[(size_t)s.stream] += s.count;
     return GH_OK;
@@ -437,10 +512,12 @@ extern "C" int gh_online_result_timed(gh_ctx* ctx, gh_online* on, int64_t n, con
         GH_HIP(hipMemcpyAsync(d_labeloff, label_off, (size_t)(n + 1) * 8, hipMemcpyHostToDevice, st));
     }
     if (path) GH_HIP(hipMemcpyAsync(d_pathoff, path_off, (size_t)(n + 1) * 8, hipMemcpyHostToDevice, st));
-    rc = on->bigram ? gh_launch_online_bigram_end(ctx, on, d_ids, d_uttoff, n, d_endcost, d_best)
+    rc = on->wide ? gh_launch_online_wide_end(ctx, on, d_ids, d_uttoff, n, d_endcost, d_best)
+       : on->bigram ? gh_launch_online_bigram_end(ctx, on, d_ids, d_uttoff, n, d_endcost, d_best)
                     : gh_launch_online_end(ctx, on, d_ids, d_uttoff, n, d_endcost, d_best);
     if (rc) return rc;
     // the one-shot decode's own back-trace on the history: utterance i = stream ids[i], its decision words at bp_off[i]
+    // (a wide session: gh_launch_lattice_backtrace hands over to the wide loop back-trace, f.W > GH_LAYERS_ROWW)
     gh_layers_args c;
     memset(&c, 0, sizeof c);
     c.lf = lat->d_layers; c.end_slot = lat->d_lf_end_slot; c.end_rows = lat->d_end_rows; c.n_end = n_end; c.S = 0;

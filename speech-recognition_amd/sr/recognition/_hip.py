@@ -178,6 +178,7 @@ SIGNATURES = {
     "gh_online_create_window": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.POINTER(C.c_void_p)]),
     "gh_online_create_bigram": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.POINTER(C.c_void_p)]),
     "gh_online_create_bigram_settle": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.POINTER(C.c_void_p)]),
+    "gh_online_create_wide": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.POINTER(C.c_void_p)]),
     "gh_online_commit": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, _c_i64p, _c_i64p, _c_i32p, _c_i32p, _c_i64p, _c_i32p]),
     "gh_online_commit_timed": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, _c_i64p, _c_i64p, _c_i32p, _c_i32p, _c_i64p, _c_i32p, _c_i32p]),
     "gh_online_tail": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, _c_i64p, _c_f64p, _c_i32p, _c_i32p, _c_i32p, _c_i64p, _c_i32p]),
@@ -1662,6 +1663,44 @@ class OnlineBigramSession(OnlineSession):
             raise Unsupported("a bigram session has no settled prefix: result() gives the running hypothesis (settle=True or window= "
                               "makes one that has)")
         return super().tail(ids, row_label, max_labels, want_begin)
+
+
+class OnlineWideSession(OnlineSession):
+    """Online decode over ONE word-loop graph of 17 to 64 words (gh_online_create_wide): the `OnlineSession` of a larger
+    vocabulary, one wave per stream.  `push`, `result` (labels, begins, paths), `reset` and `frames` are the parent's, and
+    `result` is bitwise the one-shot decode of the frames a stream has taken.  A loop graph of 16 words or fewer (that is
+    `OnlineSession`'s), a bigram graph, a K-layer lattice, a beam or several graphs raise `Unsupported`.
+    The session keeps its full history -- 256 B per frame and stream, `max_frames` is a hard capacity -- and does not
+    settle: there is no `window=`, and `commit` and `tail` raise `Unsupported`."""
+
+    def __init__(self, ctx, lat, n_streams, max_frames):
+        self.ctx, self.lat = ctx, lat
+        self.n_streams = int(n_streams)
+        self.max_frames = int(max_frames)
+        self.window = None
+        h = C.c_void_p()
+        rc = ctx.lib.gh_online_create_wide(ctx.h, lat.h, self.n_streams, self.max_frames, C.byref(h))
+        if rc == GH_ERR_UNSUPPORTED:
+            raise Unsupported(ctx.lib.gh_last_error().decode("utf-8", "replace"))
+        _check(ctx.lib, rc)
+        self.h = h
+        self.n_end, self.R = int(lat.n_end[0]), int(lat.R[0])
+        self._nlev = lat.path_cap(0, 1)
+
+    def _refused(self, rc):
+        if rc == GH_ERR_UNSUPPORTED:
+            raise Unsupported(self.ctx.lib.gh_last_error().decode("utf-8", "replace"))
+        _check(self.ctx.lib, rc)
+        raise Unsupported("a wide session keeps its full history and does not settle: result() gives the running hypothesis")
+
+    def commit(self, ids=None, row_label=None, max_labels=None, want_begin=False):
+        """`Unsupported` (the library's own refusal: a wide session does not settle)."""
+        settled = np.zeros(1, dtype=np.int64)
+        self._refused(self.ctx.lib.gh_online_commit(self.ctx.h, self.h, 0, None, _ptr(settled, _c_i64p), None, None, None, None))
+
+    def tail(self, ids=None, row_label=None, max_labels=None, want_begin=False):
+        """`Unsupported` (the library's own refusal: a wide session does not settle)."""
+        self._refused(self.ctx.lib.gh_online_tail(self.ctx.h, self.h, 0, None, None, None, None, None, None, None))
 
 
 class WordStreamSession:

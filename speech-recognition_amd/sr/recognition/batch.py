@@ -435,7 +435,8 @@ class ContinuousDecoder:
         (39 features, like the models) -- the decoder then takes audio (`push_audio`).  endpointer: a
         `sr.audio_capture.StreamingEndpointer` of the same context, sample rate and `n_streams` (needs a front-end) -- the
         decoder then takes whole recordings and cuts the utterances out itself (`push_recording`).  times=True: the
-        decoder also keeps and reports the frame every word begins in (see `OnlineDecoder`)."""
+        decoder also keeps and reports the frame every word begins in (see `OnlineDecoder`).  A decoder of more than 16
+        words (up to 64, of 2..8 states) takes `max_frames` only: it keeps its full history and does not settle."""
         return OnlineDecoder(self, n_streams, max_frames, window, frontend, endpointer, times)
 
 
@@ -672,7 +673,15 @@ class OnlineDecoder(_OnlineStreams):
 
     `result` / `finish` add `info["begins"]`, `settled_times` gives the begins of all settled words, `push_recording`
     dicts gain `begins` (frames inside the utterance) and `word_begin` (recording samples: `begin` + frame x the
-    front-end's `step`).  With times=False nothing changes and `want_times=True` raises ValueError."""
+    front-end's `step`).  With times=False nothing changes and `want_times=True` raises ValueError.
+
+    MORE THAN 16 WORDS.  A decoder of 17 to 64 words (2..8 states per word) runs on the wide session (gh_online_create_wide:
+    one wave per stream, lane = word), with the same `push` / `push_batch` / `push_audio` / `push_recording` / `result` /
+    `finish` / `reset` / `frames` and word times, and `result` is bitwise the one-shot decode of the frames pushed so far.
+    It keeps the whole history (256 B per frame and stream) and NOTHING SETTLES: `online(..., window=)` raises
+    `_hip.Unsupported` before the GPU is touched, and so do `commit`, `settled` and `settled_times`."""
+
+    wide = False                                          # more than 16 words: the wide session, which does not settle
 
     def __init__(self, decoder, n_streams, max_frames=None, window=None, frontend=None, endpointer=None, times=False):
         if decoder.grammar != "loop":
@@ -682,11 +691,17 @@ class OnlineDecoder(_OnlineStreams):
             raise ValueError("exactly one of max_frames and window must be given")
         if int(n_streams) < 1 or int(window if max_frames is None else max_frames) < 1:
             raise ValueError("n_streams and max_frames / window must be positive")
+        # more than 16 words: the wide session (a wave per stream), which keeps its full history and does not settle
+        self.wide = int(np.max(decoder.row_state)) // int(decoder.n) + 1 > 16
+        if self.wide and window is not None:
+            raise _hip.Unsupported("a decoder with more than 16 words keeps its full history: online(..., max_frames=), not window=")
         self._attach(decoder.ctx, decoder.dtype, decoder.gmm, n_streams, frontend, endpointer)
         self.decoder = decoder
         self.max_frames = None if max_frames is None else int(max_frames)
         self.window = None if window is None else int(window)
-        if window is None:
+        if self.wide:
+            self.session = _hip.OnlineWideSession(decoder.ctx, decoder.lat, self.n_streams, self.max_frames)
+        elif window is None:
             self.session = _hip.OnlineSession(decoder.ctx, decoder.lat, self.n_streams, self.max_frames)
         else:
             self.session = _hip.OnlineSession(decoder.ctx, decoder.lat, self.n_streams, window=self.window)
@@ -734,11 +749,17 @@ class OnlineDecoder(_OnlineStreams):
         r = self.session.result(ids, row_label=self._row_word, max_labels=dec._max_labels(self._frames[ids]), **tm)
         return [[int(w) for w in l] for l in r.pop("labels")], r
 
+    def _refuse_wide(self):
+        raise _hip.Unsupported("a decoder with more than 16 words has no settled prefix: it keeps its full history, and result() "
+                               "gives the running hypothesis")
+
     def commit(self, ids=None, want_times=False):
         """Settles what can no longer change of the streams `ids` (None: all; distinct): the list of the words that became
         final with THIS call, per stream.  Nothing is settled while a stream has fewer than two frames or no live cell, or
         while its traces do not meet.  want_times=True (a decoder with times=True): (new_words, new_begins), the begin
         frame of every newly settled word beside it."""
+        if self.wide:
+            self._refuse_wide()
         if want_times and not self.times:
             raise ValueError("this decoder keeps no word times: online(..., times=True)")
         ids = np.arange(self.n_streams, dtype=np.int64) if ids is None else self._ids(ids)
@@ -759,12 +780,16 @@ class OnlineDecoder(_OnlineStreams):
     def settled(self, ids=None):
         """(all settled words so far, settled_frames [n]) of the streams `ids` (None: all): stream k's first
         settled_frames[k] frames can no longer change its words."""
+        if self.wide:
+            self._refuse_wide()
         ids = np.arange(self.n_streams, dtype=np.int64) if ids is None else self._ids(ids, distinct=False)
         return [list(self._words[k]) for k in ids], self._settled[ids].copy()
 
     def settled_times(self, ids=None):
         """The begin frames of all settled words so far of the streams `ids` (None: all), aligned with `settled`'s words
         (a decoder with times=True)."""
+        if self.wide:
+            self._refuse_wide()
         if not self.times:
             raise ValueError("this decoder keeps no word times: online(..., times=True)")
         ids = np.arange(self.n_streams, dtype=np.int64) if ids is None else self._ids(ids, distinct=False)
