@@ -20,37 +20,14 @@
 // and the words of the unsettled tail (best end -> anchor).
 // online_bigram_settle_kernel, online_bigram_segment_kernel -- the same two walks over the records of a bigram session that
 // settles (gh_online_create_bigram_settle), further down.
+// A WIDE session that settles (gh_online_create_wide_settle: 17 .. 64 words, a wave per stream) has its two walks in
+// gh_online_wide_settle.hip; the host side below -- every check, the task table, the flags -- is the same for all three.
 // Bit layout: gh_loop_hb / gh_loop_cpw (gh_viterbi.h); tie rules: the LOOP branch of lattice_backtrace_kernel.  A finite
 // cell has only finite predecessors, so the "+inf: first existing arc" fallback is never taken by the settle walk; the
 // segment walk keeps it, because the chosen end of a stream may be a +inf cell (the one-shot decode's rule for it).
 #include "gh_online.h"
 #include "gh_viterbi.h"
 #include "gh_wave.h"
-
-struct gh_settle_task {
-    int32_t stream, T, has_anchor, pad;
-};
-
-struct gh_settle_args {
-    const gh_layerform* lf;
-    const int32_t* end_rows;
-    const gh_settle_task* tasks;
-    int64_t n;
-    const double* prev;            // [n_streams][N][16]
-    const uint16_t* hist;          // stream k at k * hist_stride (uint16 units), word index i at i % ring_words
-    int64_t hist_stride;
-    int ring_words;
-    gh_online_anchor* anchor;      // [n_streams]
-    gh_online_anchor* cand;        // [n]: the settle walk's result (commit), null in tail mode
-    const int32_t* best_end;       // [n] (tail mode)
-    const int32_t* row_label;
-    int32_t* labels;
-    const int64_t* label_off;
-    int32_t* n_labels;
-    int64_t* settled_frames;       // [n] (commit)
-    int* flag;
-    int32_t* begins;               // timed twins: the begin column of every label, laid out like `labels` (appended: no older field moves)
-};
 
 namespace {
 
@@ -530,9 +507,11 @@ int launch_bigram_settle(gh_ctx* ctx, const gh_settle_args& a, const gh_layerfor
     return GH_OK;
 }
 
-// the form dispatch of both walks: the records of a bigram session (gh_layerform.loop == 2) have their own kernels
+// the form dispatch of both walks: the records of a bigram session (gh_layerform.loop == 2) have their own kernels, and so
+// has the history of a wide session (more than GH_LAYERS_ROWW words: gh_online_wide_settle.hip)
 int launch_settle(gh_ctx* ctx, const gh_settle_args& a, const gh_layerform& f, bool settle, const char* who) {
     if (f.loop == 2) return launch_bigram_settle(ctx, a, f, settle, who);
+    if (f.W > GH_LAYERS_ROWW) return gh_launch_online_wide_settle(ctx, a, f, settle, who);
     const dim3 blk(64);
     const dim3 grid((unsigned)(settle ? (a.n + 3) / 4 : (a.n + 63) / 64));
 #define GH_ST(ET, NN, SK)                                                                                    \
@@ -578,7 +557,7 @@ extern "C" int gh_online_commit_timed(gh_ctx* ctx, gh_online* on, int64_t n, con
     GH_REQUIRE(ctx && on, "gh_online_commit: NULL argument");
     GH_REQUIRE(!out_begin || labels, "gh_online_commit_timed: out_begin needs labels");
     GH_REQUIRE(ctx == on->ctx, "gh_online_commit: the session belongs to another context");
-    if (on->wide) {
+    if (on->wide && !on->settles) {
         gh_set_error("gh_online_commit: a wide session (more than 16 words) keeps its full history and does not settle; gh_online_result "
                      "gives the running hypothesis");
         return GH_ERR_UNSUPPORTED;
@@ -660,7 +639,7 @@ extern "C" int gh_online_tail_timed(gh_ctx* ctx, gh_online* on, int64_t n, const
     GH_REQUIRE(ctx && on, "gh_online_tail: NULL argument");
     GH_REQUIRE(!out_begin || labels, "gh_online_tail_timed: out_begin needs labels");
     GH_REQUIRE(ctx == on->ctx, "gh_online_tail: the session belongs to another context");
-    if (on->wide) {
+    if (on->wide && !on->settles) {
         gh_set_error("gh_online_tail: a wide session (more than 16 words) keeps its full history and does not settle; gh_online_result "
                      "gives the running hypothesis");
         return GH_ERR_UNSUPPORTED;
@@ -705,7 +684,8 @@ extern "C" int gh_online_tail_timed(gh_ctx* ctx, gh_online* on, int64_t n, const
         GH_HIP(hipMemcpyAsync(d_rowlabel, row_label, (size_t)R * 4, hipMemcpyHostToDevice, st));
         GH_HIP(hipMemcpyAsync(d_labeloff, label_off, (size_t)(n + 1) * 8, hipMemcpyHostToDevice, st));
     }
-    rc = on->bigram ? gh_launch_online_bigram_end(ctx, on, d_ids, d_uttoff, n, d_endcost, d_best)
+    rc = on->wide ? gh_launch_online_wide_end(ctx, on, d_ids, d_uttoff, n, d_endcost, d_best)
+       : on->bigram ? gh_launch_online_bigram_end(ctx, on, d_ids, d_uttoff, n, d_endcost, d_best)
                     : gh_launch_online_end(ctx, on, d_ids, d_uttoff, n, d_endcost, d_best);
     if (rc) return rc;
     if (labels) {

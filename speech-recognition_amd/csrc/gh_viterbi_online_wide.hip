@@ -4,11 +4,12 @@
 //   * the previous column: the N state costs of its 64 word lanes                [stream][N][64] doubles (512 N B),
 //   * the number of frames it has taken (host side: the absolute column of the next frame),
 // and its decision history: the wide kernel writes ONE COMPLETE 32-bit decision word per column and lane, [column][64 lanes],
-// so the word of absolute column ta goes to hist[stream][ta][lane] -- 256 B per frame -- which is exactly where
+// so the word of absolute column ta goes to hist[stream][ta % ring_cols][lane] -- 256 B per frame.  A session that keeps its
+// full history passes a ring it never fills (ring_cols >= max_frames), and column ta then lies exactly where
 // viterbi_loop_wide_kernel puts column ta of a whole utterance.  There is no open word to carry and a chunk never ends
 // inside one.  The back-trace of the one-shot decode (gh_launch_lattice_backtrace hands a graph of more than GH_LAYERS_ROWW
-// words to loop_backtrace_wide_kernel: path, labels, timed labels) therefore runs UNCHANGED on the history, and "the result
-// after k frames" is bitwise the whole decode of the first k frames.
+// words to loop_backtrace_wide_kernel: path, labels, timed labels) therefore runs UNCHANGED on a full history, and "the
+// result after k frames" is bitwise the whole decode of the first k frames.
 //
 // gfx950 mapping: as the wide loop kernel -- ONE STREAM PER WAVE, lane = word, the N states of the word in registers, no LDS,
 // no barrier.  A stream owns its wave, so EXEC stays full and wave_min's v_readlane steps see every lane.  The column step is
@@ -16,8 +17,13 @@
 // order); what differs is where `prev` comes from and goes to, and that the start-row term and the history address use the
 // absolute column.  A chunk of t frames moves 512 N B of state in and out and t 256 B of decisions beside its emissions.
 //
-// NOT OFFERED: a wide session keeps its full history.  It has no settled prefix (the settle walk of gh_online_settle.hip is
-// written for four 16-lane rows, not for 64 word lanes) and no window: gh_online_commit* / gh_online_tail* refuse it.
+// THE RING.  A stream owns its wave, so the column, its ring position and the wrap are wave-uniform: the position starts from
+// t0 % ring_cols once per launch and moves on by compare-and-subtract, no division per column and no lane arithmetic
+// beyond the one-shot kernel's.  A session with a window (gh_online_create_wide_settle, window != 0) holds `window`
+// unsettled frames and the column the anchor lies in; gh_online_wide_settle.hip has the settle walk over 64 word lanes
+// that moves the anchor on.  A session from gh_online_create_wide keeps its full history and does not settle:
+// gh_online_commit* / gh_online_tail* refuse it.  NOT OFFERED: a forced commit (a stream whose traces do not meet within
+// the window can only be finished), the bigram grammar, and words of 12 or 16 states, beyond 16 words.
 #include "gh_online.h"
 #include "gh_viterbi.h"
 #include "gh_wave.h"
@@ -70,8 +76,10 @@ __global__ __launch_bounds__(64) void viterbi_online_wide_kernel(gh_online_args 
     double prev[N];
 #pragma unroll
     for (int s = 0; s < N; ++s) prev[s] = tb > 0 ? st[s * 64] : INF;
-    // column ta of the stream: word index ta * 64 + lane of its history, as in a whole utterance
-    uint32_t* bp = reinterpret_cast<uint32_t*>(a.hist + (int64_t)sl.stream * a.hist_stride) + (int64_t)tb * 64 + lane;
+    // column ta of the stream: word index (ta % ring_cols) * 64 + lane of its history (no wrap: as in a whole utterance)
+    uint32_t* bp = reinterpret_cast<uint32_t*>(a.hist + (int64_t)sl.stream * a.hist_stride) + lane;
+    const int n_ring = a.ring_words;
+    int rp = tb % n_ring;                                      // ring position of the next column (wave-uniform)
     __builtin_amdgcn_s_waitcnt(0x0F70);                        // (the ring's first fill drained: see viterbi_layers_kernel)
     auto column = [&](int t, const ET (&ev)[N]) {
         double e[N];
@@ -113,7 +121,8 @@ __global__ __launch_bounds__(64) void viterbi_online_wide_kernel(gh_online_args 
         push_bit(word, __ballot(b_l));
         push_bit(word, __ballot(b_s));
         prev[0] = vmin(vmin(base0, m2) + e[0], INF);
-        bp[(int64_t)t * 64] = word;
+        bp[(int64_t)rp * 64] = word;
+        rp = rp + 1 == n_ring ? 0 : rp + 1;
     };
     int t0 = 0;
     for (; t0 + PF <= T; t0 += PF) {

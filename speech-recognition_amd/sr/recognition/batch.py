@@ -427,7 +427,7 @@ class ContinuousDecoder:
         """Decode `xs` and tally against the label strings like main.py:54-84 -- see `sequence_report`."""
         return sequence_report(self.decode(xs), labels, verbose=verbose)
 
-    def online(self, n_streams, max_frames=None, window=None, frontend=None, endpointer=None, times=False):
+    def online(self, n_streams, max_frames=None, window=None, frontend=None, endpointer=None, times=False, settle=False):
         """An `OnlineDecoder` of `n_streams` live utterances sharing this decoder's packed mixtures and graph
         (grammar="loop" only: anything else raises `_hip.Unsupported`).  Exactly one of `max_frames` (utterances of up to
         that many frames, whole history kept) and `window` (utterances of any length, history for that many unsettled
@@ -436,8 +436,10 @@ class ContinuousDecoder:
         `sr.audio_capture.StreamingEndpointer` of the same context, sample rate and `n_streams` (needs a front-end) -- the
         decoder then takes whole recordings and cuts the utterances out itself (`push_recording`).  times=True: the
         decoder also keeps and reports the frame every word begins in (see `OnlineDecoder`).  A decoder of more than 16
-        words (up to 64, of 2..8 states) takes `max_frames` only: it keeps its full history and does not settle."""
-        return OnlineDecoder(self, n_streams, max_frames, window, frontend, endpointer, times)
+        words (up to 64, of 2..8 states) by default takes `max_frames` only, keeps its full history and does not settle;
+        `settle=True` gives it the settled prefix (`commit`, `settled`, `settled_times`) with `max_frames=` and lets it
+        take `window=`.  A decoder of up to 16 words always settles and ignores `settle`."""
+        return OnlineDecoder(self, n_streams, max_frames, window, frontend, endpointer, times, settle)
 
 
     def online_bigram(self, n_streams, max_frames=None, window=None, frontend=None, endpointer=None, times=False, settle=False):
@@ -678,12 +680,21 @@ class OnlineDecoder(_OnlineStreams):
     MORE THAN 16 WORDS.  A decoder of 17 to 64 words (2..8 states per word) runs on the wide session (gh_online_create_wide:
     one wave per stream, lane = word), with the same `push` / `push_batch` / `push_audio` / `push_recording` / `result` /
     `finish` / `reset` / `frames` and word times, and `result` is bitwise the one-shot decode of the frames pushed so far.
-    It keeps the whole history (256 B per frame and stream) and NOTHING SETTLES: `online(..., window=)` raises
-    `_hip.Unsupported` before the GPU is touched, and so do `commit`, `settled` and `settled_times`."""
+    Made like this it keeps the whole history (256 B per frame and stream) and NOTHING SETTLES: `online(..., window=)`
+    raises `_hip.Unsupported` before the GPU is touched, and so do `commit`, `settled` and `settled_times`.  The settled
+    prefix is opt-in (gh_online_create_wide_settle: the settle walk over 64 word lanes, a wave per stream):
 
-    wide = False                                          # more than 16 words: the wide session, which does not settle
+        on = dec.online(n_streams=64, max_frames=3000, settle=True)       # full history (paths), with `commit`
+        on = dec.online(n_streams=64, window=400, settle=True)            # history for 400 UNSETTLED frames per stream
 
-    def __init__(self, decoder, n_streams, max_frames=None, window=None, frontend=None, endpointer=None, times=False):
+    With `settle=True`, `commit`, `settled`, `settled_times`, the windowed `result` (no paths), the window check of a
+    push and `push_recording`'s commit after every tick are the ones described above, unchanged; there is no forced
+    commit either.  A decoder of up to 16 words always settles: `settle` changes nothing for it."""
+
+    wide = False                                          # more than 16 words: the wide session
+    settles = True                                        # ... which settles only where `settle=True` asked for it
+
+    def __init__(self, decoder, n_streams, max_frames=None, window=None, frontend=None, endpointer=None, times=False, settle=False):
         if decoder.grammar != "loop":
             raise _hip.Unsupported("online decoding takes the word-loop grammar (grammar='loop'), not %r%s"
                                    % (decoder.grammar, " (online_bigram takes it)" if decoder.grammar == "bigram" else ""))
@@ -691,16 +702,23 @@ class OnlineDecoder(_OnlineStreams):
             raise ValueError("exactly one of max_frames and window must be given")
         if int(n_streams) < 1 or int(window if max_frames is None else max_frames) < 1:
             raise ValueError("n_streams and max_frames / window must be positive")
-        # more than 16 words: the wide session (a wave per stream), which keeps its full history and does not settle
+        # more than 16 words: the wide session (a wave per stream), which keeps its full history and does not settle unless
+        # settle=True asks for it
         self.wide = int(np.max(decoder.row_state)) // int(decoder.n) + 1 > 16
-        if self.wide and window is not None:
-            raise _hip.Unsupported("a decoder with more than 16 words keeps its full history: online(..., max_frames=), not window=")
+        self.settles = not self.wide or bool(settle)
+        if not self.settles and window is not None:
+            raise _hip.Unsupported("a decoder with more than 16 words keeps its full history: online(..., max_frames=), not window= "
+                                   "(online(..., window=, settle=True) makes one that settles)")
         self._attach(decoder.ctx, decoder.dtype, decoder.gmm, n_streams, frontend, endpointer)
         self.decoder = decoder
         self.max_frames = None if max_frames is None else int(max_frames)
         self.window = None if window is None else int(window)
-        if self.wide:
+        if self.wide and not self.settles:
             self.session = _hip.OnlineWideSession(decoder.ctx, decoder.lat, self.n_streams, self.max_frames)
+        elif self.wide and window is None:
+            self.session = _hip.OnlineWideSession(decoder.ctx, decoder.lat, self.n_streams, self.max_frames, settle=True)
+        elif self.wide:
+            self.session = _hip.OnlineWideSession(decoder.ctx, decoder.lat, self.n_streams, window=self.window)
         elif window is None:
             self.session = _hip.OnlineSession(decoder.ctx, decoder.lat, self.n_streams, self.max_frames)
         else:
@@ -751,14 +769,14 @@ class OnlineDecoder(_OnlineStreams):
 
     def _refuse_wide(self):
         raise _hip.Unsupported("a decoder with more than 16 words has no settled prefix: it keeps its full history, and result() "
-                               "gives the running hypothesis")
+                               "gives the running hypothesis (online(..., settle=True) makes one that has)")
 
     def commit(self, ids=None, want_times=False):
         """Settles what can no longer change of the streams `ids` (None: all; distinct): the list of the words that became
         final with THIS call, per stream.  Nothing is settled while a stream has fewer than two frames or no live cell, or
         while its traces do not meet.  want_times=True (a decoder with times=True): (new_words, new_begins), the begin
         frame of every newly settled word beside it."""
-        if self.wide:
+        if not self.settles:
             self._refuse_wide()
         if want_times and not self.times:
             raise ValueError("this decoder keeps no word times: online(..., times=True)")
@@ -780,7 +798,7 @@ class OnlineDecoder(_OnlineStreams):
     def settled(self, ids=None):
         """(all settled words so far, settled_frames [n]) of the streams `ids` (None: all): stream k's first
         settled_frames[k] frames can no longer change its words."""
-        if self.wide:
+        if not self.settles:
             self._refuse_wide()
         ids = np.arange(self.n_streams, dtype=np.int64) if ids is None else self._ids(ids, distinct=False)
         return [list(self._words[k]) for k in ids], self._settled[ids].copy()
@@ -788,7 +806,7 @@ class OnlineDecoder(_OnlineStreams):
     def settled_times(self, ids=None):
         """The begin frames of all settled words so far of the streams `ids` (None: all), aligned with `settled`'s words
         (a decoder with times=True)."""
-        if self.wide:
+        if not self.settles:
             self._refuse_wide()
         if not self.times:
             raise ValueError("this decoder keeps no word times: online(..., times=True)")

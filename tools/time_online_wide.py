@@ -15,7 +15,9 @@ a device synchronise; `--reps` timed rounds after one warm-up round; median with
       `decode_batch` on the prefix every tick (upload, likelihoods and decode of everything heard so far).
 Everything is reported, nothing is gated.  Kernel times come from a run of its own:
     rocprofv3 --kernel-trace --stats -d <dir> -- python tools/time_online_wide.py --reps 1 --no-prefix
-usage: time_online_wide.py [--streams 4096] [--tick 20] [--reps 7] [--no-prefix] [--out profiles/online_wide_4096.json]"""
+`--states` (default 5) sets the states per word: the register use of the carried sweep, and with it the waves per SIMD, differs
+from one word size to the next.
+usage: time_online_wide.py [--streams 4096] [--tick 20] [--reps 7] [--states 5] [--no-prefix] [--out profiles/online_wide_4096.json]"""
 import argparse, json, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 for p in (ROOT, os.path.join(ROOT, "speech-recognition_amd")):
@@ -30,11 +32,12 @@ ap = argparse.ArgumentParser()
 ap.add_argument("--streams", type=int, default=4096)
 ap.add_argument("--tick", type=int, default=20)
 ap.add_argument("--reps", type=int, default=7)
+ap.add_argument("--states", type=int, default=5, help="states per word (2 .. 8)")
 ap.add_argument("--no-prefix", action="store_true", help="leave comparison (c) out (profiler runs)")
 ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "online_wide_4096.json"))
 args = ap.parse_args()
 
-K, W, n, M, D = 7, 64, 5, 8, 39
+K, W, n, M, D = 7, 64, args.states, 8, 39
 U, TICK, REPS = args.streams, args.tick, args.reps
 ctx = _hip.default_context(0)
 wl = bench.synth_workload(1064, 1, W=W, n=n, M=M, D=D)
