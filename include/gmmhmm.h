@@ -298,12 +298,14 @@ int gh_lattices_set_beam(gh_lattices* l, int beam);
  * bit 2: word-loop grammar; bit 3: one word per layer, a graph per transcript (continuous_speech.py:80); bit 4:
  * one-word chains for forward-backward; bit 5: bigram grammar -- the word loop with one non-emitting ENTRY row per word
  * (rows: start | states 1..n-1 of every word | entry rows | state 0 of every word; last state of v -> entry row of w at
- * the bigram cost, entry row of w -> state 0 of w at cost 0, start row -> state 0 of w at the start cost).
+ * the bigram cost, entry row of w -> state 0 of w at cost 0, start row -> state 0 of w at the start cost); bit 6 (64):
+ * the same grammar with MORE THAN 16 WORDS -- the WIDE bigram form.  Bits 5 and 6 exclude each other: gh_viterbi* takes both
+ * (bit 6 on a kernel of its own: a wave per utterance, lane = word), the online sessions and word streams take bit 5 only.
  * < 0: NULL argument.
  * What the forms take: words of 2 .. 8, 12 or 16 states with arcs from s, s-1, s-2; bit 1: up to 16 words per layer
  * and 8 layers (16 layers for words of <= 8 states), or 17 .. 64 words per layer with <= 8 layers of <= 8 states;
  * bit 2: up to 16 words, or 17 .. 64 words of <= 8 states; bit 3: transcripts of up to 16 words; bit 5: 2 .. 16 words
- * (not 16 states with s-2 arcs); one word is the loop form. */
+ * (not 16 states with s-2 arcs); bit 6: 17 .. 64 words of 2 .. 8 states; one word is the loop form. */
 int gh_lattices_forms(const gh_lattices* l);
 
 /* --------------------------------------------------- A6: decode_hmm_states
@@ -813,7 +815,7 @@ int gh_online_create_wide(gh_ctx* ctx, const gh_lattices* lat, int64_t n_streams
  * column the anchor lies in is kept), as gh_online_create_window: a stream may run for any length, a push past the window
  * is refused as a whole, there is no forced commit, and gh_online_result* is GH_ERR_UNSUPPORTED (gh_online_tail*).  Per
  * stream (frames + 1) x 256 + 512 N B instead of max_frames x 256 + 512 N B; a commit reads one 256 B row per unsettled
- * column of a stream and the stream's 512 N B column.  Not offered beyond 16 words: a forced commit, the bigram grammar,
+ * column of a stream and the stream's 512 N B column.  Not offered beyond 16 words: a forced commit, the bigram grammar online (gh_viterbi* decodes it: gh_lattices_forms bit 6),
  * words of 12 or 16 states. */
 int gh_online_create_wide_settle(gh_ctx* ctx, const gh_lattices* lat, int64_t n_streams, int64_t frames, int window,
                                  gh_online** out);

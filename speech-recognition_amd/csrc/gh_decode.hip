@@ -215,8 +215,9 @@ static int viterbi_impl(gh_ctx* ctx, const gh_lattices* lat, const gh_batch* b, 
         if (no_layers) use_layers = false;
         if (b->any_T1) use_layers = false;   // T == 1: the reference's column wrap (lean kernel)
     }
-    // bigram form (gh_viterbi_bigram.hip): the loop form with word-to-word costs, same conditions
-    bool use_bigram = !use_chain && !use_layers && lat->bigram_ok && uniform && !out_costs && lat->beam <= 0;
+    // bigram form (gh_viterbi_bigram.hip; more than 16 words: gh_viterbi_bigram_wide.hip): the loop form with word-to-word
+    // costs, same conditions
+    bool use_bigram = !use_chain && !use_layers && (lat->bigram_ok || lat->bigram_wide_ok) && uniform && !out_costs && lat->beam <= 0;
     {
         const bool no_bigram = forced_kernel() != 0;
         if (no_bigram) use_bigram = false;
@@ -445,8 +446,8 @@ static int viterbi_impl(gh_ctx* ctx, const gh_lattices* lat, const gh_batch* b, 
         if (labels_direct) { c.row_label = d_rowlabel; c.labels = d_labels; c.label_off = d_labeloff; c.n_labels = d_nlabels; if (want_begin) c.path = d_begins; }
         for (size_t k = 0; k + 1 < chunk_begin.size(); ++k) {
             const int64_t u0 = chunk_begin[k], nu = chunk_begin[k + 1] - u0;
-            rc = gh_launch_viterbi_bigram(ctx, c, lat->h_layers, u0, nu, b->dtype == GH_F64, want_path);
-            if (!rc && want_path) rc = gh_launch_bigram_backtrace(ctx, c, lat->h_layers, u0, nu, labels_direct && want_begin);
+            rc = gh_launch_viterbi_bigram(ctx, c, lat->h_layers, u0, nu, b->dtype == GH_F64, want_path, lat->d_bigram_wide);
+            if (!rc && want_path) rc = gh_launch_bigram_backtrace(ctx, c, lat->h_layers, u0, nu, labels_direct && want_begin, lat->d_bigram_wide);
             if (rc) return rc;
         }
         use_layers = true;   // (from here on: "a lattice kernel has run", the row-per-lane kernels are skipped)

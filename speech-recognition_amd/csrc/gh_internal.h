@@ -196,6 +196,10 @@ static inline bool gh_seq_n_ok(int N) { return (N >= 2 && N <= 8) || N == 12 || 
 // by the last state of every word v at cost bg[v][w]; rows loop_row + W + w = state 0 of word w, fed by the start row
 // (cin0), by its entry row at cost 0 and by itself.  Same lane layout; the one row minimum becomes a 16 x 16 min-plus
 // step (gh_viterbi_bigram.hip).  Up to GH_LAYERS_ROWW words.
+// WIDE BIGRAM form (gh_lattices::bigram_wide_ok, neither bigram_ok nor layers_ok): the same rows with 17 .. GH_LAYERS_MAXW words of
+// 2 .. 8 states.  The per-word part of gh_layerform is filled alike (loop = 2); the word-to-word costs and arc masks do not
+// fit its bg / bg_in and live in a gh_bigram_wide of their own (gh_viterbi_bigram_wide.hip: one utterance per wave, lane =
+// word, the costs in LDS).
 struct gh_layerform {
     int32_t K, W, N, skip;      // layers, words per layer, states per word, any s-2 arc
     int32_t P, R, loop, loop_row;
@@ -207,6 +211,12 @@ struct gh_layerform {
     // BIGRAM form (loop = 2, up to GH_LAYERS_ROWW words): loop_row is the FIRST of the W entry rows
     double bg[GH_LAYERS_ROWW][GH_LAYERS_ROWW];          // bg[v][w]: last state of word v -> entry row of word w, +inf = no such arc
     uint16_t bg_in[GH_LAYERS_ROWW];                     // bit v of bg_in[w]: that arc exists
+};
+
+// word-to-word costs of the WIDE bigram form; what lies behind the W words is +inf / 0
+struct gh_bigram_wide {
+    double bg[GH_LAYERS_MAXW][GH_LAYERS_MAXW];          // bg[v][w]: last state of word v -> entry row of word w, +inf = no such arc
+    uint64_t bg_in[GH_LAYERS_MAXW];                     // bit v of bg_in[w]: that arc exists
 };
 
 // SEQUENCE form: a forced-alignment lattice (continuous_speech.py:80: build_state_sequences(models, [[l] for l in labels])) --
@@ -277,6 +287,8 @@ struct gh_lattices {
     bool layers_ok;                  // L == 1 and the graph is a gh_layerform (layers or loop: h_layers.loop)
     gh_layerform h_layers;
     bool bigram_ok = false;          // L == 1 and the graph is in bigram form (h_layers.loop == 2; layers_ok stays false)
+    bool bigram_wide_ok = false;     // ... in WIDE bigram form: more than GH_LAYERS_ROWW words; h_layers holds the per-word part, the
+    gh_bigram_wide* d_bigram_wide = nullptr;   //   word-to-word costs are here.  The online sessions and the word streams go by bigram_ok
     gh_layerform* d_layers;
     int32_t* d_lf_end_slot;          // [R] position of a row in the end list or -1
     bool seq_ok;                     // every graph is in sequence form with the same N

@@ -481,7 +481,9 @@ extern "C" int gh_lattices_create(gh_ctx* ctx, int L, const int64_t* row_off, co
         }
     }
     // ---- bigram form (gh_layerform with loop = 2): the loop grammar with one non-emitting ENTRY row per word ----
-    // (one word: the layout IS the loop form's, recognised above)
+    // (one word: the layout IS the loop form's, recognised above).  Up to GH_LAYERS_ROWW words: bigram_ok, the costs in
+    // gh_layerform::bg; 17 .. GH_LAYERS_MAXW words of up to 8 states: bigram_wide_ok, the costs in a gh_bigram_wide
+    std::vector<gh_bigram_wide> bgw_one;
     if (!lt->layers_ok && L == 1 && !lt->has_nan_arc && !lt->has_self_arc) {
         const int R = lt->lat[0].R;
         gh_layerform& f = lt->h_layers;
@@ -491,11 +493,12 @@ extern "C" int gh_lattices_create(gh_ctx* ctx, int L, const int64_t* row_off, co
         if (ok) {
             while (Lr < R && h_state[Lr] >= 0) ++Lr;                 // states 1 .. N-1 of every word
             while (Lr + W < R && h_state[Lr + W] < 0) ++W;           // the entry rows
-            ok = Lr > 1 && W >= 2 && W <= GH_LAYERS_ROWW && Lr + 2 * W == R && (Lr - 1) % W == 0;
+            ok = Lr > 1 && W >= 2 && W <= GH_LAYERS_MAXW && Lr + 2 * W == R && (Lr - 1) % W == 0;
             for (int r = Lr + W; ok && r < R; ++r) if (h_state[r] < 0) ok = false;
         }
         const int N = ok ? (Lr - 1) / W + 1 : 0;
-        ok = ok && gh_seq_n_ok(N) && lt->lat[0].n_start == 1 && (h_start[0] & 1);
+        const bool wide = W > GH_LAYERS_ROWW;
+        ok = ok && gh_seq_n_ok(N) && (!wide || N <= 8) && lt->lat[0].n_start == 1 && (h_start[0] & 1);
         auto row_of = [&](int w, int sx) { return sx == 0 ? Lr + W + w : 1 + w * (N - 1) + (sx - 1); };
         std::vector<int> wof(R, -1), sof(R, -1);
         for (int w = 0; ok && w < W; ++w)
@@ -506,6 +509,12 @@ extern "C" int gh_lattices_create(gh_ctx* ctx, int L, const int64_t* row_off, co
         }
         for (int v = 0; v < GH_LAYERS_ROWW; ++v)
             for (int w = 0; w < GH_LAYERS_ROWW; ++w) f.bg[v][w] = INFINITY;
+        bgw_one.resize(1);
+        gh_bigram_wide& bgw = bgw_one[0];
+        for (int v = 0; v < GH_LAYERS_MAXW; ++v) {
+            bgw.bg_in[v] = 0;
+            for (int w = 0; w < GH_LAYERS_MAXW; ++w) bgw.bg[v][w] = INFINITY;
+        }
         bool skip = false;
         const int32_t* ptr = h_ptr.data();
         for (int r = 0; ok && r < R; ++r)
@@ -515,9 +524,9 @@ extern "C" int gh_lattices_create(gh_ctx* ctx, int L, const int64_t* row_off, co
                 if (r == 0) { ok = false; break; }                                   // nothing enters the start row
                 if (r >= Lr && r < Lr + W) {                                         // last state of word v -> entry row of word w
                     const int w = r - Lr, v = wof[o];
-                    if (v < 0 || sof[o] != N - 1 || ((f.bg_in[w] >> v) & 1)) { ok = false; break; }
-                    f.bg[v][w] = c;
-                    f.bg_in[w] |= (uint16_t)(1u << v);
+                    if (v < 0 || sof[o] != N - 1 || ((bgw.bg_in[w] >> v) & 1)) { ok = false; break; }
+                    bgw.bg[v][w] = c;
+                    bgw.bg_in[w] |= 1ull << v;
                 } else if (o == 0 || (o >= Lr && o < Lr + W)) {                      // start row / the word's own entry row -> state 0
                     const int w = wof[r];
                     const int bit = o == 0 ? 16 : 8;
@@ -549,12 +558,21 @@ extern "C" int gh_lattices_create(gh_ctx* ctx, int L, const int64_t* row_off, co
             for (int w = 0; w < W; ++w)
                 for (int sx = 0; sx < N; ++sx) f.state[w][sx] = h_state[row_of(w, sx)];
             f.K = 1; f.W = W; f.N = N; f.skip = skip ? 1 : 0; f.P = W * N; f.R = R; f.loop = 2; f.loop_row = Lr;
-            lt->bigram_ok = true;
+            if (wide) lt->bigram_wide_ok = true;
+            else {
+                for (int w = 0; w < W; ++w) {
+                    f.bg_in[w] = (uint16_t)bgw.bg_in[w];
+                    for (int v = 0; v < W; ++v) f.bg[v][w] = bgw.bg[v][w];
+                }
+                lt->bigram_ok = true;
+            }
         }
+        if (!lt->bigram_wide_ok) bgw_one.clear();
     }
     UploadArena ar;
     std::vector<gh_layerform> one(1, lt->h_layers);
-    if (lt->layers_ok || lt->bigram_ok) { ar.add(&lt->d_layers, one); ar.add(&lt->d_lf_end_slot, lf_slot); }
+    if (lt->layers_ok || lt->bigram_ok || lt->bigram_wide_ok) { ar.add(&lt->d_layers, one); ar.add(&lt->d_lf_end_slot, lf_slot); }
+    if (lt->bigram_wide_ok) ar.add(&lt->d_bigram_wide, bgw_one);
     if (lt->chain_ok) {
         ar.add(&lt->d_ch_cost0, ch0); ar.add(&lt->d_ch_cost1, ch1); ar.add(&lt->d_ch_cost2, ch2);
         ar.add(&lt->d_ch_info, chinfo); ar.add(&lt->d_ch_end_slot, chslot); ar.add(&lt->d_ch_group_row0, chgroups);
@@ -595,7 +613,7 @@ extern "C" int gh_lattices_forms(const gh_lattices* l) {
     if (!l) return -1;
     const bool loop = l->layers_ok && l->h_layers.loop;
     return (l->chain_ok ? 1 : 0) | (l->layers_ok && !loop ? 2 : 0) | (loop ? 4 : 0) | (l->seq_ok ? 8 : 0) | (l->fbchain_ok ? 16 : 0) |
-           (l->bigram_ok ? 32 : 0);
+           (l->bigram_ok ? 32 : 0) | (l->bigram_wide_ok ? 64 : 0);
 }
 
 extern "C" int64_t gh_viterbi_path_cap(const gh_lattices* lat, int l, int64_t T) {

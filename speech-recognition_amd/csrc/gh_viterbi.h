@@ -157,9 +157,16 @@ int gh_launch_seq_backtrace(gh_ctx* ctx, const gh_layers_args& a, int N, int ski
 bool gh_bigram_n_ok(int N, int skip);
 size_t gh_bigram_bp_entries(const gh_layerform& f, int64_t T);
 int gh_launch_viterbi_bigram(gh_ctx* ctx, const gh_layers_args& a, const gh_layerform& f, int64_t u_begin, int64_t n_utts,
-                             bool f64, bool want_path);
+                             bool f64, bool want_path, const gh_bigram_wide* wide = nullptr);
 int gh_launch_bigram_backtrace(gh_ctx* ctx, const gh_layers_args& a, const gh_layerform& f, int64_t u_begin, int64_t n_utts,
-        bool timed = false);   // timed: label mode with begins in a.path
+        bool timed = false, const gh_bigram_wide* wide = nullptr);   // timed: label mode with begins in a.path
+// more than GH_LAYERS_ROWW words (gh_viterbi_bigram_wide.hip: one utterance per wave, lane = word, the word-to-word costs `wide`
+// in LDS); the three functions above hand over to these
+size_t gh_bigram_wide_bp_entries(int64_t T);
+int gh_launch_viterbi_bigram_wide(gh_ctx* ctx, const gh_layers_args& a, const gh_layerform& f, const gh_bigram_wide* wide,
+                                  int64_t u_begin, int64_t n_utts, bool f64, bool want_path);
+int gh_launch_bigram_backtrace_wide(gh_ctx* ctx, const gh_layers_args& a, const gh_layerform& f, const gh_bigram_wide* wide,
+                                    int64_t u_begin, int64_t n_utts, bool timed);
 
 // ---------------------------------------------------------------------------------------------------------------------
 // Decision-word layout of the register forms above, ONE definition for the sweep that writes the words, the back-trace that
@@ -168,6 +175,7 @@ int gh_launch_bigram_backtrace(gh_ctx* ctx, const gh_layers_args& a, const gh_la
 constexpr int gh_layer_hb(int N, bool skip) { return N + 1 + (skip ? N - 2 : 0); }    // layer form, narrow and wide
 constexpr int gh_loop_hb(int N, bool skip) { return N + 2 + (skip ? N - 2 : 0); }     // loop form, narrow and wide
 constexpr int gh_bigram_hb(int N, bool skip) { return N + 5 + (skip ? N - 2 : 0); }   // in-word bits, 4 bits of predecessor word, 2 bits of state 0
+constexpr int gh_bigram_wide_hb(int N, bool skip) { return N + 7 + (skip ? N - 2 : 0); }   // the same with 6 bits of predecessor word
 constexpr int gh_seq_hb(int N, bool skip) { return N + (skip ? N - 2 : 0); }
 // layer form: `sets` register sets (2: up to 8 layers, 4: up to 16) share a word, 64 bits wide when 32 do not hold them
 constexpr int gh_layer_word_bits(int N, bool skip, int sets) { return sets * gh_layer_hb(N, skip) > 32 ? 64 : 32; }
@@ -197,6 +205,7 @@ static_assert(gh_layer_word_bits(16, false, 2) == 64 && gh_layer_word_bits(12, f
               gh_layer_word_bits(12, true, 2) == 64 && gh_layer_word_bits(7, false, 4) == 32 && gh_layer_word_bits(8, false, 4) == 64 &&
               gh_layer_word_bits(4, true, 4) == 32 && gh_layer_word_bits(5, true, 4) == 64, "layer form: where the words turn 64 bits wide");
 static_assert(4 * gh_layer_hb(8, true) <= 64 && gh_loop_hb(8, true) <= 32, "wide forms: one word per column (and four layers)");
+static_assert(gh_bigram_wide_hb(8, true) <= 32, "wide bigram form: one word per column");
 static_assert(gh_bigram_hb(16, true) > 32, "bigram form: 16 states with skip arcs do not fit a word");
 }  // namespace gh_layout_check
 

@@ -309,6 +309,7 @@ bool gh_bigram_n_ok(int N, int skip) { return gh_seq_n_ok(N) && !(N == 16 && ski
 
 // back-pointer scratch of one utterance of T frames, in uint16 units (the lattice kernels' common unit)
 size_t gh_bigram_bp_entries(const gh_layerform& f, int64_t T) {
+    if (f.W > GH_LAYERS_ROWW) return gh_bigram_wide_bp_entries(T);
     return gh_bp_entries(T, gh_bigram_cpw(f.N, f.skip), 16, 32);
 }
 
@@ -316,7 +317,8 @@ size_t gh_bigram_bp_entries(const gh_layerform& f, int64_t T) {
     GH_NSKIP_SWITCH(f.N, f.skip, 16_NO_SKIP16, MACRO, ET, "gh_viterbi: bigram form with %d states per word (skip arcs: %d)", f.N, f.skip)
 
 int gh_launch_viterbi_bigram(gh_ctx* ctx, const gh_layers_args& a, const gh_layerform& f, int64_t u_begin, int64_t n_utts,
-                             bool f64, bool want_path) {
+                             bool f64, bool want_path, const gh_bigram_wide* wide) {
+    if (f.W > GH_LAYERS_ROWW) return gh_launch_viterbi_bigram_wide(ctx, a, f, wide, u_begin, n_utts, f64, want_path);
     if (n_utts <= 0) return GH_OK;
     gh_layers_args b = a;
     b.slot0 = u_begin;
@@ -334,7 +336,9 @@ int gh_launch_viterbi_bigram(gh_ctx* ctx, const gh_layers_args& a, const gh_laye
 }
 
 // the path (a.path) or the label sequences (a.labels) of the utterances [u_begin, u_begin + n_utts) from the decision words
-int gh_launch_bigram_backtrace(gh_ctx* ctx, const gh_layers_args& a, const gh_layerform& f, int64_t u_begin, int64_t n_utts, bool timed) {
+int gh_launch_bigram_backtrace(gh_ctx* ctx, const gh_layers_args& a, const gh_layerform& f, int64_t u_begin, int64_t n_utts, bool timed,
+                               const gh_bigram_wide* wide) {
+    if (f.W > GH_LAYERS_ROWW) return gh_launch_bigram_backtrace_wide(ctx, a, f, wide, u_begin, n_utts, timed);
     if (n_utts <= 0 || !(a.path || a.labels)) return GH_OK;
     gh_layers_args b = a;
     b.slot0 = u_begin;

@@ -1224,7 +1224,7 @@ class Lattices:
         _check(self.ctx.lib, self.ctx.lib.gh_lattices_set_beam(self.h, k))
         self.beam = k
 
-    FORMS = ("chain", "layers", "loop", "sequence", "fb_chain", "bigram")
+    FORMS = ("chain", "layers", "loop", "sequence", "fb_chain", "bigram", "bigram_wide")
 
     def forms(self):
         """Names of the special forms the graphs were recognised in (gh_lattices_forms): they select the kernels."""

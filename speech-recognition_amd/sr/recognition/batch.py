@@ -355,7 +355,8 @@ class ContinuousDecoder:
     grammar="bigram": the loop grammar with word-to-word costs (`build_bigram_grammar`): `bigram` is a [W, W] cost
     matrix (`bigram[v, w]`: word w after word v, +inf = forbidden) with optional start costs `initial` [W], or a
     `sr.langmodel.BigramModel`, whose `costs(lm_scale)` are then used.  Up to 16 words of 2..8, 12 or 16 states
-    run on the bigram-form kernel; anything larger decodes on the row-per-lane kernels, same results."""
+    run on the bigram-form kernel, 17 to 64 words of 2..8 states on the wide one (a wave per utterance, lane = word);
+    anything else decodes on the row-per-lane kernels, same results.  (`online_bigram` stops at 16 words.)"""
 
     def __init__(self, models, n_layers=7, device=None, dtype=np.float64, grammar="layers", word_penalty=0.0, ctx=None,
                  bigram=None, initial=None, lm_scale=1.0):
