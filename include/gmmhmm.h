@@ -815,10 +815,27 @@ int gh_online_create_wide(gh_ctx* ctx, const gh_lattices* lat, int64_t n_streams
  * column the anchor lies in is kept), as gh_online_create_window: a stream may run for any length, a push past the window
  * is refused as a whole, there is no forced commit, and gh_online_result* is GH_ERR_UNSUPPORTED (gh_online_tail*).  Per
  * stream (frames + 1) x 256 + 512 N B instead of max_frames x 256 + 512 N B; a commit reads one 256 B row per unsettled
- * column of a stream and the stream's 512 N B column.  Not offered beyond 16 words: a forced commit, the bigram grammar online (gh_viterbi* decodes it: gh_lattices_forms bit 6),
- * words of 12 or 16 states. */
+ * column of a stream and the stream's 512 N B column.  Not offered beyond 16 words: a forced commit, the settled prefix of
+ * a bigram session (gh_online_create_bigram_wide, below, keeps its full history), words of 12 or 16 states. */
 int gh_online_create_wide_settle(gh_ctx* ctx, const gh_lattices* lat, int64_t n_streams, int64_t frames, int window,
                                  gh_online** out);
+
+/* ------------------------------------------------ online decode with a bigram grammar of 17 to 64 words
+ * The same session object over ONE graph in the WIDE BIGRAM form (gh_lattices_forms bit 6: the bigram grammar with 17 .. 64
+ * words of 2 .. 8 states) without a beam: the carried form of the wide bigram sweep, one wave per stream, lane = word, four
+ * streams per block around one 32 KB LDS image of the word-to-word costs.  CONTRACT as gh_online_create: after k frames
+ * gh_online_result / gh_online_result_timed return bitwise what gh_viterbi / gh_viterbi_labels / gh_viterbi_labels_timed
+ * return for those k frames (the one-shot kernel's own back-trace reads the history: the record layout has one reader).  A
+ * loop graph (gh_online_create / gh_online_create_wide take it), a bigram graph of 16 words or fewer (gh_online_create_bigram
+ * takes it), a K-layer lattice, a graph in no wide bigram form, several graphs or a beam are GH_ERR_UNSUPPORTED; every other
+ * gh_online_create* goes on refusing a graph in the wide bigram form.  Per stream: 512 N B of state (fp64 for fp32
+ * likelihoods too) and 256 B of history PER FRAME (one complete 32-bit record per column and word lane: the in-word bits, 6
+ * bits of predecessor word, the two bits of state 0; no open word); a size the device cannot give is GH_ERR_NOMEM, the
+ * message holds the byte count.  max_frames is a hard capacity as in gh_online_create.  gh_online_push, gh_online_result*,
+ * gh_online_reset, gh_online_frames and gh_online_destroy serve the session as they serve every other, with the same
+ * checks.  The session keeps its FULL HISTORY and DOES NOT SETTLE: gh_online_commit* / gh_online_tail* on it are
+ * GH_ERR_UNSUPPORTED, and there is no windowed form yet. */
+int gh_online_create_bigram_wide(gh_ctx* ctx, const gh_lattices* lat, int64_t n_streams, int64_t max_frames, gh_online** out);
 
 /* ------------------------------------------------ online isolated-word recognition: A5 while the audio is still arriving
  * HMM.evaluate (hmm.py:126-135) of every word model, carried across the chunks of n_streams live utterances: the cost of a

@@ -1,6 +1,7 @@
 // The online session (gh_online_*): what gh_viterbi_online.hip (create, push, result), gh_viterbi_bigram_online.hip (the carried
-// bigram sweep), gh_viterbi_online_wide.hip (the carried wide loop sweep), gh_online_settle.hip (commit, tail) and
-// gh_online_wide_settle.hip (the two walks of commit and tail over a wide session's history) share.
+// bigram sweep), gh_viterbi_online_wide.hip (the carried wide loop sweep), gh_viterbi_bigram_online_wide.hip (the carried wide
+// bigram sweep), gh_online_settle.hip (commit, tail) and gh_online_wide_settle.hip (the two walks of commit and tail over a
+// wide session's history) share.
 #pragma once
 #include "gh_internal.h"
 #include "gh_host.h"
@@ -17,7 +18,8 @@ struct gh_online_anchor {
     int32_t col, word, state, pad;
 };
 
-// argument block of the carried sweeps (viterbi_online_kernel, viterbi_bigram_online_kernel, viterbi_online_wide_kernel)
+// argument block of the carried sweeps (viterbi_online_kernel, viterbi_bigram_online_kernel, viterbi_online_wide_kernel,
+// viterbi_bigram_online_wide_kernel)
 struct gh_online_args {
     const gh_layerform* lf;
     const void* nll;
@@ -68,7 +70,8 @@ struct gh_online {
     bool wide;                     // the graph is a word loop of 17 .. 64 words (gh_online_create_wide[_settle]): lane = word, a wave
                                    // per stream, one 32-bit decision word per column and lane.  From gh_online_create_wide: full
                                    // history, no settled prefix; from gh_online_create_wide_settle: `settles`, and a ring of columns
-                                   // where it has a window
+                                   // where it has a window.  With `bigram` (gh_online_create_bigram_wide): the WIDE BIGRAM form, the
+                                   // same state and history shapes, the records of viterbi_bigram_wide_kernel; full history only
     int64_t n_streams, max_frames, hist_stride;
     int64_t window;                // > 0: the history is a ring that holds `window` unsettled frames (gh_online_create_window)
     int32_t ring_words;            // decision words per lane in a stream's history: word index i lives at i % ring_words
@@ -100,6 +103,11 @@ int gh_launch_online_bigram(gh_ctx* ctx, const gh_online_args& a, const gh_layer
 int gh_launch_online_wide_end(gh_ctx* ctx, const gh_online* on, const int64_t* d_ids, const int64_t* d_utt_off, int64_t n,
                               double* d_end_cost, int32_t* d_best_end);
 int gh_launch_online_wide(gh_ctx* ctx, const gh_online_args& a, const gh_layerform& f, bool f64);
+// ... and for a wide BIGRAM session (gh_viterbi_bigram_online_wide.hip): one wave per stream, four streams per block around one
+// LDS image of `wide`'s word-to-word costs; the same history addressing
+int gh_launch_online_bigram_wide_end(gh_ctx* ctx, const gh_online* on, const int64_t* d_ids, const int64_t* d_utt_off, int64_t n,
+                                     double* d_end_cost, int32_t* d_best_end);
+int gh_launch_online_bigram_wide(gh_ctx* ctx, const gh_online_args& a, const gh_layerform& f, const gh_bigram_wide* wide, bool f64);
 // The settle walk (settle) or the segment walk of a wide session that settles (gh_online_wide_settle.hip); launch_settle of
 // gh_online_settle.hip hands over to it where the graph has more than GH_LAYERS_ROWW words
 int gh_launch_online_wide_settle(gh_ctx* ctx, const gh_settle_args& a, const gh_layerform& f, bool settle, const char* who);

@@ -32,6 +32,10 @@
 // over to the wide one by itself.  One made by gh_online_create_wide keeps its full history and has no commit;
 // gh_online_create_wide_settle makes one that settles (gh_online_wide_settle.hip: the settle walk over 64 word lanes) and,
 // with a window, keeps the unsettled tail in a ring of columns.
+//
+// ... and the WIDE BIGRAM form (gh_online_create_bigram_wide, on->wide && on->bigram: the bigram grammar with 17 .. 64 words):
+// the carried sweep and the end kernel of gh_viterbi_bigram_online_wide.hip, the history in the one-shot wide bigram kernel's
+// layout, the back-trace of gh_viterbi_bigram_wide.hip.  Full history only: no commit, no window.
 #include "gh_online.h"
 #include "gh_viterbi.h"
 #include "gh_wave.h"
@@ -343,6 +347,72 @@ int online_create_wide(gh_ctx* ctx, const gh_lattices* lat, int64_t n_streams, i
     return GH_OK;
 }
 
+// a WIDE BIGRAM session (gh_viterbi_bigram_online_wide.hip): the bigram grammar with 17 .. 64 words of 2 .. 8 states, a wave
+// per stream.  State [stream][N][64] doubles, no open word, and the full history in the one-shot wide bigram kernel's layout
+// -- gh_bigram_wide_bp_entries(max_frames) uint16 units, 256 B per frame, per stream; a ring that is never filled, no anchors:
+// the session does not settle
+int online_create_bigram_wide(gh_ctx* ctx, const gh_lattices* lat, int64_t n_streams, int64_t max_frames, gh_online** out) {
+    const char* const who = "gh_online_create_bigram_wide";
+    GH_REQUIRE(ctx && lat && out, "%s: NULL argument", who);
+    *out = nullptr;
+    GH_REQUIRE(n_streams >= 1 && n_streams <= 0x7fffffff, "%s: n_streams=%lld", who, (long long)n_streams);
+    GH_REQUIRE(max_frames >= 1 && max_frames <= 0x7fffffff, "%s: max_frames=%lld", who, (long long)max_frames);
+    const char* why = nullptr;
+    if (lat->L != 1 || lat->deferred_src) why = "several graphs (one graph serves all streams)";
+    else if (lat->beam > 0) why = "a rank beam is set on the graph";
+    else if (lat->bigram_ok) why = "a bigram grammar of 16 words or fewer (gh_online_create_bigram takes it)";
+    else if (lat->layers_ok && lat->h_layers.loop)
+        why = lat->h_layers.W > GH_LAYERS_ROWW ? "a word-loop graph (gh_online_create_wide takes it)" : "a word-loop graph (gh_online_create takes it)";
+    else if (lat->layers_ok) why = "a K-layer word lattice";
+    else if (!lat->bigram_wide_ok) why = "a graph that is not in wide bigram form (more than 64 words, and more than 8 states per word, are not)";
+    if (why) {
+        gh_set_error("%s: wide online bigram decoding takes the bigram grammar with %d to %d words of 2 to 8 states, not %s", who,
+                     GH_LAYERS_ROWW + 1, GH_LAYERS_MAXW, why);
+        return GH_ERR_UNSUPPORTED;
+    }
+    GH_REQUIRE(lat->d_bigram_wide, "%s: internal: wide bigram form without its cost table", who);
+    const gh_layerform& f = lat->h_layers;
+    auto pad = [](size_t b) { return (b + 255) & ~size_t(255); };
+    // max_frames < 2^31: the stride (128 uint16 units per frame) fits gh_layers_args::bp_off with room to spare; streams x
+    // stride is checked before anything is allocated
+    const int64_t stride = (int64_t)gh_bigram_wide_bp_entries(max_frames);
+    const size_t stream_bytes = (size_t)stride * 2 + (size_t)f.N * 64 * sizeof(double) + sizeof(gh_online_slot);
+    if ((size_t)n_streams > (SIZE_MAX / 2 - 1024) / stream_bytes) {
+        gh_set_error("%s: %lld streams x %lld frames (%.0f bytes): the size does not fit a size_t", who, (long long)n_streams,
+                     (long long)max_frames, (double)n_streams * (double)stream_bytes);
+        return GH_ERR_NOMEM;
+    }
+    GH_HIP(hipSetDevice(ctx->device));
+    gh_online* on = new gh_online();
+    on->ctx = ctx; on->lat = lat; on->bigram = true; on->settles = false; on->wide = true; on->n_streams = n_streams;
+    on->max_frames = max_frames;
+    on->window = 0;
+    on->ring_words = 0x7fffffff;                                           // (columns; full history: never filled)
+    on->hist_stride = stride;
+    on->d_arena = nullptr; on->h_slots = nullptr; on->copied = nullptr; on->copy_pending = false;
+    on->d_open = nullptr; on->d_anchor = nullptr;
+    on->frames.assign((size_t)n_streams, 0);
+    on->settled.assign((size_t)n_streams, 0);
+    on->seen.assign((size_t)n_streams, 0);
+    const size_t b_prev = pad((size_t)n_streams * f.N * 64 * sizeof(double));
+    const size_t b_hist = pad((size_t)n_streams * (size_t)stride * 2), b_slots = pad((size_t)n_streams * sizeof(gh_online_slot));
+    hipError_t e = hipMalloc(&on->d_arena, b_prev + b_hist + b_slots);
+    if (e == hipSuccess) e = hipHostMalloc((void**)&on->h_slots, b_slots, hipHostMallocDefault);
+    if (e == hipSuccess) e = hipEventCreateWithFlags(&on->copied, hipEventDisableTiming);
+    if (e != hipSuccess) {
+        gh_set_error("%s: %lld streams x %lld frames (%zu bytes): %s", who, (long long)n_streams, (long long)max_frames,
+                     b_prev + b_hist + b_slots, hipGetErrorString(e));
+        gh_online_destroy(on);
+        return e == hipErrorOutOfMemory ? GH_ERR_NOMEM : GH_ERR_HIP;
+    }
+    char* p = static_cast<char*>(on->d_arena);
+    on->d_prev = reinterpret_cast<double*>(p); p += b_prev;
+    on->d_hist = reinterpret_cast<uint16_t*>(p); p += b_hist;
+    on->d_slots = reinterpret_cast<gh_online_slot*>(p);
+    *out = on;
+    return GH_OK;
+}
+
 }  // namespace
 
 int gh_launch_online_end(gh_ctx* ctx, const gh_online* on, const int64_t* d_ids, const int64_t* d_utt_off, int64_t n, double* d_end_cost,
@@ -369,6 +439,10 @@ extern "C" int gh_online_create_wide(gh_ctx* ctx, const gh_lattices* lat, int64_
 extern "C" int gh_online_create_wide_settle(gh_ctx* ctx, const gh_lattices* lat, int64_t n_streams, int64_t frames, int window,
                                             gh_online** out) {
     return online_create_wide(ctx, lat, n_streams, frames, true, window != 0, out);
+}
+
+extern "C" int gh_online_create_bigram_wide(gh_ctx* ctx, const gh_lattices* lat, int64_t n_streams, int64_t max_frames, gh_online** out) {
+    return online_create_bigram_wide(ctx, lat, n_streams, max_frames, out);
 }
 
 extern "C" int gh_online_create_window(gh_ctx* ctx, const gh_lattices* lat, int64_t n_streams, int64_t window_frames, gh_online** out) {
@@ -466,7 +540,8 @@ extern "C" int gh_online_push(gh_ctx* ctx, gh_online* on, const gh_batch* b, con
     memset(&a, 0, sizeof a);
     a.lf = on->lat->d_layers; a.nll = b->nll; a.S = b->nll_S; a.slots = on->d_slots; a.n_slots = (int64_t)slots.size();
     a.prev = on->d_prev; a.open = on->d_open; a.hist = on->d_hist; a.hist_stride = on->hist_stride; a.ring_words = on->ring_words;
-    const int rc = on->wide ? gh_launch_online_wide(ctx, a, f, b->dtype == GH_F64)
+    const int rc = on->wide && on->bigram ? gh_launch_online_bigram_wide(ctx, a, f, on->lat->d_bigram_wide, b->dtype == GH_F64)
+                 : on->wide ? gh_launch_online_wide(ctx, a, f, b->dtype == GH_F64)
                  : on->bigram ? gh_launch_online_bigram(ctx, a, f, b->dtype == GH_F64) : launch_online(ctx, a, f, b->dtype == GH_F64);
     if (rc) return rc;
     for (const gh_online_slot& s : slots) on->frames[(size_t)s.stream] += s.count;
@@ -524,25 +599,28 @@ extern "C" int gh_online_result_timed(gh_ctx* ctx, gh_online* on, int64_t n, con
         GH_HIP(hipMemcpyAsync(d_labeloff, label_off, (size_t)(n + 1) * 8, hipMemcpyHostToDevice, st));
     }
     if (path) GH_HIP(hipMemcpyAsync(d_pathoff, path_off, (size_t)(n + 1) * 8, hipMemcpyHostToDevice, st));
-    rc = on->wide ? gh_launch_online_wide_end(ctx, on, d_ids, d_uttoff, n, d_endcost, d_best)
+    rc = on->wide && on->bigram ? gh_launch_online_bigram_wide_end(ctx, on, d_ids, d_uttoff, n, d_endcost, d_best)
+       : on->wide ? gh_launch_online_wide_end(ctx, on, d_ids, d_uttoff, n, d_endcost, d_best)
        : on->bigram ? gh_launch_online_bigram_end(ctx, on, d_ids, d_uttoff, n, d_endcost, d_best)
                     : gh_launch_online_end(ctx, on, d_ids, d_uttoff, n, d_endcost, d_best);
     if (rc) return rc;
     // the one-shot decode's own back-trace on the history: utterance i = stream ids[i], its decision words at bp_off[i]
-    // (a wide session: gh_launch_lattice_backtrace hands over to the wide loop back-trace, f.W > GH_LAYERS_ROWW)
+    // (a wide session: gh_launch_lattice_backtrace hands over to the wide loop back-trace, f.W > GH_LAYERS_ROWW, and
+    //  gh_launch_bigram_backtrace, given the cost table of the wide bigram form, to the wide bigram one; a narrow bigram
+    //  session has no such table: null)
     gh_layers_args c;
     memset(&c, 0, sizeof c);
     c.lf = lat->d_layers; c.end_slot = lat->d_lf_end_slot; c.end_rows = lat->d_end_rows; c.n_end = n_end; c.S = 0;
     c.utt_off = d_uttoff; c.bp = on->d_hist; c.bp_off = d_bpoff; c.best_end = d_best; c.flag = d_flag;
     if (path) {
         c.path = d_path; c.path_off = d_pathoff; c.path_len = d_pathlen;
-        rc = on->bigram ? gh_launch_bigram_backtrace(ctx, c, f, 0, n) : gh_launch_lattice_backtrace(ctx, c, f, 0, n);
+        rc = on->bigram ? gh_launch_bigram_backtrace(ctx, c, f, 0, n, false, lat->d_bigram_wide) : gh_launch_lattice_backtrace(ctx, c, f, 0, n);
         if (rc) return rc;
     }
     if (labels) {
         c.row_label = d_rowlabel; c.labels = d_labels; c.label_off = d_labeloff; c.n_labels = d_nlabels;
         if (d_begins) c.path = d_begins;                    // timed label mode: the begins go where a path launch has its path
-        rc = on->bigram ? gh_launch_bigram_backtrace(ctx, c, f, 0, n, d_begins != nullptr)
+        rc = on->bigram ? gh_launch_bigram_backtrace(ctx, c, f, 0, n, d_begins != nullptr, lat->d_bigram_wide)
                         : gh_launch_lattice_backtrace(ctx, c, f, 0, n, d_begins != nullptr);
         if (rc) return rc;
     }

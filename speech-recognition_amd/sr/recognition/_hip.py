@@ -180,6 +180,7 @@ SIGNATURES = {
     "gh_online_create_bigram_settle": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.POINTER(C.c_void_p)]),
     "gh_online_create_wide": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.POINTER(C.c_void_p)]),
     "gh_online_create_wide_settle": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.POINTER(C.c_void_p)]),
+    "gh_online_create_bigram_wide": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.POINTER(C.c_void_p)]),
     "gh_online_commit": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, _c_i64p, _c_i64p, _c_i32p, _c_i32p, _c_i64p, _c_i32p]),
     "gh_online_commit_timed": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, _c_i64p, _c_i64p, _c_i32p, _c_i32p, _c_i64p, _c_i32p, _c_i32p]),
     "gh_online_tail": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, _c_i64p, _c_f64p, _c_i32p, _c_i32p, _c_i32p, _c_i64p, _c_i32p]),
@@ -1716,6 +1717,47 @@ class OnlineWideSession(OnlineSession):
         """The parent's `tail` where the session settles; otherwise `Unsupported` (the library's own refusal)."""
         if self.settles:
             return super().tail(ids, row_label, max_labels, want_begin)
+        self._refused(self.ctx.lib.gh_online_tail(self.ctx.h, self.h, 0, None, None, None, None, None, None, None))
+
+
+class OnlineBigramWideSession(OnlineSession):
+    """Online decode over ONE graph in the wide bigram form, the bigram grammar with 17 to 64 words of 2 to 8 states
+    (gh_online_create_bigram_wide): one wave per stream, four streams per block around one LDS image of the word-to-word
+    costs.  `push`, `result` (labels, begins, paths), `reset` and `frames` are the parent's, and `result` is bitwise the
+    one-shot bigram decode of the frames a stream has taken.  A loop graph, a bigram graph of 16 words or fewer (that is
+    `OnlineBigramSession`'s), a K-layer lattice, a beam or several graphs raise `Unsupported`.
+    The session keeps its full history -- 256 B per frame and stream, `max_frames` is a hard capacity -- and does not
+    settle: `commit` and `tail` raise `Unsupported`, and there is no windowed form."""
+
+    settles = False
+
+    def __init__(self, ctx, lat, n_streams, max_frames):
+        self.ctx, self.lat = ctx, lat
+        self.n_streams = int(n_streams)
+        self.max_frames = int(max_frames)
+        self.window = None
+        h = C.c_void_p()
+        rc = ctx.lib.gh_online_create_bigram_wide(ctx.h, lat.h, self.n_streams, self.max_frames, C.byref(h))
+        if rc == GH_ERR_UNSUPPORTED:
+            raise Unsupported(ctx.lib.gh_last_error().decode("utf-8", "replace"))
+        _check(ctx.lib, rc)
+        self.h = h
+        self.n_end, self.R = int(lat.n_end[0]), int(lat.R[0])
+        self._nlev = lat.path_cap(0, 1)
+
+    def _refused(self, rc):
+        if rc == GH_ERR_UNSUPPORTED:
+            raise Unsupported(self.ctx.lib.gh_last_error().decode("utf-8", "replace"))
+        _check(self.ctx.lib, rc)
+        raise Unsupported("a wide bigram session keeps its full history and does not settle: result() gives the running hypothesis")
+
+    def commit(self, ids=None, row_label=None, max_labels=None, want_begin=False):
+        """`Unsupported` (the library's own refusal: a session from gh_online_create_bigram_wide does not settle)."""
+        settled = np.zeros(1, dtype=np.int64)
+        self._refused(self.ctx.lib.gh_online_commit(self.ctx.h, self.h, 0, None, _ptr(settled, _c_i64p), None, None, None, None))
+
+    def tail(self, ids=None, row_label=None, max_labels=None, want_begin=False):
+        """`Unsupported` (the library's own refusal)."""
         self._refused(self.ctx.lib.gh_online_tail(self.ctx.h, self.h, 0, None, None, None, None, None, None, None))
 
 

@@ -356,7 +356,8 @@ class ContinuousDecoder:
     matrix (`bigram[v, w]`: word w after word v, +inf = forbidden) with optional start costs `initial` [W], or a
     `sr.langmodel.BigramModel`, whose `costs(lm_scale)` are then used.  Up to 16 words of 2..8, 12 or 16 states
     run on the bigram-form kernel, 17 to 64 words of 2..8 states on the wide one (a wave per utterance, lane = word);
-    anything else decodes on the row-per-lane kernels, same results.  (`online_bigram` stops at 16 words.)"""
+    anything else decodes on the row-per-lane kernels, same results.  (`online_bigram` takes up to 16 words, and 17 to 64
+    with `wide=True`.)"""
 
     def __init__(self, models, n_layers=7, device=None, dtype=np.float64, grammar="layers", word_penalty=0.0, ctx=None,
                  bigram=None, initial=None, lm_scale=1.0):
@@ -443,15 +444,20 @@ class ContinuousDecoder:
         return OnlineDecoder(self, n_streams, max_frames, window, frontend, endpointer, times, settle)
 
 
-    def online_bigram(self, n_streams, max_frames=None, window=None, frontend=None, endpointer=None, times=False, settle=False):
+    def online_bigram(self, n_streams, max_frames=None, window=None, frontend=None, endpointer=None, times=False, settle=False,
+                      wide=False):
         """An `OnlineBigramDecoder` of `n_streams` live utterances sharing this decoder's packed mixtures and bigram graph
         (grammar="bigram" only: anything else raises `_hip.Unsupported` before the GPU is touched).  Exactly one of
         `max_frames` (utterances of up to that many frames, whole history kept) and `window` (utterances of any length,
         history for that many unsettled frames) must be given.  The settled prefix (`commit`, `settled`,
         `settled_times`) is opt-in: `window=` implies it, `max_frames=..., settle=True` asks for it; without either the
         decoder refuses those three calls.  frontend / endpointer / times: as in `online`.  The language-model costs
-        (`bigram`, `initial`, `lm_scale`) are in the graph; nothing is passed again."""
-        return OnlineBigramDecoder(self, n_streams, max_frames, window, frontend, endpointer, times, settle)
+        (`bigram`, `initial`, `lm_scale`) are in the graph; nothing is passed again.  wide=True lets a decoder of more
+        than 16 words (up to 64, of 2..8 states) run on the wide bigram session: `max_frames` only, full history, nothing
+        settles (`window=` and `settle=True` raise `_hip.Unsupported` before the GPU is touched).  It is a permission, not
+        a demand: a decoder of up to 16 words is served as without it, and without it a larger decoder is refused as
+        before."""
+        return OnlineBigramDecoder(self, n_streams, max_frames, window, frontend, endpointer, times, settle, wide)
 
 
 class _OnlineStreams:
@@ -878,9 +884,22 @@ class OnlineBigramDecoder(OnlineDecoder):
 
     With `window=`, or with `max_frames=..., settle=True`, `commit`, `settled`, `settled_times`, the windowed `result`
     (no paths), the window check of a push and `push_recording`'s commit after every tick are `OnlineDecoder`'s own,
-    unchanged; there is no forced commit either."""
+    unchanged; there is no forced commit either.
 
-    def __init__(self, decoder, n_streams, max_frames=None, window=None, frontend=None, endpointer=None, times=False, settle=False):
+    MORE THAN 16 WORDS.  `online_bigram(..., wide=True)` lets a decoder of 17 to 64 words (2..8 states per word) run on the
+    wide bigram session (gh_online_create_bigram_wide: one wave per stream, lane = word, the word-to-word costs in LDS):
+
+        on = dec.online_bigram(n_streams=64, max_frames=3000, times=True, wide=True)
+
+    with the same `push` / `push_batch` / `push_audio` / `push_recording` / `result` / `finish` / `reset` / `frames` and
+    word times, and `result` is bitwise the one-shot decode of the frames pushed so far.  It keeps the whole history (256 B
+    per frame and stream) and nothing settles: the settled prefix of a wide bigram session is not built yet, so `window=`
+    and `settle=True` raise `_hip.Unsupported` before the GPU is touched, and `commit`, `settled` and `settled_times` are
+    refused.  `wide=True` is a permission, not a demand: a decoder of up to 16 words is served exactly as without it.
+    Without it a decoder of more than 16 words is refused by the library, as before."""
+
+    def __init__(self, decoder, n_streams, max_frames=None, window=None, frontend=None, endpointer=None, times=False, settle=False,
+                 wide=False):
         if decoder.grammar != "bigram":
             raise _hip.Unsupported("online_bigram takes the bigram grammar (grammar='bigram'), not %r%s"
                                    % (decoder.grammar, " (online takes it)" if decoder.grammar == "loop" else ""))
@@ -888,6 +907,11 @@ class OnlineBigramDecoder(OnlineDecoder):
             raise ValueError("exactly one of max_frames and window must be given")
         if int(n_streams) < 1 or int(window if max_frames is None else max_frames) < 1:
             raise ValueError("n_streams and max_frames / window must be positive")
+        # more than 16 words, and the caller allows it: the wide bigram session (a wave per stream), full history only
+        self.wide = bool(wide) and int(np.max(decoder.row_state)) // int(decoder.n) + 1 > 16
+        if self.wide and (window is not None or settle):
+            raise _hip.Unsupported("the settled prefix of a wide bigram session (more than 16 words) is not built yet: "
+                                   "online_bigram(..., max_frames=, wide=True) without window= and settle=True")
         self._attach(decoder.ctx, decoder.dtype, decoder.gmm, n_streams, frontend, endpointer)
         self.decoder = decoder
         self.max_frames = None if max_frames is None else int(max_frames)
@@ -897,6 +921,8 @@ class OnlineBigramDecoder(OnlineDecoder):
         # recognises its graph in the loop form: the loop session serves it, with the same rows and the same results
         if int(decoder.lat.n_end[0]) == 1 and "bigram" not in decoder.lat.forms():
             self.session = _hip.OnlineSession(decoder.ctx, decoder.lat, self.n_streams, self.max_frames, self.window)
+        elif self.wide:
+            self.session = _hip.OnlineBigramWideSession(decoder.ctx, decoder.lat, self.n_streams, self.max_frames)
         elif not self.settles:
             self.session = _hip.OnlineBigramSession(decoder.ctx, decoder.lat, self.n_streams, self.max_frames)
         elif window is None:
