@@ -816,7 +816,7 @@ int gh_online_create_wide(gh_ctx* ctx, const gh_lattices* lat, int64_t n_streams
  * is refused as a whole, there is no forced commit, and gh_online_result* is GH_ERR_UNSUPPORTED (gh_online_tail*).  Per
  * stream (frames + 1) x 256 + 512 N B instead of max_frames x 256 + 512 N B; a commit reads one 256 B row per unsettled
  * column of a stream and the stream's 512 N B column.  Not offered beyond 16 words: a forced commit, the settled prefix of
- * a bigram session (gh_online_create_bigram_wide, below, keeps its full history), words of 12 or 16 states. */
+ * words of 12 or 16 states (a bigram session of 17 to 64 words settles through gh_online_create_bigram_wide_settle, below). */
 int gh_online_create_wide_settle(gh_ctx* ctx, const gh_lattices* lat, int64_t n_streams, int64_t frames, int window,
                                  gh_online** out);
 
@@ -833,9 +833,22 @@ int gh_online_create_wide_settle(gh_ctx* ctx, const gh_lattices* lat, int64_t n_
  * bits of predecessor word, the two bits of state 0; no open word); a size the device cannot give is GH_ERR_NOMEM, the
  * message holds the byte count.  max_frames is a hard capacity as in gh_online_create.  gh_online_push, gh_online_result*,
  * gh_online_reset, gh_online_frames and gh_online_destroy serve the session as they serve every other, with the same
- * checks.  The session keeps its FULL HISTORY and DOES NOT SETTLE: gh_online_commit* / gh_online_tail* on it are
- * GH_ERR_UNSUPPORTED, and there is no windowed form yet. */
+ * checks.  A session made by gh_online_create_bigram_wide keeps its FULL HISTORY and DOES NOT SETTLE: gh_online_commit* /
+ * gh_online_tail* on it are GH_ERR_UNSUPPORTED (gh_online_create_bigram_wide_settle makes one that does). */
 int gh_online_create_bigram_wide(gh_ctx* ctx, const gh_lattices* lat, int64_t n_streams, int64_t max_frames, gh_online** out);
+
+/* A wide bigram session WITH A SETTLED PREFIX: the same graph checks as gh_online_create_bigram_wide, and gh_online_commit* /
+ * gh_online_tail* serve it as they serve every session that settles, with the same host checks and flags (the settle walk
+ * over 64 word lanes, a wave per stream, where a first state is left through the predecessor word its own record names, and
+ * the segment walk over the wide bigram records).  window == 0: history for `frames` frames per stream in the one-shot
+ * layout, a hard capacity as above; gh_online_result* goes on covering the whole history, paths included.  window != 0:
+ * history for `frames` UNSETTLED frames per stream in a ring of frames + 1 columns (the column the anchor lies in is kept), as
+ * gh_online_create_window: a stream may run for any length, a push past the window is refused as a whole, there is no forced
+ * commit, and gh_online_result* is GH_ERR_UNSUPPORTED (gh_online_tail*).  Per stream (frames + 1) x 256 + 512 N B instead of
+ * max_frames x 256 + 512 N B; a commit reads one 256 B row per unsettled column of a stream and the stream's 512 N B column.
+ * Not offered beyond 16 words: a forced commit, words of 12 or 16 states. */
+int gh_online_create_bigram_wide_settle(gh_ctx* ctx, const gh_lattices* lat, int64_t n_streams, int64_t frames, int window,
+                                        gh_online** out);
 
 /* ------------------------------------------------ online isolated-word recognition: A5 while the audio is still arriving
  * HMM.evaluate (hmm.py:126-135) of every word model, carried across the chunks of n_streams live utterances: the cost of a

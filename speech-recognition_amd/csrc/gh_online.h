@@ -1,7 +1,7 @@
 // The online session (gh_online_*): what gh_viterbi_online.hip (create, push, result), gh_viterbi_bigram_online.hip (the carried
 // bigram sweep), gh_viterbi_online_wide.hip (the carried wide loop sweep), gh_viterbi_bigram_online_wide.hip (the carried wide
-// bigram sweep), gh_online_settle.hip (commit, tail) and gh_online_wide_settle.hip (the two walks of commit and tail over a
-// wide session's history) share.
+// bigram sweep), gh_online_settle.hip (commit, tail), gh_online_wide_settle.hip (the two walks of commit and tail over a
+// wide session's history) and gh_online_bigram_wide_settle.hip (the same two walks over a wide bigram session's) share.
 #pragma once
 #include "gh_internal.h"
 #include "gh_host.h"
@@ -39,7 +39,8 @@ struct gh_settle_task {
     int32_t stream, T, has_anchor, pad;
 };
 
-// argument block of the settle and segment walks (gh_online_settle.hip; gh_online_wide_settle.hip for a wide session)
+// argument block of the settle and segment walks (gh_online_settle.hip; gh_online_wide_settle.hip for a wide session,
+// gh_online_bigram_wide_settle.hip for a wide bigram one, whose segment walk takes the cost table as a second kernel argument)
 struct gh_settle_args {
     const gh_layerform* lf;
     const int32_t* end_rows;
@@ -70,8 +71,10 @@ struct gh_online {
     bool wide;                     // the graph is a word loop of 17 .. 64 words (gh_online_create_wide[_settle]): lane = word, a wave
                                    // per stream, one 32-bit decision word per column and lane.  From gh_online_create_wide: full
                                    // history, no settled prefix; from gh_online_create_wide_settle: `settles`, and a ring of columns
-                                   // where it has a window.  With `bigram` (gh_online_create_bigram_wide): the WIDE BIGRAM form, the
-                                   // same state and history shapes, the records of viterbi_bigram_wide_kernel; full history only
+                                   // where it has a window.  With `bigram` (gh_online_create_bigram_wide[_settle]): the WIDE BIGRAM
+                                   // form, the same state and history shapes, the records of viterbi_bigram_wide_kernel; full history
+                                   // and no settled prefix from gh_online_create_bigram_wide, `settles` (and a ring of columns where
+                                   // it has a window) from gh_online_create_bigram_wide_settle
     int64_t n_streams, max_frames, hist_stride;
     int64_t window;                // > 0: the history is a ring that holds `window` unsettled frames (gh_online_create_window)
     int32_t ring_words;            // decision words per lane in a stream's history: word index i lives at i % ring_words
@@ -111,3 +114,7 @@ int gh_launch_online_bigram_wide(gh_ctx* ctx, const gh_online_args& a, const gh_
 // The settle walk (settle) or the segment walk of a wide session that settles (gh_online_wide_settle.hip); launch_settle of
 // gh_online_settle.hip hands over to it where the graph has more than GH_LAYERS_ROWW words
 int gh_launch_online_wide_settle(gh_ctx* ctx, const gh_settle_args& a, const gh_layerform& f, bool settle, const char* who);
+// ... and of a wide BIGRAM session that settles (gh_online_bigram_wide_settle.hip); launch_settle hands over to it where the
+// graph is in the wide bigram form, `wide` is the graph's cost table (the segment walk reads its arc masks)
+int gh_launch_online_bigram_wide_settle(gh_ctx* ctx, const gh_settle_args& a, const gh_layerform& f, const gh_bigram_wide* wide,
+                                        bool settle, const char* who);

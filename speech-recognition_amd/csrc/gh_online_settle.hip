@@ -21,7 +21,8 @@
 // online_bigram_settle_kernel, online_bigram_segment_kernel -- the same two walks over the records of a bigram session that
 // settles (gh_online_create_bigram_settle), further down.
 // A WIDE session that settles (gh_online_create_wide_settle: 17 .. 64 words, a wave per stream) has its two walks in
-// gh_online_wide_settle.hip; the host side below -- every check, the task table, the flags -- is the same for all three.
+// gh_online_wide_settle.hip, and a WIDE BIGRAM session that settles (gh_online_create_bigram_wide_settle) in
+// gh_online_bigram_wide_settle.hip; the host side below -- every check, the task table, the flags -- is the same for all four.
 // Bit layout: gh_loop_hb / gh_loop_cpw (gh_viterbi.h); tie rules: the LOOP branch of lattice_backtrace_kernel.  A finite
 // cell has only finite predecessors, so the "+inf: first existing arc" fallback is never taken by the settle walk; the
 // segment walk keeps it, because the chosen end of a stream may be a +inf cell (the one-shot decode's rule for it).
@@ -508,8 +509,11 @@ int launch_bigram_settle(gh_ctx* ctx, const gh_settle_args& a, const gh_layerfor
 }
 
 // the form dispatch of both walks: the records of a bigram session (gh_layerform.loop == 2) have their own kernels, and so
-// has the history of a wide session (more than GH_LAYERS_ROWW words: gh_online_wide_settle.hip)
-int launch_settle(gh_ctx* ctx, const gh_settle_args& a, const gh_layerform& f, bool settle, const char* who) {
+// has the history of a wide session (more than GH_LAYERS_ROWW words: gh_online_wide_settle.hip).  A graph in the WIDE BIGRAM
+// form has loop == 2 as well and goes first: gh_online_bigram_wide_settle.hip, with the graph's cost table
+int launch_settle(gh_ctx* ctx, const gh_settle_args& a, const gh_lattices* lat, bool settle, const char* who) {
+    const gh_layerform& f = lat->h_layers;
+    if (lat->bigram_wide_ok) return gh_launch_online_bigram_wide_settle(ctx, a, f, lat->d_bigram_wide, settle, who);
     if (f.loop == 2) return launch_bigram_settle(ctx, a, f, settle, who);
     if (f.W > GH_LAYERS_ROWW) return gh_launch_online_wide_settle(ctx, a, f, settle, who);
     const dim3 blk(64);
@@ -573,7 +577,6 @@ extern "C" int gh_online_commit_timed(gh_ctx* ctx, gh_online* on, int64_t n, con
     if (rc) return rc;
     if (n <= 0) return GH_OK;
     const gh_lattices* lat = on->lat;
-    const gh_layerform& f = lat->h_layers;
     const int R = lat->lat[0].R;
     GH_HIP(hipSetDevice(ctx->device));
     int* d_flag;
@@ -600,9 +603,9 @@ extern "C" int gh_online_commit_timed(gh_ctx* ctx, gh_online* on, int64_t n, con
     a.hist_stride = on->hist_stride; a.ring_words = on->ring_words; a.anchor = on->d_anchor; a.cand = d_cand;
     a.row_label = d_rowlabel; a.labels = d_labels; a.label_off = d_labeloff; a.n_labels = d_nlabels; a.settled_frames = d_settled;
     a.flag = d_flag; a.begins = d_begins;
-    rc = launch_settle(ctx, a, f, true, "gh_online_commit");
+    rc = launch_settle(ctx, a, lat, true, "gh_online_commit");
     if (rc) return rc;
-    rc = launch_settle(ctx, a, f, false, "gh_online_commit");
+    rc = launch_settle(ctx, a, lat, false, "gh_online_commit");
     if (rc) return rc;
     int flag = 0;
     std::vector<int64_t> h_settled((size_t)n);
@@ -655,7 +658,6 @@ extern "C" int gh_online_tail_timed(gh_ctx* ctx, gh_online* on, int64_t n, const
     if (rc) return rc;
     if (n <= 0) return GH_OK;
     const gh_lattices* lat = on->lat;
-    const gh_layerform& f = lat->h_layers;
     const int n_end = lat->lat[0].n_end, R = lat->lat[0].R;
     std::vector<int64_t> h_ids((size_t)n), utt_off((size_t)n + 1, 0);
     for (int64_t i = 0; i < n; ++i) {
@@ -684,7 +686,8 @@ extern "C" int gh_online_tail_timed(gh_ctx* ctx, gh_online* on, int64_t n, const
         GH_HIP(hipMemcpyAsync(d_rowlabel, row_label, (size_t)R * 4, hipMemcpyHostToDevice, st));
         GH_HIP(hipMemcpyAsync(d_labeloff, label_off, (size_t)(n + 1) * 8, hipMemcpyHostToDevice, st));
     }
-    rc = on->wide ? gh_launch_online_wide_end(ctx, on, d_ids, d_uttoff, n, d_endcost, d_best)
+    rc = on->wide && on->bigram ? gh_launch_online_bigram_wide_end(ctx, on, d_ids, d_uttoff, n, d_endcost, d_best)
+       : on->wide ? gh_launch_online_wide_end(ctx, on, d_ids, d_uttoff, n, d_endcost, d_best)
        : on->bigram ? gh_launch_online_bigram_end(ctx, on, d_ids, d_uttoff, n, d_endcost, d_best)
                     : gh_launch_online_end(ctx, on, d_ids, d_uttoff, n, d_endcost, d_best);
     if (rc) return rc;
@@ -695,7 +698,7 @@ extern "C" int gh_online_tail_timed(gh_ctx* ctx, gh_online* on, int64_t n, const
         a.hist_stride = on->hist_stride; a.ring_words = on->ring_words; a.anchor = on->d_anchor; a.best_end = d_best;
         a.row_label = d_rowlabel; a.labels = d_labels; a.label_off = d_labeloff; a.n_labels = d_nlabels; a.flag = d_flag;
         a.begins = d_begins;
-        rc = launch_settle(ctx, a, f, false, "gh_online_tail");
+        rc = launch_settle(ctx, a, lat, false, "gh_online_tail");
         if (rc) return rc;
     }
     int flag = 0;

@@ -25,9 +25,10 @@
 // its emissions, and its block reads the 32 KB of costs once.
 //
 // THE RING.  A stream owns its wave, so the column, its ring position and the wrap are wave-uniform: the position starts from
-// t0 % ring_cols once per launch and moves on by compare-and-subtract, as in viterbi_online_wide_kernel.  The one session
-// there is (gh_online_create_bigram_wide) keeps its full history and does not settle: gh_online_commit* / gh_online_tail*
-// refuse it.  NOT OFFERED: the settled prefix and a window (they need a settle walk over these records), a forced commit,
+// t0 % ring_cols once per launch and moves on by compare-and-subtract, as in viterbi_online_wide_kernel.  A session from
+// gh_online_create_bigram_wide keeps its full history and does not settle: gh_online_commit* / gh_online_tail* refuse it.  One
+// from gh_online_create_bigram_wide_settle settles, and with a window its ring holds the unsettled frames and the column the
+// anchor lies in; the settle walk over these records is in gh_online_bigram_wide_settle.hip.  NOT OFFERED: a forced commit,
 // and words of 12 or 16 states.
 // No scratch and no runtime-indexed private array for any instantiation (profiles/online_bigram_wide_kernel_resources.txt).
 #include "gh_online.h"

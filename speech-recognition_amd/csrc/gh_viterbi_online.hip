@@ -35,7 +35,10 @@
 //
 // ... and the WIDE BIGRAM form (gh_online_create_bigram_wide, on->wide && on->bigram: the bigram grammar with 17 .. 64 words):
 // the carried sweep and the end kernel of gh_viterbi_bigram_online_wide.hip, the history in the one-shot wide bigram kernel's
-// layout, the back-trace of gh_viterbi_bigram_wide.hip.  Full history only: no commit, no window.
+// layout, the back-trace of gh_viterbi_bigram_wide.hip.  One made by gh_online_create_bigram_wide keeps its full history and
+// has no commit; gh_online_create_bigram_wide_settle makes one that settles (gh_online_bigram_wide_settle.hip: the settle walk
+// over 64 word lanes with the hop through the predecessor word a record names) and, with a window, keeps the unsettled tail in
+// a ring of columns.
 #include "gh_online.h"
 #include "gh_viterbi.h"
 #include "gh_wave.h"
@@ -350,13 +353,17 @@ int online_create_wide(gh_ctx* ctx, const gh_lattices* lat, int64_t n_streams, i
 // a WIDE BIGRAM session (gh_viterbi_bigram_online_wide.hip): the bigram grammar with 17 .. 64 words of 2 .. 8 states, a wave
 // per stream.  State [stream][N][64] doubles, no open word, and the full history in the one-shot wide bigram kernel's layout
 // -- gh_bigram_wide_bp_entries(max_frames) uint16 units, 256 B per frame, per stream; a ring that is never filled, no anchors:
-// the session does not settle
-int online_create_bigram_wide(gh_ctx* ctx, const gh_lattices* lat, int64_t n_streams, int64_t max_frames, gh_online** out) {
-    const char* const who = "gh_online_create_bigram_wide";
+// the session does not settle.
+// settles (gh_online_create_bigram_wide_settle): commit and tail serve the session, which has its anchors; `max_frames` is then
+// its capacity (full history, the same layout) or, with `window`, the unsettled frames its ring of columns holds -- frames + 1
+// columns as in online_create_wide (the column the anchor lies in is kept), 128 uint16 units each
+int online_create_bigram_wide(gh_ctx* ctx, const gh_lattices* lat, int64_t n_streams, int64_t max_frames, bool settles, bool window,
+                              gh_online** out) {
+    const char* const who = settles ? "gh_online_create_bigram_wide_settle" : "gh_online_create_bigram_wide";
     GH_REQUIRE(ctx && lat && out, "%s: NULL argument", who);
     *out = nullptr;
     GH_REQUIRE(n_streams >= 1 && n_streams <= 0x7fffffff, "%s: n_streams=%lld", who, (long long)n_streams);
-    GH_REQUIRE(max_frames >= 1 && max_frames <= 0x7fffffff, "%s: max_frames=%lld", who, (long long)max_frames);
+    GH_REQUIRE(max_frames >= 1 && max_frames <= 0x7fffffff, "%s: %s=%lld", who, window ? "window_frames" : "max_frames", (long long)max_frames);
     const char* why = nullptr;
     if (lat->L != 1 || lat->deferred_src) why = "several graphs (one graph serves all streams)";
     else if (lat->beam > 0) why = "a rank beam is set on the graph";
@@ -375,8 +382,9 @@ int online_create_bigram_wide(gh_ctx* ctx, const gh_lattices* lat, int64_t n_str
     auto pad = [](size_t b) { return (b + 255) & ~size_t(255); };
     // max_frames < 2^31: the stride (128 uint16 units per frame) fits gh_layers_args::bp_off with room to spare; streams x
     // stride is checked before anything is allocated
-    const int64_t stride = (int64_t)gh_bigram_wide_bp_entries(max_frames);
-    const size_t stream_bytes = (size_t)stride * 2 + (size_t)f.N * 64 * sizeof(double) + sizeof(gh_online_slot);
+    const int64_t stride = (int64_t)gh_bigram_wide_bp_entries(max_frames + (window ? 1 : 0));
+    const size_t stream_bytes = (size_t)stride * 2 + (size_t)f.N * 64 * sizeof(double) + sizeof(gh_online_slot) +
+                                (settles ? sizeof(gh_online_anchor) : 0);
     if ((size_t)n_streams > (SIZE_MAX / 2 - 1024) / stream_bytes) {
         gh_set_error("%s: %lld streams x %lld frames (%.0f bytes): the size does not fit a size_t", who, (long long)n_streams,
                      (long long)max_frames, (double)n_streams * (double)stream_bytes);
@@ -384,10 +392,10 @@ int online_create_bigram_wide(gh_ctx* ctx, const gh_lattices* lat, int64_t n_str
     }
     GH_HIP(hipSetDevice(ctx->device));
     gh_online* on = new gh_online();
-    on->ctx = ctx; on->lat = lat; on->bigram = true; on->settles = false; on->wide = true; on->n_streams = n_streams;
-    on->max_frames = max_frames;
-    on->window = 0;
-    on->ring_words = 0x7fffffff;                                           // (columns; full history: never filled)
+    on->ctx = ctx; on->lat = lat; on->bigram = true; on->settles = settles; on->wide = true; on->n_streams = n_streams;
+    on->max_frames = window ? 0x7fffffff : max_frames;
+    on->window = window ? max_frames : 0;
+    on->ring_words = window ? (int32_t)std::min<int64_t>(max_frames + 1, 0x7fffffff) : 0x7fffffff;   // (columns; full history: never filled)
     on->hist_stride = stride;
     on->d_arena = nullptr; on->h_slots = nullptr; on->copied = nullptr; on->copy_pending = false;
     on->d_open = nullptr; on->d_anchor = nullptr;
@@ -396,19 +404,21 @@ int online_create_bigram_wide(gh_ctx* ctx, const gh_lattices* lat, int64_t n_str
     on->seen.assign((size_t)n_streams, 0);
     const size_t b_prev = pad((size_t)n_streams * f.N * 64 * sizeof(double));
     const size_t b_hist = pad((size_t)n_streams * (size_t)stride * 2), b_slots = pad((size_t)n_streams * sizeof(gh_online_slot));
-    hipError_t e = hipMalloc(&on->d_arena, b_prev + b_hist + b_slots);
+    const size_t b_anchor = settles ? pad((size_t)n_streams * sizeof(gh_online_anchor)) : 0;
+    hipError_t e = hipMalloc(&on->d_arena, b_prev + b_hist + b_slots + b_anchor);
     if (e == hipSuccess) e = hipHostMalloc((void**)&on->h_slots, b_slots, hipHostMallocDefault);
     if (e == hipSuccess) e = hipEventCreateWithFlags(&on->copied, hipEventDisableTiming);
     if (e != hipSuccess) {
         gh_set_error("%s: %lld streams x %lld frames (%zu bytes): %s", who, (long long)n_streams, (long long)max_frames,
-                     b_prev + b_hist + b_slots, hipGetErrorString(e));
+                     b_prev + b_hist + b_slots + b_anchor, hipGetErrorString(e));
         gh_online_destroy(on);
         return e == hipErrorOutOfMemory ? GH_ERR_NOMEM : GH_ERR_HIP;
     }
     char* p = static_cast<char*>(on->d_arena);
     on->d_prev = reinterpret_cast<double*>(p); p += b_prev;
     on->d_hist = reinterpret_cast<uint16_t*>(p); p += b_hist;
-    on->d_slots = reinterpret_cast<gh_online_slot*>(p);
+    on->d_slots = reinterpret_cast<gh_online_slot*>(p); p += b_slots;
+    if (settles) on->d_anchor = reinterpret_cast<gh_online_anchor*>(p);   // (read only where `settled` says a stream has one)
     *out = on;
     return GH_OK;
 }
@@ -442,7 +452,12 @@ extern "C" int gh_online_create_wide_settle(gh_ctx* ctx, const gh_lattices* lat,
 }
 
 extern "C" int gh_online_create_bigram_wide(gh_ctx* ctx, const gh_lattices* lat, int64_t n_streams, int64_t max_frames, gh_online** out) {
-    return online_create_bigram_wide(ctx, lat, n_streams, max_frames, out);
+    return online_create_bigram_wide(ctx, lat, n_streams, max_frames, false, false, out);
+}
+
+extern "C" int gh_online_create_bigram_wide_settle(gh_ctx* ctx, const gh_lattices* lat, int64_t n_streams, int64_t frames, int window,
+                                                   gh_online** out) {
+    return online_create_bigram_wide(ctx, lat, n_streams, frames, true, window != 0, out);
 }
 
 extern "C" int gh_online_create_window(gh_ctx* ctx, const gh_lattices* lat, int64_t n_streams, int64_t window_frames, gh_online** out) {

@@ -181,6 +181,7 @@ SIGNATURES = {
     "gh_online_create_wide": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.POINTER(C.c_void_p)]),
     "gh_online_create_wide_settle": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.POINTER(C.c_void_p)]),
     "gh_online_create_bigram_wide": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.POINTER(C.c_void_p)]),
+    "gh_online_create_bigram_wide_settle": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.POINTER(C.c_void_p)]),
     "gh_online_commit": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, _c_i64p, _c_i64p, _c_i32p, _c_i32p, _c_i64p, _c_i32p]),
     "gh_online_commit_timed": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, _c_i64p, _c_i64p, _c_i32p, _c_i32p, _c_i64p, _c_i32p, _c_i32p]),
     "gh_online_tail": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, _c_i64p, _c_f64p, _c_i32p, _c_i32p, _c_i32p, _c_i64p, _c_i32p]),
@@ -1726,18 +1727,27 @@ class OnlineBigramWideSession(OnlineSession):
     costs.  `push`, `result` (labels, begins, paths), `reset` and `frames` are the parent's, and `result` is bitwise the
     one-shot bigram decode of the frames a stream has taken.  A loop graph, a bigram graph of 16 words or fewer (that is
     `OnlineBigramSession`'s), a K-layer lattice, a beam or several graphs raise `Unsupported`.
-    The session keeps its full history -- 256 B per frame and stream, `max_frames` is a hard capacity -- and does not
-    settle: `commit` and `tail` raise `Unsupported`, and there is no windowed form."""
+    By default the session keeps its full history -- 256 B per frame and stream, `max_frames` is a hard capacity -- and
+    does not settle: `commit` and `tail` raise `Unsupported`.  `settle=True` (gh_online_create_bigram_wide_settle) gives it
+    the parent's `commit` and `tail`; `window=` instead of `max_frames=` implies it and keeps history for that many
+    UNSETTLED frames per stream in a ring of columns, so a stream may run for any length (`result` is then `Unsupported`:
+    no paths, use `tail`)."""
 
-    settles = False
-
-    def __init__(self, ctx, lat, n_streams, max_frames):
+    def __init__(self, ctx, lat, n_streams, max_frames=None, window=None, settle=False):
+        if (max_frames is None) == (window is None):
+            raise ValueError("exactly one of max_frames and window must be given")
         self.ctx, self.lat = ctx, lat
         self.n_streams = int(n_streams)
-        self.max_frames = int(max_frames)
-        self.window = None
+        self.max_frames = None if max_frames is None else int(max_frames)
+        self.window = None if window is None else int(window)
+        self.settles = bool(settle) or window is not None
         h = C.c_void_p()
-        rc = ctx.lib.gh_online_create_bigram_wide(ctx.h, lat.h, self.n_streams, self.max_frames, C.byref(h))
+        if self.settles:
+            rc = ctx.lib.gh_online_create_bigram_wide_settle(ctx.h, lat.h, self.n_streams,
+                                                             self.max_frames if window is None else self.window,
+                                                             int(window is not None), C.byref(h))
+        else:
+            rc = ctx.lib.gh_online_create_bigram_wide(ctx.h, lat.h, self.n_streams, self.max_frames, C.byref(h))
         if rc == GH_ERR_UNSUPPORTED:
             raise Unsupported(ctx.lib.gh_last_error().decode("utf-8", "replace"))
         _check(ctx.lib, rc)
@@ -1752,12 +1762,17 @@ class OnlineBigramWideSession(OnlineSession):
         raise Unsupported("a wide bigram session keeps its full history and does not settle: result() gives the running hypothesis")
 
     def commit(self, ids=None, row_label=None, max_labels=None, want_begin=False):
-        """`Unsupported` (the library's own refusal: a session from gh_online_create_bigram_wide does not settle)."""
+        """The parent's `commit` where the session settles (settle=True or window=); otherwise `Unsupported` (the library's
+        own refusal: a session from gh_online_create_bigram_wide does not settle)."""
+        if self.settles:
+            return super().commit(ids, row_label, max_labels, want_begin)
         settled = np.zeros(1, dtype=np.int64)
         self._refused(self.ctx.lib.gh_online_commit(self.ctx.h, self.h, 0, None, _ptr(settled, _c_i64p), None, None, None, None))
 
     def tail(self, ids=None, row_label=None, max_labels=None, want_begin=False):
-        """`Unsupported` (the library's own refusal)."""
+        """The parent's `tail` where the session settles; otherwise `Unsupported` (the library's own refusal)."""
+        if self.settles:
+            return super().tail(ids, row_label, max_labels, want_begin)
         self._refused(self.ctx.lib.gh_online_tail(self.ctx.h, self.h, 0, None, None, None, None, None, None, None))
 
 

@@ -454,9 +454,10 @@ class ContinuousDecoder:
         decoder refuses those three calls.  frontend / endpointer / times: as in `online`.  The language-model costs
         (`bigram`, `initial`, `lm_scale`) are in the graph; nothing is passed again.  wide=True lets a decoder of more
         than 16 words (up to 64, of 2..8 states) run on the wide bigram session: `max_frames` only, full history, nothing
-        settles (`window=` and `settle=True` raise `_hip.Unsupported` before the GPU is touched).  It is a permission, not
-        a demand: a decoder of up to 16 words is served as without it, and without it a larger decoder is refused as
-        before."""
+        settles (`window=` and `settle=True` raise `_hip.Unsupported` before the GPU is touched).  wide="settle" lets it
+        run there in all three forms -- `max_frames=`, `max_frames=..., settle=True` and `window=` -- with the settled
+        prefix of a narrow bigram decoder.  Both are permissions, not demands: a decoder of up to 16 words is served as
+        without them, and without them a larger decoder is refused as before.  Any other value of `wide` is a ValueError."""
         return OnlineBigramDecoder(self, n_streams, max_frames, window, frontend, endpointer, times, settle, wide)
 
 
@@ -893,10 +894,23 @@ class OnlineBigramDecoder(OnlineDecoder):
 
     with the same `push` / `push_batch` / `push_audio` / `push_recording` / `result` / `finish` / `reset` / `frames` and
     word times, and `result` is bitwise the one-shot decode of the frames pushed so far.  It keeps the whole history (256 B
-    per frame and stream) and nothing settles: the settled prefix of a wide bigram session is not built yet, so `window=`
-    and `settle=True` raise `_hip.Unsupported` before the GPU is touched, and `commit`, `settled` and `settled_times` are
-    refused.  `wide=True` is a permission, not a demand: a decoder of up to 16 words is served exactly as without it.
-    Without it a decoder of more than 16 words is refused by the library, as before."""
+    per frame and stream) and nothing settles: `wide=True` with `window=` or `settle=True` raises `_hip.Unsupported` before
+    the GPU is touched (under wide=True the settled prefix is not built yet: wide="settle" has it), and `commit`, `settled`
+    and `settled_times` are refused.  `wide=True` is a permission, not a demand: a decoder of up to 16 words is served
+    exactly as without it.  Without it a decoder of more than 16 words is refused by the library, as before.
+
+    THE SETTLED PREFIX BEYOND 16 WORDS is asked for by name (gh_online_create_bigram_wide_settle: the settle walk over 64
+    word lanes, a wave per stream, where a first state is left through the predecessor word its own record names):
+
+        on = dec.online_bigram(n_streams=64, window=400, times=True, wide="settle")         # 400 UNSETTLED frames per stream
+        on = dec.online_bigram(n_streams=64, max_frames=3000, settle=True, wide="settle")   # full history (paths), with `commit`
+        on = dec.online_bigram(n_streams=64, max_frames=3000, wide="settle")                # as wide=True: nothing settles
+
+    `wide="settle"` is a permission like `wide=True`: up to 16 words it changes nothing, beyond 16 words `window=` and
+    `settle=True` mean what they mean for a narrow bigram decoder -- `commit`, `settled`, `settled_times`, the windowed
+    `result` (no paths), the window check of a push and `push_recording`'s commit after every tick, unchanged; device memory
+    per stream is then (window + 1) x 256 B + the 512 n B column instead of max_frames x 256 B.  There is no forced commit,
+    and words of 12 or 16 states are not offered beyond 16 words.  Any other value of `wide` is a ValueError."""
 
     def __init__(self, decoder, n_streams, max_frames=None, window=None, frontend=None, endpointer=None, times=False, settle=False,
                  wide=False):
@@ -907,11 +921,15 @@ class OnlineBigramDecoder(OnlineDecoder):
             raise ValueError("exactly one of max_frames and window must be given")
         if int(n_streams) < 1 or int(window if max_frames is None else max_frames) < 1:
             raise ValueError("n_streams and max_frames / window must be positive")
-        # more than 16 words, and the caller allows it: the wide bigram session (a wave per stream), full history only
+        if not (isinstance(wide, (bool, np.bool_)) or (isinstance(wide, str) and wide == "settle")):
+            raise ValueError("wide must be False, True or 'settle', not %r" % (wide,))
+        # more than 16 words, and the caller allows it: the wide bigram session (a wave per stream); it settles, and may have
+        # a window, only where wide="settle" asked for that by name
         self.wide = bool(wide) and int(np.max(decoder.row_state)) // int(decoder.n) + 1 > 16
-        if self.wide and (window is not None or settle):
-            raise _hip.Unsupported("the settled prefix of a wide bigram session (more than 16 words) is not built yet: "
-                                   "online_bigram(..., max_frames=, wide=True) without window= and settle=True")
+        if self.wide and not isinstance(wide, str) and (window is not None or settle):
+            raise _hip.Unsupported("under wide=True the settled prefix of a wide bigram session (more than 16 words) is not built yet: "
+                                   "online_bigram(..., max_frames=, wide=True) without window= and settle=True, or "
+                                   "online_bigram(..., wide=\"settle\") with them")
         self._attach(decoder.ctx, decoder.dtype, decoder.gmm, n_streams, frontend, endpointer)
         self.decoder = decoder
         self.max_frames = None if max_frames is None else int(max_frames)
@@ -921,8 +939,12 @@ class OnlineBigramDecoder(OnlineDecoder):
         # recognises its graph in the loop form: the loop session serves it, with the same rows and the same results
         if int(decoder.lat.n_end[0]) == 1 and "bigram" not in decoder.lat.forms():
             self.session = _hip.OnlineSession(decoder.ctx, decoder.lat, self.n_streams, self.max_frames, self.window)
-        elif self.wide:
+        elif self.wide and not self.settles:
             self.session = _hip.OnlineBigramWideSession(decoder.ctx, decoder.lat, self.n_streams, self.max_frames)
+        elif self.wide and window is None:
+            self.session = _hip.OnlineBigramWideSession(decoder.ctx, decoder.lat, self.n_streams, self.max_frames, settle=True)
+        elif self.wide:
+            self.session = _hip.OnlineBigramWideSession(decoder.ctx, decoder.lat, self.n_streams, window=self.window)
         elif not self.settles:
             self.session = _hip.OnlineBigramSession(decoder.ctx, decoder.lat, self.n_streams, self.max_frames)
         elif window is None:
