@@ -38,6 +38,28 @@ void gh_set_error(const char* fmt, ...);
 #define GH_LSE_SCALE32 1.4426950408889634074
 #define GH_LSE_OFF64 (-1e300)
 #define GH_LSE_OFF32 (-1e30f)
+// K ln 2^-1075 (fp64): a scaled log-density below it is exp()'s exact +0 in the reference's linear domain (compat bit 0)
+#define GH_LSE_COMPAT_BELOW64 (-745.1332191019412 * GH_LSE_SCALE64)
+// The fp64 log-sum-exp against a PACK-TIME reference (gh_loglik_mfma.hip, BND): a component log-density never exceeds its
+// log(w * normaliser) logc_g, so mh_s = max of logc_g over
+// the switched-on components of state s bounds every accumulator of the state.  CpkRel = K (C_g - mh_s) is the addend
+// that makes the accumulators finish as y_g = K (a_g - mh_s) <= 0; the sum s = sum 2^(y_g/128) is trusted while
+// s >= thr: GH_LSE_BOUND_THR (every term within 2^-53 of the largest is then a normal number), and in compat mode
+// also the s below which the largest term COULD lie under GH_LSE_COMPAT_BELOW64 (s <= M_pad 2^(max y/128); one more
+// bit of margin for the rounding of s).  One helper for the host's and the device's packing.
+#define GH_LSE_BOUND_THR 0x1p-900
+struct gh_lse_state { double k_mh, thr; };   // K mh_s; compat-mode threshold (+inf: no switched-on component, 0: padding)
+__host__ __device__ inline gh_lse_state gh_lse_state_of(double mh, bool any_on, int M_pad) {
+    gh_lse_state e;
+    if (!any_on) { e.k_mh = 0.0; e.thr = INFINITY; return e; }
+    e.k_mh = mh * GH_LSE_SCALE64;
+    const double ex = (GH_LSE_COMPAT_BELOW64 - e.k_mh) * (1.0 / 128.0);
+    const double t = (ex > 1000.0) ? (double)INFINITY : ((ex < -1060.0) ? 0.0 : ldexp(exp2(ex - floor(ex)), (int)floor(ex)) * (2.0 * M_pad));
+    e.thr = (t > GH_LSE_BOUND_THR) ? t : GH_LSE_BOUND_THR;
+    return e;
+}
+// states the per-state table holds: every state a tile can name (mixture padding of the last tile included)
+static inline int gh_lse_states_padded(int M_pad, int n_tiles) { return n_tiles * (16 / M_pad); }   // (M_pad <= 16)
 
 struct gh_ctx {
     int device;
@@ -98,6 +120,10 @@ struct gh_gmm {
     int M_pad, n_tiles;
     double *dApk64, *dCpk64;
     float *dApk32, *dCpk32;
+    // fp64 log-sum-exp against the pack-time bound (gh_lse_state_of): CpkRel64 laid out and padded like Cpk64, one
+    // gh_lse_state per (padded) state
+    double* dCpkRel64 = nullptr;
+    gh_lse_state* dLseState64 = nullptr;
     // stamp of the parameter set (new at creation and at every in-place update): a batch remembers whose likelihoods its
     // [N, S] matrix holds (gh_batch::nll_serial), so that a kernel that reuses them as mixture denominators can tell
     uint64_t serial = 0;

@@ -96,6 +96,12 @@ struct LseK {
     __device__ __forceinline__ void pin() {
         asm volatile("" : "+v"(e3), "+v"(l4), "+v"(l3), "+v"(l2), "+v"(l1));
     }
+    // (BND) the addends of the last three Horner steps of logs() in SCALAR registers: a v_fma_f64 takes one scalar source,
+    // and theirs are two vector operands and this addend (e3 and l4 meet a scalar coefficient, so they stay in vector
+    // registers).  Six vector registers fewer: the kernel keeps the accumulators alive up to the guard and has to fit 216.
+    __device__ __forceinline__ void pin_bnd() {
+        asm volatile("" : "+v"(e3), "+v"(l4), "+s"(l3), "+s"(l2), "+s"(l1));
+    }
 };
 
 // K ln s for s in [1, M] (or NaN)
@@ -186,6 +192,49 @@ __device__ __forceinline__ void tile_lse(const V& a, int width, T& mx, T& sm, co
     sm = e;
 }
 
+// (max, sum) of a state that spans W = 2 or 4 lane groups, for BOTH column tiles at once: the even group finishes column
+// tile 0, the odd group column tile 1, so both butterflies run on the PAIR of column tiles (pair_*_split: one exchange
+// instead of one per column tile, the xor-32 level follows on the result).  mxs is the max of "this group's" column tile
+// -- what `odd ? mx1 : mx0` would select --, and one more exchange hands every lane both maxima for its exponents.
+// Same operands in the same order as tile_lse().
+template <typename T, typename V, int W>
+__device__ __forceinline__ void wide_lse(const V& acc0, const V& acc1, T& mxs, T& sm, const double* tab, const LseK& k) {
+    mxs = pair_max_split(lane_max<T, V>(acc0), lane_max<T, V>(acc1));
+    if (W >= 4) mxs = pair_max<T, 32>(mxs);
+    T mx0, mx1;
+    pair_of<16>(mxs, mx0, mx1);
+    sm = pair_sum_split(lane_terms<T, V>(acc0, mx0, tab, k), lane_terms<T, V>(acc1, mx1, tab, k));
+    if (W >= 4) sm = pair_sum<T, 32>(sm);
+}
+
+// ---- fp64 log-sum-exp against the PACK-TIME bound (BND; gh_internal.h, gh_lse_state_of) -------------------------
+// The maximum over the mixture is only a reference point.  A diagonal Gaussian's log-density a_g(x) never exceeds its
+// log(w * normaliser) logc_g, so with the addends CpkRel = K (C_g - mh_s), mh_s = max logc_g over the state's
+// switched-on components, the accumulators finish as y_g = K (a_g - mh_s) <= 0 and
+//     nll = -(K mh_s + K ln sum_g 2^(y_g/128)) / K
+// needs no maximum, no `a - max` and no cross-lane maximum exchange: 7 v_max_f64, 8 v_add_f64, 4 of 6 v_permlane16_swap
+// and the +inf select leave the tile.  exp2s() keeps its relative accuracy while its result is a normal
+// number, logs() is general in its argument.  The result is taken only where the sum s >= thr_s (the per-state table
+// staged in LDS: (K mh_s, thr_s)); when some lane of the wave has s < thr -- every term may have underflowed, or in
+// compat mode the largest term could lie below the reference's underflow limit -- the tile's epilogue is redone on the
+// same accumulators with the max-shifted form (translation invariant), K mh_s added at the end, the +inf rule on
+// max(y) + K mh_s, and the lanes with s < thr take its result: a wave-uniform branch, but a (frame, state) result never
+// depends on its neighbours in the tile.  A NaN sum compares false and stays: it poisons its own state as before.
+template <typename T, typename V> __device__ __forceinline__ T lane_terms0(const V& a, const double* tab, const LseK& k) {
+    return (exp2s(a[0], tab, k.e3) + exp2s(a[1], tab, k.e3)) + (exp2s(a[2], tab, k.e3) + exp2s(a[3], tab, k.e3));
+}
+template <typename T> __device__ __forceinline__ T nll_bnd(T k_mh, T sm, const double* tab, const LseK& k) {
+    return (k_mh + logs(sm, tab, k)) * -Dom<T>::inv_k;
+}
+// the redo: (max, sum) of the shifted accumulators -> nll
+template <typename T> __device__ __forceinline__ T nll_cold(T mx, T sm, T k_mh, const double* tab, T inf_below, const LseK& k) {
+    const T v = ((mx + logs(sm, tab, k)) + k_mh) * -Dom<T>::inv_k;
+    return (mx + k_mh < inf_below) ? T(INFINITY) : v;
+}
+__device__ __forceinline__ bool wave_any(bool p) { return __builtin_amdgcn_ballot_w64(p) != 0; }
+// first statement of a redo: keeps the compiler from turning the wave-uniform branch into both paths plus selects
+__device__ __forceinline__ void cold_block() { asm volatile("; log-sum-exp redo (max-shifted)" ::: "memory"); }
+
 // ---- opt-in epilogue with the exponentials in FP32 (gh_ctx_set_compat bit 1 / GMMHMM_LSE=f32exp; fp64 batches only).
 // The maximum, `a - max` and the final `max + log(sum)` stay fp64; the terms 2^((a - max)/128) <= 1 go through
 // v_cvt_f32_f64 + v_exp_f32, their sum and its v_log_f32 stay fp32: 2 instructions on the shared fp64 pipe per term
@@ -237,10 +286,14 @@ template <typename T> __device__ __forceinline__ global_ptr<T> uniform_ptr(const
 // S * tiles_per_state and no tile has any), so the tile loop runs without the test -- the compare, a select and part
 // of the slot address leave the pipe the MFMAs share: 155 -> 151 / 152 vector instructions per tile in <double,20,8>,
 // 61 -> 38 for M_pad = 1 -- and only the epilogue after it, which may see the model's last tile, keeps it.
-template <typename T, typename V, int MP, bool FE = false, bool CHK = true>
+// BND: the log-sum-exp against the pack-time bound (above; MP = 2 ... 16); st_tab = the LDS copy of the per-state table,
+// entry 0 = state chunk_s0.
+template <typename T, typename V, int MP, bool FE = false, bool CHK = true, bool BND = false>
 __device__ __forceinline__ void tile_epilogue(const V& acc0, const V& acc1, int t, int f, int q, int S, int RS,
                                               int chunk_s0, int tiles_per_state, T* lds, T* dummy,
-                                              const double* tab, T (&run_mx)[2], T (&run_sm)[2], T inf_below, const LseK& k) {
+                                              const double* tab, T (&run_mx)[2], T (&run_sm)[2], T inf_below, const LseK& k,
+                                              const double* st_tab) {
+    static_assert(!BND || (MP >= 2 && MP <= 16), "the bound form covers one tile per state");
     T* orow0 = lds + f * RS - chunk_s0;
     T* orow1 = orow0 + 16 * RS;
     if (MP == 1) {
@@ -252,6 +305,77 @@ __device__ __forceinline__ void tile_epilogue(const V& acc0, const V& acc1, int 
 #pragma unroll
             for (int r = 0; r < 4; ++r)
                 *((!CHK || s + r < S) ? orow + s + r : dummy) = (acc[r] < inf_below) ? T(INFINITY) : acc[r] * -Dom<T>::inv_k;
+        }
+    } else if (BND) {
+        if constexpr (BND) {
+            const double* st = st_tab - 2 * chunk_s0;
+            if (MP == 2) {
+                const int s = 8 * t + 2 * q;
+                const T km[2] = {st[2 * s], st[2 * s + 2]}, th[2] = {st[2 * s + 1], st[2 * s + 3]};
+                T v[2][2];
+                bool redo[2][2], cold = false;
+#pragma unroll
+                for (int c = 0; c < 2; ++c) {
+                    const V& acc = c ? acc1 : acc0;
+#pragma unroll
+                    for (int h = 0; h < 2; ++h) {
+                        const T e = exp2s(acc[2 * h], tab, k.e3) + exp2s(acc[2 * h + 1], tab, k.e3);
+                        redo[c][h] = e < th[h];
+                        cold |= redo[c][h];
+                        v[c][h] = nll_bnd<T>(km[h], e, tab, k);
+                    }
+                }
+                if (__builtin_expect(wave_any(cold), 0)) {
+                    cold_block();
+#pragma unroll
+                    for (int c = 0; c < 2; ++c) {
+                        const V& acc = c ? acc1 : acc0;
+#pragma unroll
+                        for (int h = 0; h < 2; ++h) {
+                            const T x0 = acc[2 * h], x1 = acc[2 * h + 1];
+                            const T m = vmax(x0, x1);
+                            const T e = exp2s(x0 - m, tab, k.e3) + exp2s(x1 - m, tab, k.e3);
+                            v[c][h] = redo[c][h] ? nll_cold<T>(m, e, km[h], tab, inf_below, k) : v[c][h];
+                        }
+                    }
+                }
+#pragma unroll
+                for (int c = 0; c < 2; ++c)
+#pragma unroll
+                    for (int h = 0; h < 2; ++h) *((!CHK || s + h < S) ? (c ? orow1 : orow0) + s + h : dummy) = v[c][h];
+            } else if (MP == 4) {
+                const int s = 4 * t + q;
+                const T km = st[2 * s], th = st[2 * s + 1];
+                const T e0 = lane_terms0<T, V>(acc0, tab, k), e1 = lane_terms0<T, V>(acc1, tab, k);
+                T v0 = nll_bnd<T>(km, e0, tab, k), v1 = nll_bnd<T>(km, e1, tab, k);
+                if (__builtin_expect(wave_any((e0 < th) | (e1 < th)), 0)) {
+                    cold_block();
+                    T mx, sm;
+                    tile_lse<T, V>(acc0, 1, mx, sm, tab, k);
+                    v0 = (e0 < th) ? nll_cold<T>(mx, sm, km, tab, inf_below, k) : v0;
+                    tile_lse<T, V>(acc1, 1, mx, sm, tab, k);
+                    v1 = (e1 < th) ? nll_cold<T>(mx, sm, km, tab, inf_below, k) : v1;
+                }
+                *((!CHK || s < S) ? orow0 + s : dummy) = v0;
+                *((!CHK || s < S) ? orow1 + s : dummy) = v1;
+            } else {
+                constexpr int width = MP / 4;  // lane groups per state: 2 or 4
+                // the even group finishes column tile 0, the odd group column tile 1 (as wide_lse): one exchange for the pair
+                T sm = pair_sum_split(lane_terms0<T, V>(acc0, tab, k), lane_terms0<T, V>(acc1, tab, k));
+                if (width >= 4) sm = pair_sum<T, 32>(sm);
+                const bool odd = q & 1;
+                const int s = (16 / MP) * t + q / width;
+                const T km = st[2 * s], th = st[2 * s + 1];
+                const bool redo = wave_any(sm < th);
+                T v = nll_bnd<T>(km, sm, tab, k);
+                if (__builtin_expect(redo, 0)) {
+                    cold_block();
+                    T mxs, smc;
+                    wide_lse<T, V, width>(acc0, acc1, mxs, smc, tab, k);
+                    v = (sm < th) ? nll_cold<T>(mxs, smc, km, tab, inf_below, k) : v;
+                }
+                *(((q & (width - 1)) < 2 && (!CHK || s < S)) ? (odd ? orow1 : orow0) + s : dummy) = v;
+            }
         }
     } else if (MP == 2) {
         const int s = 8 * t + 2 * q;
@@ -325,16 +449,8 @@ __device__ __forceinline__ void tile_epilogue(const V& acc0, const V& acc1, int 
         *((!CHK || s < S) ? orow1 + s : dummy) = nll_of<T>(mx, sm, tab, inf_below, k);
     } else if (MP <= 16) {
         constexpr int width = MP / 4;  // lane groups per state: 2 or 4
-        // The even group finishes column tile 0, the odd group column tile 1, so both butterflies run on the PAIR of
-        // column tiles (pair_*_split: one exchange instead of one per column tile, the xor-32 level follows on the
-        // result).  mxs is the max of "this group's" column tile -- what `odd ? mx1 : mx0` would select --, and one more
-        // exchange hands every lane both maxima for its exponents.  Same operands in the same order as tile_lse().
-        T mxs = pair_max_split(lane_max<T, V>(acc0), lane_max<T, V>(acc1));
-        if (width >= 4) mxs = pair_max<T, 32>(mxs);
-        T mx0, mx1;
-        pair_of<16>(mxs, mx0, mx1);
-        T sm = pair_sum_split(lane_terms<T, V>(acc0, mx0, tab, k), lane_terms<T, V>(acc1, mx1, tab, k));
-        if (width >= 4) sm = pair_sum<T, 32>(sm);
+        T mxs, sm;
+        wide_lse<T, V, width>(acc0, acc1, mxs, sm, tab, k);
         const bool odd = q & 1;
         const int s = (16 / MP) * t + q / width;
         const T v = nll_of<T>(mxs, sm, tab, inf_below, k);
@@ -375,14 +491,17 @@ __device__ __forceinline__ void tile_epilogue(const V& acc0, const V& acc1, int 
 #define GH_MF_SGB 0
 #endif
 // MULTI: the wave walks `bpw` blocks (light models); false = one block per wave, the block loop folds away.
-template <typename T, int KS, int MP, bool MULTI, bool FE = false>
+// BND: fp64 log-sum-exp against the pack-time bound (Cpk = the model's CpkRel64, st_glob = its per-state table)
+template <typename T, int KS, int MP, bool MULTI, bool FE = false, bool BND = false>
 __global__ __launch_bounds__(64, (sizeof(T) == 4 ? 3 : 1)) void loglik_mfma_kernel(const T* __restrict__ X, int64_t N, int D,
                                                          const T* __restrict__ Apk, const T* __restrict__ Cpk,
                                                          int n_tiles, int S, int M_pad, int chunk_tiles,
                                                          const double* __restrict__ tables, int tab_off,
                                                          T* __restrict__ out, int bpw,
                                                          const gh_loglik_blk* __restrict__ blk_tab, int64_t n_blk,
-                                                         const T* __restrict__ cen, T inf_below) {
+                                                         const T* __restrict__ cen, T inf_below,
+                                                         const gh_lse_state* __restrict__ st_glob, int st_off) {
+    static_assert(!BND || (sizeof(T) == 8 && !FE && MP >= 2 && MP <= 16), "the pack-time bound is for the default fp64 log-sum-exp, one tile per state");
     typedef typename Acc<T>::type V;
 #ifndef GH_MF_RING32
 #define GH_MF_RING32 2
@@ -411,6 +530,31 @@ __global__ __launch_bounds__(64, (sizeof(T) == 4 ? 3 : 1)) void loglik_mfma_kern
     const int64_t kb0 = (int64_t)blockIdx.x * (MULTI ? bpw : 1);
     int t_lo = subset ? blk_tab[kb0].t0 : 0, t_hi = n_tiles, nxt_t0 = 0;
     double* tab = reinterpret_cast<double*>(smem_raw + tab_off);  // exp / log tables (fp64 path)
+    // (BND) the per-state table (K mh_s, thr_s) of the states [s0, s0 + SC) of one output chunk, in LDS.  thr for the
+    // current compat mode: the packed value when inf_below carries the reference's underflow limit, else the plain
+    // 2^-900 (0 stays 0: mixture padding of the last tile, never redone).  A chunk is <= 71 states: two entries per lane.
+    double* st_tab = reinterpret_cast<double*>(smem_raw + st_off);
+    const int tiles_per_state = (MP <= 16) ? 1 : M_pad / 16;
+    const int SC = (MP <= 16) ? chunk_tiles * (16 / (MP <= 16 ? MP : 16)) : chunk_tiles / tiles_per_state;   // states per output chunk
+    const int st_n = n_tiles * (16 / (MP <= 16 ? MP : 16));                  // entries of st_glob (BND: MP <= 16)
+    int st_s0 = -1;
+    auto stage_states = [&](int s0) {
+        if constexpr (BND) {
+            const int cnt = (st_n - s0 < SC) ? st_n - s0 : SC;
+            const bool compat = inf_below > Dom<T>::off_test;
+            gh_lse_state e[2];
+#pragma unroll
+            for (int it = 0; it < 2; ++it) e[it] = (lane + 64 * it < cnt) ? st_glob[s0 + lane + 64 * it] : gh_lse_state{0.0, 0.0};
+#pragma unroll
+            for (int it = 0; it < 2; ++it)
+                if (lane + 64 * it < cnt) {
+                    st_tab[2 * (lane + 64 * it)] = e[it].k_mh;
+                    st_tab[2 * (lane + 64 * it) + 1] = compat ? e[it].thr : ((e[it].thr == 0.0) ? 0.0 : GH_LSE_BOUND_THR);
+                }
+            st_s0 = s0;
+        }
+    };
+    if (BND) stage_states(t_lo * (16 / (MP <= 16 ? MP : 16)));   // the first block's chunk, with the prologue's other loads
     if (sizeof(T) == 8 && MP != 1) {   // (a single-component state needs no exp / log)
         double tr[6];
 #pragma unroll
@@ -459,13 +603,11 @@ __global__ __launch_bounds__(64, (sizeof(T) == 4 ? 3 : 1)) void loglik_mfma_kern
         __syncthreads();
     };
 
-    const int tiles_per_state = (MP <= 16) ? 1 : M_pad / 16;
-    const int SC = (MP <= 16) ? chunk_tiles * (16 / (MP <= 16 ? MP : 16)) : chunk_tiles / tiles_per_state;
     const int RS = (S <= SC) ? S : SC;  // LDS row stride: whole matrix rows when they fit one chunk
     T* dummy = lds + 32 * RS + lane;    // per-lane slot behind the output tile
     T run_mx[2] = {Dom<T>::off, Dom<T>::off}, run_sm[2] = {T(0), T(0)};
     LseK lse_k;
-    if (sizeof(T) == 8 && !MULTI && !FE && MP != 1) lse_k.pin();
+    if (sizeof(T) == 8 && !MULTI && !FE && MP != 1) { if (BND) lse_k.pin_bnd(); else lse_k.pin(); }
     int chunk_s0 = 0;  // first state held in the LDS output tile
     int subset_cnt = 0;  // (block table) number of states the block's tile range covers
 
@@ -573,6 +715,7 @@ __global__ __launch_bounds__(64, (sizeof(T) == 4 ? 3 : 1)) void loglik_mfma_kern
             const int s_end = (MP <= 16) ? t_hi * (16 / (MP <= 16 ? MP : 16)) : t_hi / tiles_per_state;
             subset_cnt = ((s_end < S) ? s_end : S) - chunk_s0;
         }
+        if (BND && st_s0 != chunk_s0) { stage_states(chunk_s0); __syncthreads(); }
 #ifdef GH_MF_TIMING
         tk[1] = clock64();
         tk[2] = tk[1];
@@ -581,13 +724,16 @@ __global__ __launch_bounds__(64, (sizeof(T) == 4 ? 3 : 1)) void loglik_mfma_kern
         // with the MFMAs of tile t without copying accumulators (16 v_mov per tile otherwise).
         // (chk: std::true_type for the block's last tile, the only one that may hold padding states -- see tile_epilogue)
         auto epi = [&](const V& e0, const V& e1, int t, auto chk) {
-            tile_epilogue<T, V, MP, FE, decltype(chk)::value>(e0, e1, t, f, q, S, RS, chunk_s0, tiles_per_state, lds, dummy, tab, run_mx, run_sm, inf_below, lse_k);
+            tile_epilogue<T, V, MP, FE, decltype(chk)::value, BND>(e0, e1, t, f, q, S, RS, chunk_s0, tiles_per_state, lds, dummy, tab, run_mx, run_sm, inf_below, lse_k, st_tab);
 #pragma unroll
             for (int i = 0; i < (GH_MF_SGB ? 2 * KS : 0); ++i) {   // (forced MFMA / VALU interleave: measured slower)
                 __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
                 __builtin_amdgcn_sched_group_barrier(0x002, sizeof(T) == 8 ? 5 : 3, 0);
             }
-            if (!subset && (t + 1) % chunk_tiles == 0 && t + 1 < n_tiles) flush();
+            if (!subset && (t + 1) % chunk_tiles == 0 && t + 1 < n_tiles) {
+                flush();
+                if (BND) { stage_states(chunk_s0); __syncthreads(); }   // the next chunk's states
+            }
         };
         V r0, r1;
         // (every block starts with c_a holding tile 0's C: n_tiles tiles alternate c_a / c_b, so the wrap-around load
@@ -697,8 +843,15 @@ static int build_blk_table(const gh_gmm* g, const gh_batch* b, int SC, const int
     return GH_OK;
 }
 
+// GMMHMM_LSE_BOUND=0: the fp64 log-sum-exp in its max-shifted form (read at every launch: a caller's way back, and the
+// "new build, old form" leg of a measurement)
+static bool lse_bound_enabled() {
+    const char* e = getenv("GMMHMM_LSE_BOUND");
+    return !(e && e[0] == '0' && e[1] == 0);
+}
+
 template <typename T>
-int launch_mfma_t(gh_ctx* ctx, const gh_gmm* g, gh_batch* b, const T* Apk, const T* Cpk, const int32_t* st_lo,
+int launch_mfma_t(gh_ctx* ctx, const gh_gmm* g, gh_batch* b, const T* Apk, const T* Cpk, const T* CpkRel, const int32_t* st_lo,
                   const int32_t* st_hi, const T* cen, const int64_t* rng_off, const gh_loglik_plan* plan) {
     const int64_t N = b->N;
     if (N == 0) return GH_OK;
@@ -710,6 +863,13 @@ int launch_mfma_t(gh_ctx* ctx, const gh_gmm* g, gh_batch* b, const T* Apk, const
     lds = (lds + 15) & ~size_t(15);
     const int tab_off = (int)lds;
     if (sizeof(T) == 8 && M_pad != 1) lds += 384 * sizeof(double);   // exp / log tables (not needed for M = 1)
+    // fp64 log-sum-exp against the pack-time bound (the default; GMMHMM_LSE_BOUND=0 launches the max-shifted form): the
+    // per-state table of one output chunk follows the tables, 16 bytes per state (SC <= 71 states: at most 1 136 bytes)
+    // (M_pad <= 16: one tile per state.  Mixtures of more than 16 components keep the max-shifted form with its running
+    //  (max, sum) merge: out of scope here)
+    const bool bnd = sizeof(T) == 8 && M_pad != 1 && M_pad <= 16 && !((ctx->compat & 2) && M_pad >= 4) && CpkRel && g->dLseState64 && lse_bound_enabled();
+    const int st_off = (int)lds;
+    if (bnd) lds += (size_t)std::min(SC, gh_lse_states_padded(M_pad, n_tiles)) * sizeof(gh_lse_state);
     const double* tables = ctx->d_fp64_tables;
     // ln 2^-1075 = -745.13...: exp() of anything below rounds to +0 in fp64 (the reference's arithmetic, whatever T is)
     const T inf_below = (ctx->compat & 1) ? (T)(-745.1332191019412 * (sizeof(T) == 8 ? GH_LSE_SCALE64 : GH_LSE_SCALE32)) : Dom<T>::off_test;
@@ -747,21 +907,23 @@ int launch_mfma_t(gh_ctx* ctx, const gh_gmm* g, gh_batch* b, const T* Apk, const
     T* out = static_cast<T*>(b->nll);
     // fp32 exponentials in the fp64 epilogue (opt-in, see tile_lse_fe): mixtures of >= 4 components
     const bool fe = sizeof(T) == 8 && (ctx->compat & 2) && M_pad >= 4;
+#define GH_MF_LAUNCH1(ks, mp, multi, fe_, bnd_)                                                                          \
+    hipLaunchKernelGGL((loglik_mfma_kernel<T, ks, mp, multi, fe_, bnd_>), dim3(grid), dim3(64), lds, ctx->stream, X, N, g->D, \
+                       Apk, bnd ? CpkRel : Cpk, n_tiles, S, M_pad, chunk_tiles, tables, tab_off, out, bpw, d_blk, n_blk, cen, \
+                       inf_below, g->dLseState64, st_off)
 #define GH_MF_LAUNCH(ks, mp)                                                                                             \
     do {                                                                                                                 \
-        if (fe && sizeof(T) == 8 && mp >= 4) {                                                                           \
-            if (bpw > 1)                                                                                                 \
-                hipLaunchKernelGGL((loglik_mfma_kernel<T, ks, mp, true, (sizeof(T) == 8 && mp >= 4)>), dim3(grid), dim3(64), lds, ctx->stream, X, N, g->D, \
-                                   Apk, Cpk, n_tiles, S, M_pad, chunk_tiles, tables, tab_off, out, bpw, d_blk, n_blk, cen, inf_below); \
-            else                                                                                                         \
-                hipLaunchKernelGGL((loglik_mfma_kernel<T, ks, mp, false, (sizeof(T) == 8 && mp >= 4)>), dim3(grid), dim3(64), lds, ctx->stream, X, N, g->D, \
-                                   Apk, Cpk, n_tiles, S, M_pad, chunk_tiles, tables, tab_off, out, bpw, d_blk, n_blk, cen, inf_below); \
-        } else if (bpw > 1)                                                                                                     \
-            hipLaunchKernelGGL((loglik_mfma_kernel<T, ks, mp, true>), dim3(grid), dim3(64), lds, ctx->stream, X, N, g->D, \
-                               Apk, Cpk, n_tiles, S, M_pad, chunk_tiles, tables, tab_off, out, bpw, d_blk, n_blk, cen, inf_below); \
+        constexpr bool f64 = sizeof(T) == 8;                                                                             \
+        if (fe && f64 && mp >= 4) {                                                                                      \
+            if (bpw > 1) GH_MF_LAUNCH1(ks, mp, true, (f64 && mp >= 4), false);                                           \
+            else GH_MF_LAUNCH1(ks, mp, false, (f64 && mp >= 4), false);                                                  \
+        } else if (bnd && f64 && mp != 1 && mp <= 16) {                                                                  \
+            if (bpw > 1) GH_MF_LAUNCH1(ks, mp, true, false, (f64 && mp != 1 && mp <= 16));                               \
+            else GH_MF_LAUNCH1(ks, mp, false, false, (f64 && mp != 1 && mp <= 16));                                      \
+        } else if (bpw > 1)                                                                                              \
+            GH_MF_LAUNCH1(ks, mp, true, false, false);                                                                   \
         else                                                                                                             \
-            hipLaunchKernelGGL((loglik_mfma_kernel<T, ks, mp, false>), dim3(grid), dim3(64), lds, ctx->stream, X, N, g->D, \
-                               Apk, Cpk, n_tiles, S, M_pad, chunk_tiles, tables, tab_off, out, bpw, d_blk, n_blk, cen, inf_below); \
+            GH_MF_LAUNCH1(ks, mp, false, false, false);                                                                  \
     } while (0)
 #define GH_MF_CASE(ks)                                   \
     case ks:                                             \
@@ -787,6 +949,7 @@ int launch_mfma_t(gh_ctx* ctx, const gh_gmm* g, gh_batch* b, const T* Apk, const
     }
 #undef GH_MF_CASE
 #undef GH_MF_LAUNCH
+#undef GH_MF_LAUNCH1
     GH_HIP(hipGetLastError());
     return GH_OK;
 }
@@ -801,8 +964,8 @@ int gh_launch_loglik_mfma(gh_ctx* ctx, const gh_gmm* g, gh_batch* b, const int32
     // caller that mixes models across ranges loses the stamp's meaning -- the consumer, gh_bw_accumulate with M > 8,
     // documents that the E-step's likelihoods must come from the model it is given)
     b->nll_serial = g->serial;
-    if (b->dtype == GH_F64) return launch_mfma_t<double>(ctx, g, b, g->dApk64, g->dCpk64, st_lo, st_hi, nullptr, rng_off, plan);
-    return launch_mfma_t<float>(ctx, g, b, g->dApk32, g->dCpk32, st_lo, st_hi, g->dCen32, rng_off, plan);
+    if (b->dtype == GH_F64) return launch_mfma_t<double>(ctx, g, b, g->dApk64, g->dCpk64, g->dCpkRel64, st_lo, st_hi, nullptr, rng_off, plan);
+    return launch_mfma_t<float>(ctx, g, b, g->dApk32, g->dCpk32, (const float*)nullptr, st_lo, st_hi, g->dCen32, rng_off, plan);
 }
 
 // a block table that outlives the call (own allocation): 1 = shape / ranges not covered by the subset kernel

@@ -9,6 +9,29 @@ uint64_t gh_next_serial() {
     return ++counter;
 }
 
+// One state's packing for the log-sum-exp against the pack-time bound (gh_internal.h, gh_lse_state_of): c = the state's M
+// GEMM-form constants C_g = logc_g - 0.5 sum mean^2/var, logc = its log(w * normaliser) -- the component log-density is
+// logc_g - 0.5 sum (x - mean)^2/var <= logc_g, so the bound is mh = max logc_g over the switched-on components --, rel
+// = its M_pad slots of CpkRel64 (the padding slots keep OFF).  A NaN constant stays NaN, as in Cpk64.  A state without a
+// switched-on finite component gets what the max-shifted form gives it: its maximum (v_max_f64 drops a NaN operand) is
+// OFF as soon as one of the M_pad slots is OFF -- a weight-0 component or mixture padding -- and the state costs +inf,
+// so every slot is packed OFF and the guard (thr = +inf) sends it to the redo; when all M_pad slots are NaN the maximum
+// is NaN too and the state is NaN: the NaN addends stay and poison the sum, which never takes the redo.
+__host__ __device__ inline void gh_pack_lse_state(const double* c, const double* logc, int M, int M_pad, double* rel, gh_lse_state* st) {
+    double mh = -INFINITY;
+    bool any_on = false, all_nan = (M == M_pad);
+    for (int m = 0; m < M; ++m) {
+        if (c[m] - c[m] == 0.0 && logc[m] - logc[m] == 0.0 && c[m] * GH_LSE_SCALE64 > GH_LSE_OFF64) { any_on = true; mh = (logc[m] > mh) ? logc[m] : mh; }
+        all_nan = all_nan && c[m] != c[m];
+    }
+    *st = gh_lse_state_of(mh, any_on, M_pad);
+    for (int m = 0; m < M; ++m) {
+        const double r = (c[m] - mh) * GH_LSE_SCALE64;
+        if (!any_on) rel[m] = all_nan ? c[m] : GH_LSE_OFF64;
+        else rel[m] = (c[m] == -INFINITY) ? GH_LSE_OFF64 : ((r > GH_LSE_OFF64) ? r : GH_LSE_OFF64) + (c[m] != c[m] ? c[m] : 0.0);
+    }
+}
+
 extern "C" int gh_gmm_create(gh_ctx* ctx, int S, int M, int D, const double* mean, const double* var,
                              const double* weight, gh_gmm** out) {
     GH_REQUIRE(ctx && out && mean && var && weight, "gh_gmm_create: NULL argument");
@@ -106,6 +129,11 @@ extern "C" int gh_gmm_create(gh_ctx* ctx, int S, int M, int D, const double* mea
                     apk32[((size_t)t * KS + ks) * 64 + kq * 16 + row32] = (float)(v32 * GH_LSE_SCALE32);
                 }
         }
+    // (the bound form covers one tile per state: nothing is packed for more than 16 mixture components, or for one)
+    const bool lse_bound = M_pad >= 2 && M_pad <= 16;
+    std::vector<double> cpkrel64(lse_bound ? cpk64.size() : 0, GH_LSE_OFF64);
+    std::vector<gh_lse_state> lse_state(lse_bound ? gh_lse_states_padded(M_pad, n_tiles) : 0, gh_lse_state{0.0, 0.0});
+    for (int s = 0; lse_bound && s < S; ++s) gh_pack_lse_state(&g->hC[(size_t)s * M], &logc[(size_t)s * M], M, M_pad, &cpkrel64[(size_t)s * M_pad], &lse_state[s]);
     std::vector<double> vmean(mean, mean + (size_t)G * D);
     std::vector<int> anypos(1, 0);
     for (int i = 0; i < G; ++i) if (logc[i] > 0) anypos[0] = 1;
@@ -115,6 +143,7 @@ extern "C" int gh_gmm_create(gh_ctx* ctx, int S, int M, int D, const double* mea
     ar.add(&g->dMean, vmean); ar.add(&g->dIvar, ivar); ar.add(&g->dLogc, logc); ar.add(&g->dAnyPos, anypos);
     g->any_pos_host = anypos[0];
     ar.add(&g->dApk64, apk64); ar.add(&g->dCpk64, cpk64); ar.add(&g->dApk32, apk32); ar.add(&g->dCpk32, cpk32);
+    ar.add(&g->dCpkRel64, cpkrel64); ar.add(&g->dLseState64, lse_state);
     const int rc = ar.commit(&g->d_arena);
     if (rc) {
         gh_gmm_destroy(g);
@@ -161,7 +190,8 @@ __global__ __launch_bounds__(1024) void gmm_centre_kernel(const double* __restri
 struct gmm_dev_view {
     int* any_pos;
     int S, M, D, KP, M_pad, n_tiles;
-    double *A64, *B64, *C64, *Mean, *Ivar, *Logc, *Apk64, *Cpk64;
+    double *A64, *B64, *C64, *Mean, *Ivar, *Logc, *Apk64, *Cpk64, *CpkRel64;
+    gh_lse_state* LseState64;
     float *A32, *B32, *C32, *Apk32, *Cpk32;
     const float* cen32;
 };
@@ -202,6 +232,13 @@ __global__ void gmm_pack_plain_kernel(gmm_dev_view v, const double* __restrict__
     v.Cpk32[gp] = (c32 == -INFINITY) ? GH_LSE_OFF32 : (float)(fmax(c32 * GH_LSE_SCALE32, (double)GH_LSE_OFF32) + (c32 != c32 ? c32 : 0.0));
 }
 
+// one thread per state, after gmm_pack_plain_kernel on the stream: the state's bound and its relative addends
+__global__ void gmm_pack_lse_kernel(gmm_dev_view v) {
+    const int s = blockIdx.x * blockDim.x + threadIdx.x;
+    if (s >= v.S) return;
+    gh_pack_lse_state(v.C64 + (size_t)s * v.M, v.Logc + (size_t)s * v.M, v.M, v.M_pad, v.CpkRel64 + (size_t)s * v.M_pad, v.LseState64 + s);
+}
+
 __global__ void gmm_pack_operands_kernel(gmm_dev_view v) {
     // one thread per (padded Gaussian gp, k index kk in [0, 2 KP))
     const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -235,9 +272,11 @@ int gh_gmm_update_dev(gh_ctx* ctx, gh_gmm* g, const double* d_mean, const double
     v.A64 = g->dA64; v.B64 = g->dB64; v.C64 = g->dC64; v.Mean = g->dMean; v.Ivar = g->dIvar; v.Logc = g->dLogc;
     v.Apk64 = g->dApk64; v.Cpk64 = g->dCpk64; v.A32 = g->dA32; v.B32 = g->dB32; v.C32 = g->dC32;
     v.Apk32 = g->dApk32; v.Cpk32 = g->dCpk32; v.cen32 = g->dCen32; v.any_pos = g->dAnyPos;
+    v.CpkRel64 = g->dCpkRel64; v.LseState64 = g->dLseState64;
     g->any_pos_host = -1;      // (the flag is rewritten on the device: the host no longer knows it)
     hipLaunchKernelGGL(gmm_centre_kernel, dim3(g->KP), dim3(1024), 0, st, d_mean, G, g->D, g->KP, g->dCen32, g->dAnyPos);
     hipLaunchKernelGGL(gmm_pack_plain_kernel, dim3((G + 63) / 64), dim3(64), 0, st, v, d_mean, d_var, d_weight, d_flag);
+    if (g->dCpkRel64) hipLaunchKernelGGL(gmm_pack_lse_kernel, dim3((g->S + 63) / 64), dim3(64), 0, st, v);
     const int64_t total = (int64_t)g->n_tiles * 16 * 2 * g->KP;
     hipLaunchKernelGGL(gmm_pack_operands_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, v);
     GH_HIP(hipGetLastError());

@@ -8,7 +8,7 @@ blocks with the most MFMAs: one tile of MFMAs and the epilogue of the tile befor
 fp64 -- and prints their vector instructions by opcode, the s_nop, and the kernel's registers.
 
     python tools/epilogue_isa.py                       # every fp64 instantiation with 20 k-steps (D <= 40)
-    python tools/epilogue_isa.py double,20,8,false,false float,20,8,false
+    python tools/epilogue_isa.py double,20,8,false,false,true float,20,8,false     # T,KS,MP,MULTI,FE,BND
     python tools/epilogue_isa.py --asm listing.s ...   # a listing made earlier (--keep writes one)
 """
 import argparse
@@ -55,9 +55,9 @@ def tile_blocks(body):
     epilogue of the tile before (the flush test between two tiles ends a block, so the two tiles of an fp64 iteration are
     two blocks; the first and the last tiles of a frame block sit outside the loop and are not counted)."""
     blocks = []
-    for blk in re.split(r"\n(?=\.LBB\d+_\d+:)", body):
+    for blk in re.split(r"\n(?=\.LBB\d+_\d+:|; %bb\.\d+:)", body):    # (a block that is only fallen into has no label)
         lines = blk.split("\n")
-        depth = re.search(r"Depth=(\d+)", lines[0]) if lines[0].startswith(".LBB") else None
+        depth = re.search(r"Depth=(\d+)", lines[0]) if lines[0].startswith((".LBB", "; %bb.")) else None
         ins = [l.strip() for l in lines if l.startswith("\t") and not l.strip().startswith((".", ";"))]
         blocks.append((sum(x.startswith("v_mfma") for x in ins), int(depth.group(1)) if depth else 0, ins))
     most = max(n for n, _, _ in blocks)
@@ -85,7 +85,7 @@ def report(name, body):
 
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-    ap.add_argument("inst", nargs="*", help="template arguments T,KS,MP,MULTI[,FE]; default: every fp64 instantiation with KS = 20")
+    ap.add_argument("inst", nargs="*", help="template arguments T,KS,MP,MULTI[,FE[,BND]]; default: every fp64 instantiation with KS = 20")
     ap.add_argument("--asm", help="read this listing instead of compiling")
     ap.add_argument("--keep", help="write the listing here")
     a = ap.parse_args()

@@ -2,7 +2,7 @@
 """Do two likelihood waves and one decode wave of the headline step fit a SIMD's register file together?
 
 A gfx950 SIMD has 512 unified registers per lane.  While bench.py's headline step runs, two waves of
-loglik_mfma_kernel<double,20,8,false,false> share every SIMD and the other lane's viterbi_chain_lanes_kernel<double,5,
+loglik_mfma_kernel<double,20,8,false,false,true> (the log-sum-exp against the pack-time bound) share every SIMD and the other lane's viterbi_chain_lanes_kernel<double,5,
 false,false,false,LANE_PF> (the shallow-ring "beside" form of the lane = chain decode) runs underneath.  A decode wave that does not fit beside two likelihood
 waves can only start in the registers of a likelihood wave that has retired, and then keeps the next likelihood wave out
 until it ends.  With alloc(k) = next_free_vgpr (ArchVGPRs + AGPRs) rounded up to the granule of 8 the condition is
@@ -31,7 +31,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PKG = os.path.join(ROOT, "speech-recognition_amd")
 SIMD_REGISTERS = 512
 GRANULE = 8
-LOGLIK = ("gh_loglik_mfma.hip", "loglik_mfma_kernelIdLi20ELi8ELb0ELb0EE")
+LOGLIK = ("gh_loglik_mfma.hip", "loglik_mfma_kernelIdLi20ELi8ELb0ELb0ELb1EE")     # T, KS, MP, MULTI, FE, BND: the default fp64 form
 DECODE = ("gh_viterbi_chain.hip", "viterbi_chain_lanes_kernelIdLi5ELb0ELb0ELb0ELi")     # + ring depth: the shallowest
 
 
