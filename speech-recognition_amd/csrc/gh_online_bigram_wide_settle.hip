@@ -3,7 +3,7 @@
 // ONE complete 32-bit record per column and lane (gh_bigram_wide_hb: the in-word bits from the top, 6 bits of predecessor word
 // v, b_l, b_s), column j of a stream at word index (j % ring_words) * 64 + lane.  What the anchor is, why the set of cells only
 // shrinks going back and what the flags mean: the header of gh_online_settle.hip.  The host side (checks, task table, flags) is
-// that file's; launch_settle hands over where the graph is in the wide bigram form (gh_lattices::bigram_wide_ok).
+// gh_online.hip's, which launches these for a session of the wide bigram form (gh_online_form::walk).
 //
 // online_bigram_wide_settle_kernel -- online_wide_settle_kernel's structure (gh_online_wide_settle.hip): ONE STREAM PER WAVE,
 // lane = word, a lane holds the live states of its word as an N-bit mask and maps it through its OWN record; the row address
@@ -258,9 +258,10 @@ __global__ __launch_bounds__(64) void online_bigram_wide_segment_kernel(gh_settl
 
 }  // namespace
 
-int gh_launch_online_bigram_wide_settle(gh_ctx* ctx, const gh_settle_args& a, const gh_layerform& f, const gh_bigram_wide* wide,
-                                        bool settle, const char* who) {
+int gh_launch_online_bigram_wide_settle(gh_ctx* ctx, const gh_online* on, const gh_settle_args& a, bool settle, const char* who) {
     if (a.n <= 0) return GH_OK;
+    const gh_layerform& f = on->lat->h_layers;
+    const gh_bigram_wide* wide = on->lat->d_bigram_wide;
     GH_REQUIRE(wide, "%s: internal: wide bigram form without its cost table", who);
     const dim3 blk(64);
     const dim3 grid((unsigned)(settle ? a.n : (a.n + 63) / 64));

@@ -20,9 +20,9 @@
 // and the words of the unsettled tail (best end -> anchor).
 // online_bigram_settle_kernel, online_bigram_segment_kernel -- the same two walks over the records of a bigram session that
 // settles (gh_online_create_bigram_settle), further down.
-// A WIDE session that settles (gh_online_create_wide_settle: 17 .. 64 words, a wave per stream) has its two walks in
-// gh_online_wide_settle.hip, and a WIDE BIGRAM session that settles (gh_online_create_bigram_wide_settle) in
-// gh_online_bigram_wide_settle.hip; the host side below -- every check, the task table, the flags -- is the same for all four.
+// The wide forms (17 .. 64 words, a wave per stream) have their two walks in gh_online_wide_settle.hip and
+// gh_online_bigram_wide_settle.hip; the host side -- every check, the task table, the flags -- is gh_online.hip's and the same
+// for all four (gh_online_form::walk).
 // Bit layout: gh_loop_hb / gh_loop_cpw (gh_viterbi.h); tie rules: the LOOP branch of lattice_backtrace_kernel.  A finite
 // cell has only finite predecessors, so the "+inf: first existing arc" fallback is never taken by the settle walk; the
 // segment walk keeps it, because the chosen end of a stream may be a +inf cell (the one-shot decode's rule for it).
@@ -493,7 +493,10 @@ __global__ __launch_bounds__(64) void online_bigram_segment_kernel(gh_settle_arg
     a.n_labels[i] = (int32_t)len;
 }
 
-int launch_bigram_settle(gh_ctx* ctx, const gh_settle_args& a, const gh_layerform& f, bool settle, const char* who) {
+}  // namespace
+
+int gh_launch_online_bigram_settle(gh_ctx* ctx, const gh_online* on, const gh_settle_args& a, bool settle, const char* who) {
+    const gh_layerform& f = on->lat->h_layers;
     const dim3 blk(64);
     const dim3 grid((unsigned)(settle ? (a.n + 3) / 4 : (a.n + 63) / 64));
 #define GH_STB(ET, NN, SK)                                                                                          \
@@ -508,14 +511,8 @@ int launch_bigram_settle(gh_ctx* ctx, const gh_settle_args& a, const gh_layerfor
     return GH_OK;
 }
 
-// the form dispatch of both walks: the records of a bigram session (gh_layerform.loop == 2) have their own kernels, and so
-// has the history of a wide session (more than GH_LAYERS_ROWW words: gh_online_wide_settle.hip).  A graph in the WIDE BIGRAM
-// form has loop == 2 as well and goes first: gh_online_bigram_wide_settle.hip, with the graph's cost table
-int launch_settle(gh_ctx* ctx, const gh_settle_args& a, const gh_lattices* lat, bool settle, const char* who) {
-    const gh_layerform& f = lat->h_layers;
-    if (lat->bigram_wide_ok) return gh_launch_online_bigram_wide_settle(ctx, a, f, lat->d_bigram_wide, settle, who);
-    if (f.loop == 2) return launch_bigram_settle(ctx, a, f, settle, who);
-    if (f.W > GH_LAYERS_ROWW) return gh_launch_online_wide_settle(ctx, a, f, settle, who);
+int gh_launch_online_loop_settle(gh_ctx* ctx, const gh_online* on, const gh_settle_args& a, bool settle, const char* who) {
+    const gh_layerform& f = on->lat->h_layers;
     const dim3 blk(64);
     const dim3 grid((unsigned)(settle ? (a.n + 3) / 4 : (a.n + 63) / 64));
 #define GH_ST(ET, NN, SK)                                                                                    \
@@ -528,201 +525,4 @@ int launch_settle(gh_ctx* ctx, const gh_settle_args& a, const gh_lattices* lat, 
 #undef GH_ST
     GH_HIP(hipGetLastError());
     return GH_OK;
-}
-
-// the streams a call names (NULL: all), checked; `distinct`: a stream may be named once
-int tasks_of(gh_online* on, const char* who, int64_t& n, const int64_t* ids, bool distinct, std::vector<gh_settle_task>& tasks) {
-    if (!ids) n = on->n_streams;
-    tasks.resize((size_t)std::max<int64_t>(n, 0));
-    for (int64_t i = 0; i < n; ++i) {
-        const int64_t id = ids ? ids[i] : i;
-        GH_REQUIRE(id >= 0 && id < on->n_streams, "%s: stream %lld out of range [0, %lld)", who, (long long)id, (long long)on->n_streams);
-        gh_settle_task& t = tasks[(size_t)i];
-        t.stream = (int32_t)id; t.T = (int32_t)on->frames[(size_t)id]; t.has_anchor = on->settled[(size_t)id] > 0; t.pad = 0;
-    }
-    if (distinct && ids) {
-        int64_t twice = -1, k = 0;
-        for (; k < n && twice < 0; ++k) {
-            if (on->seen[(size_t)ids[k]]) twice = ids[k];
-            on->seen[(size_t)ids[k]] = 1;
-        }
-        for (int64_t q = 0; q < k; ++q) on->seen[(size_t)ids[q]] = 0;
-        GH_REQUIRE(twice < 0, "%s: stream %lld is named twice", who, (long long)twice);
-    }
-    return GH_OK;
-}
-
-}  // namespace
-
-// --------------------------------------------------------------------------------------------------------------- C ABI
-extern "C" int gh_online_commit_timed(gh_ctx* ctx, gh_online* on, int64_t n, const int64_t* ids, int64_t* settled_frames,
-                                      const int32_t* row_label, int32_t* labels, const int64_t* label_off, int32_t* n_new_labels,
-                                      int32_t* out_begin) {
-    GH_REQUIRE(ctx && on, "gh_online_commit: NULL argument");
-    GH_REQUIRE(!out_begin || labels, "gh_online_commit_timed: out_begin needs labels");
-    GH_REQUIRE(ctx == on->ctx, "gh_online_commit: the session belongs to another context");
-    if (on->wide && !on->settles) {
-        gh_set_error("gh_online_commit: a wide session (more than 16 words) keeps its full history and does not settle; gh_online_result "
-                     "gives the running hypothesis");
-        return GH_ERR_UNSUPPORTED;
-    }
-    if (on->bigram && !on->settles) {
-        gh_set_error("gh_online_commit: a bigram session has no settled prefix (its records need their own settle walk); gh_online_result gives the "
-                     "running hypothesis");
-        return GH_ERR_UNSUPPORTED;
-    }
-    GH_REQUIRE(!labels || (row_label && label_off && n_new_labels), "gh_online_commit: labels need row_label, label_off and n_new_labels");
-    std::vector<gh_settle_task> tasks;
-    int rc = tasks_of(on, "gh_online_commit", n, ids, true, tasks);
-    if (rc) return rc;
-    if (n <= 0) return GH_OK;
-    const gh_lattices* lat = on->lat;
-    const int R = lat->lat[0].R;
-    GH_HIP(hipSetDevice(ctx->device));
-    int* d_flag;
-    gh_settle_task* d_tasks;
-    gh_online_anchor* d_cand;
-    int64_t *d_settled, *d_labeloff = nullptr;
-    int32_t *d_rowlabel = nullptr, *d_nlabels = nullptr, *d_labels = nullptr, *d_begins = nullptr;
-    Carver cv;
-    cv.add(&d_flag, 64); cv.add(&d_tasks, (size_t)n); cv.add(&d_cand, (size_t)n); cv.add(&d_settled, (size_t)n);
-    if (labels) { cv.add(&d_rowlabel, (size_t)R); cv.add(&d_labeloff, (size_t)n + 1); cv.add(&d_nlabels, (size_t)n); cv.add(&d_labels, (size_t)label_off[n] + 1); }
-    if (out_begin) cv.add(&d_begins, (size_t)label_off[n] + 1);
-    rc = cv.commit(ctx);
-    if (rc) return rc;
-    hipStream_t st = ctx->stream;
-    GH_HIP(hipMemsetAsync(d_flag, 0, sizeof(int), st));
-    GH_HIP(hipMemcpyAsync(d_tasks, tasks.data(), (size_t)n * sizeof(gh_settle_task), hipMemcpyHostToDevice, st));
-    if (labels) {
-        GH_HIP(hipMemcpyAsync(d_rowlabel, row_label, (size_t)R * 4, hipMemcpyHostToDevice, st));
-        GH_HIP(hipMemcpyAsync(d_labeloff, label_off, (size_t)(n + 1) * 8, hipMemcpyHostToDevice, st));
-    }
-    gh_settle_args a;
-    memset(&a, 0, sizeof a);
-    a.lf = lat->d_layers; a.end_rows = lat->d_end_rows; a.tasks = d_tasks; a.n = n; a.prev = on->d_prev; a.hist = on->d_hist;
-    a.hist_stride = on->hist_stride; a.ring_words = on->ring_words; a.anchor = on->d_anchor; a.cand = d_cand;
-    a.row_label = d_rowlabel; a.labels = d_labels; a.label_off = d_labeloff; a.n_labels = d_nlabels; a.settled_frames = d_settled;
-    a.flag = d_flag; a.begins = d_begins;
-    rc = launch_settle(ctx, a, lat, true, "gh_online_commit");
-    if (rc) return rc;
-    rc = launch_settle(ctx, a, lat, false, "gh_online_commit");
-    if (rc) return rc;
-    int flag = 0;
-    std::vector<int64_t> h_settled((size_t)n);
-    GH_HIP(hipMemcpyAsync(&flag, d_flag, sizeof(int), hipMemcpyDeviceToHost, st));
-    GH_HIP(hipMemcpyAsync(h_settled.data(), d_settled, (size_t)n * 8, hipMemcpyDeviceToHost, st));
-    if (labels) {
-        GH_HIP(hipMemcpyAsync(n_new_labels, d_nlabels, (size_t)n * 4, hipMemcpyDeviceToHost, st));
-        if (label_off[n] > 0) GH_HIP(hipMemcpyAsync(labels, d_labels, (size_t)label_off[n] * 4, hipMemcpyDeviceToHost, st));
-        if (out_begin && label_off[n] > 0) GH_HIP(hipMemcpyAsync(out_begin, d_begins, (size_t)label_off[n] * 4, hipMemcpyDeviceToHost, st));
-    }
-    GH_HIP(hipStreamSynchronize(st));
-    // (the anchors on the device have moved whatever the flag says: the mirror follows them)
-    for (int64_t i = 0; i < n; ++i) on->settled[(size_t)tasks[(size_t)i].stream] = h_settled[(size_t)i];
-    if (settled_frames) memcpy(settled_frames, h_settled.data(), (size_t)n * 8);
-    if (flag & 2) {
-        gh_set_error("gh_online_commit: a trace reached a cell without predecessor or missed the anchor");
-        return GH_ERR_INVALID;
-    }
-    if (flag & 8) {
-        gh_set_error("gh_online_commit: label capacity of a stream too small");
-        return GH_ERR_INVALID;
-    }
-    return GH_OK;
-}
-
-extern "C" int gh_online_commit(gh_ctx* ctx, gh_online* on, int64_t n, const int64_t* ids, int64_t* settled_frames,
-                                const int32_t* row_label, int32_t* labels, const int64_t* label_off, int32_t* n_new_labels) {
-    return gh_online_commit_timed(ctx, on, n, ids, settled_frames, row_label, labels, label_off, n_new_labels, nullptr);
-}
-
-extern "C" int gh_online_tail_timed(gh_ctx* ctx, gh_online* on, int64_t n, const int64_t* ids, double* end_cost, int32_t* best_end,
-                                    const int32_t* row_label, int32_t* labels, const int64_t* label_off, int32_t* n_labels,
-                                    int32_t* out_begin) {
-    GH_REQUIRE(ctx && on, "gh_online_tail: NULL argument");
-    GH_REQUIRE(!out_begin || labels, "gh_online_tail_timed: out_begin needs labels");
-    GH_REQUIRE(ctx == on->ctx, "gh_online_tail: the session belongs to another context");
-    if (on->wide && !on->settles) {
-        gh_set_error("gh_online_tail: a wide session (more than 16 words) keeps its full history and does not settle; gh_online_result "
-                     "gives the running hypothesis");
-        return GH_ERR_UNSUPPORTED;
-    }
-    if (on->bigram && !on->settles) {
-        gh_set_error("gh_online_tail: a bigram session has no settled prefix (its records need their own settle walk); gh_online_result gives the "
-                     "running hypothesis");
-        return GH_ERR_UNSUPPORTED;
-    }
-    GH_REQUIRE(!labels || (row_label && label_off && n_labels), "gh_online_tail: labels need row_label, label_off and n_labels");
-    std::vector<gh_settle_task> tasks;
-    int rc = tasks_of(on, "gh_online_tail", n, ids, false, tasks);
-    if (rc) return rc;
-    if (n <= 0) return GH_OK;
-    const gh_lattices* lat = on->lat;
-    const int n_end = lat->lat[0].n_end, R = lat->lat[0].R;
-    std::vector<int64_t> h_ids((size_t)n), utt_off((size_t)n + 1, 0);
-    for (int64_t i = 0; i < n; ++i) {
-        h_ids[(size_t)i] = tasks[(size_t)i].stream;
-        utt_off[(size_t)i + 1] = utt_off[(size_t)i] + tasks[(size_t)i].T;
-    }
-    GH_HIP(hipSetDevice(ctx->device));
-    int* d_flag;
-    gh_settle_task* d_tasks;
-    double* d_endcost;
-    int64_t *d_ids, *d_uttoff, *d_labeloff = nullptr;
-    int32_t *d_best, *d_rowlabel = nullptr, *d_nlabels = nullptr, *d_labels = nullptr, *d_begins = nullptr;
-    Carver cv;
-    cv.add(&d_flag, 64); cv.add(&d_tasks, (size_t)n); cv.add(&d_best, (size_t)n); cv.add(&d_endcost, (size_t)n * n_end);
-    cv.add(&d_ids, (size_t)n); cv.add(&d_uttoff, (size_t)n + 1);
-    if (labels) { cv.add(&d_rowlabel, (size_t)R); cv.add(&d_labeloff, (size_t)n + 1); cv.add(&d_nlabels, (size_t)n); cv.add(&d_labels, (size_t)label_off[n] + 1); }
-    if (out_begin) cv.add(&d_begins, (size_t)label_off[n] + 1);
-    rc = cv.commit(ctx);
-    if (rc) return rc;
-    hipStream_t st = ctx->stream;
-    GH_HIP(hipMemsetAsync(d_flag, 0, sizeof(int), st));
-    GH_HIP(hipMemcpyAsync(d_tasks, tasks.data(), (size_t)n * sizeof(gh_settle_task), hipMemcpyHostToDevice, st));
-    GH_HIP(hipMemcpyAsync(d_ids, h_ids.data(), (size_t)n * 8, hipMemcpyHostToDevice, st));
-    GH_HIP(hipMemcpyAsync(d_uttoff, utt_off.data(), (size_t)(n + 1) * 8, hipMemcpyHostToDevice, st));
-    if (labels) {
-        GH_HIP(hipMemcpyAsync(d_rowlabel, row_label, (size_t)R * 4, hipMemcpyHostToDevice, st));
-        GH_HIP(hipMemcpyAsync(d_labeloff, label_off, (size_t)(n + 1) * 8, hipMemcpyHostToDevice, st));
-    }
-    rc = on->wide && on->bigram ? gh_launch_online_bigram_wide_end(ctx, on, d_ids, d_uttoff, n, d_endcost, d_best)
-       : on->wide ? gh_launch_online_wide_end(ctx, on, d_ids, d_uttoff, n, d_endcost, d_best)
-       : on->bigram ? gh_launch_online_bigram_end(ctx, on, d_ids, d_uttoff, n, d_endcost, d_best)
-                    : gh_launch_online_end(ctx, on, d_ids, d_uttoff, n, d_endcost, d_best);
-    if (rc) return rc;
-    if (labels) {
-        gh_settle_args a;
-        memset(&a, 0, sizeof a);
-        a.lf = lat->d_layers; a.end_rows = lat->d_end_rows; a.tasks = d_tasks; a.n = n; a.prev = on->d_prev; a.hist = on->d_hist;
-        a.hist_stride = on->hist_stride; a.ring_words = on->ring_words; a.anchor = on->d_anchor; a.best_end = d_best;
-        a.row_label = d_rowlabel; a.labels = d_labels; a.label_off = d_labeloff; a.n_labels = d_nlabels; a.flag = d_flag;
-        a.begins = d_begins;
-        rc = launch_settle(ctx, a, lat, false, "gh_online_tail");
-        if (rc) return rc;
-    }
-    int flag = 0;
-    GH_HIP(hipMemcpyAsync(&flag, d_flag, sizeof(int), hipMemcpyDeviceToHost, st));
-    if (best_end) GH_HIP(hipMemcpyAsync(best_end, d_best, (size_t)n * 4, hipMemcpyDeviceToHost, st));
-    if (end_cost) GH_HIP(hipMemcpyAsync(end_cost, d_endcost, (size_t)n * n_end * 8, hipMemcpyDeviceToHost, st));
-    if (labels) {
-        GH_HIP(hipMemcpyAsync(n_labels, d_nlabels, (size_t)n * 4, hipMemcpyDeviceToHost, st));
-        if (label_off[n] > 0) GH_HIP(hipMemcpyAsync(labels, d_labels, (size_t)label_off[n] * 4, hipMemcpyDeviceToHost, st));
-        if (out_begin && label_off[n] > 0) GH_HIP(hipMemcpyAsync(out_begin, d_begins, (size_t)label_off[n] * 4, hipMemcpyDeviceToHost, st));
-    }
-    GH_HIP(hipStreamSynchronize(st));
-    if (flag & 2) {
-        gh_set_error("gh_online_tail: back-trace reached a cell without predecessor or missed the anchor");
-        return GH_ERR_INVALID;
-    }
-    if (flag & 8) {
-        gh_set_error("gh_online_tail: label capacity of a stream too small");
-        return GH_ERR_INVALID;
-    }
-    return GH_OK;
-}
-
-extern "C" int gh_online_tail(gh_ctx* ctx, gh_online* on, int64_t n, const int64_t* ids, double* end_cost, int32_t* best_end,
-                              const int32_t* row_label, int32_t* labels, const int64_t* label_off, int32_t* n_labels) {
-    return gh_online_tail_timed(ctx, on, n, ids, end_cost, best_end, row_label, labels, label_off, n_labels, nullptr);
 }

@@ -3,7 +3,7 @@
 // word per column and lane (CPW = 1), column j of a stream at word index (j % ring_words) * 64 + lane.  What the anchor is,
 // why the set of cells only shrinks going back and what the flags mean: the header of gh_online_settle.hip, whose
 // online_settle_kernel / online_segment_kernel these two restate for 64 word lanes; the host side (checks, task table,
-// flags) is that file's, launch_settle hands over where the graph has more than GH_LAYERS_ROWW words.
+// flags) is gh_online.hip's, which launches these for a session of the wide loop form (gh_online_form::walk).
 //
 // online_wide_settle_kernel -- the mapping of the wide sweep: ONE STREAM PER WAVE, lane = word.  A lane holds the live states
 // of its word as an N-bit mask and maps it through its OWN decision word, so a column step is one coalesced 256 B row for
@@ -244,8 +244,9 @@ __global__ __launch_bounds__(64) void online_wide_segment_kernel(gh_settle_args 
 
 }  // namespace
 
-int gh_launch_online_wide_settle(gh_ctx* ctx, const gh_settle_args& a, const gh_layerform& f, bool settle, const char* who) {
+int gh_launch_online_wide_settle(gh_ctx* ctx, const gh_online* on, const gh_settle_args& a, bool settle, const char* who) {
     if (a.n <= 0) return GH_OK;
+    const gh_layerform& f = on->lat->h_layers;
     const dim3 blk(64);
     const dim3 grid((unsigned)(settle ? a.n : (a.n + 63) / 64));
 #define GH_STW(ET, NN, SK)                                                                                        \

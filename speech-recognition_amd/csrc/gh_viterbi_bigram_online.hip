@@ -157,57 +157,15 @@ __global__ __launch_bounds__(64) void viterbi_bigram_online_kernel(gh_online_arg
     *op = word;
 }
 
-// End costs and end selection of n streams from their carried columns: the tail of viterbi_bigram_kernel ('>=': the last of
-// equal minima, decode.py:129-134; no frames: +inf / -1) in the bigram row numbering -- state 0 of word w is row
-// loop_row + W + w.  DPP row = stream, lane = word.
-__global__ __launch_bounds__(64) void online_bigram_end_kernel(const gh_layerform* __restrict__ lf, const int32_t* __restrict__ end_slot,
-                                                               int n_end, const double* __restrict__ prev, const int64_t* __restrict__ ids,
-                                                               const int64_t* __restrict__ utt_off, int64_t n, double* __restrict__ end_cost,
-                                                               int32_t* __restrict__ best_end) {
-    const int lane = threadIdx.x, kk = lane >> 4, w = lane & 15;
-    const int64_t i = (int64_t)blockIdx.x * 4 + kk;
-    if (i >= n) return;
-    const int W = lf->W, N = lf->N, Lr = lf->loop_row;
-    const int64_t stream = ids[i];
-    const int64_t T = utt_off[i + 1] - utt_off[i];
-    const double INF = INFINITY;
-    double best_v = INF;
-    int best_slot = -1;
-    if (w < W)
-        for (int s = 0; s < N; ++s) {
-            const int r = s == 0 ? Lr + W + w : 1 + w * (N - 1) + (s - 1);
-            const int es = end_slot[r];
-            if (es >= 0) {
-                const double v = T > 0 ? prev[(stream * N + s) * 16 + w] : INF;
-                end_cost[i * n_end + es] = v;
-                if (v < best_v || (v == best_v && es > best_slot)) { best_v = v; best_slot = es; }
-            }
-        }
-#pragma unroll
-    for (int o = 8; o >= 1; o >>= 1) {
-        const double ov = __shfl_xor(best_v, o);
-        const int os = __shfl_xor(best_slot, o);
-        if (ov < best_v || (ov == best_v && os > best_slot)) { best_v = ov; best_slot = os; }
-    }
-    if (w == 0) best_end[i] = T > 0 ? best_slot : -1;
-}
-
 }  // namespace
 
-int gh_launch_online_bigram(gh_ctx* ctx, const gh_online_args& a, const gh_layerform& f, bool f64) {
+int gh_launch_online_bigram(gh_ctx* ctx, const gh_online* on, const gh_online_args& a, bool f64) {
+    const gh_layerform& f = on->lat->h_layers;
     const dim3 grid((unsigned)((a.n_slots + 3) / 4)), blk(64);
 #define GH_ONB(ET, NN, SK) hipLaunchKernelGGL((viterbi_bigram_online_kernel<ET, NN, SK>), grid, blk, 0, ctx->stream, a)
     if (f64) { GH_NSKIP_SWITCH(f.N, f.skip, 16_NO_SKIP16, GH_ONB, double, "gh_online_push: bigram form with %d states per word (skip arcs: %d)", f.N, f.skip) }
     else { GH_NSKIP_SWITCH(f.N, f.skip, 16_NO_SKIP16, GH_ONB, float, "gh_online_push: bigram form with %d states per word (skip arcs: %d)", f.N, f.skip) }
 #undef GH_ONB
-    GH_HIP(hipGetLastError());
-    return GH_OK;
-}
-
-int gh_launch_online_bigram_end(gh_ctx* ctx, const gh_online* on, const int64_t* d_ids, const int64_t* d_utt_off, int64_t n,
-                                double* d_end_cost, int32_t* d_best_end) {
-    hipLaunchKernelGGL(online_bigram_end_kernel, dim3((unsigned)((n + 3) / 4)), dim3(64), 0, ctx->stream, on->lat->d_layers,
-                       on->lat->d_lf_end_slot, on->lat->lat[0].n_end, on->d_prev, d_ids, d_utt_off, n, d_end_cost, d_best_end);
     GH_HIP(hipGetLastError());
     return GH_OK;
 }

@@ -21,7 +21,7 @@
 // v with the fences that keep a group's arg beside its minimum, the wave-uniform skip of groups behind the last word, the
 // merges with the lower group on the left; word = (word << 6) | v; then b_l, b_s.  What differs is where `prev` comes from and
 // goes to, that the start-row term and the history address use the absolute column, and that there is no end selection in the
-// sweep (online_bigram_wide_end_kernel).  A chunk of t frames moves 512 N B of state in and out and t 256 B of records beside
+// sweep (online_end_kernel of gh_online.hip).  A chunk of t frames moves 512 N B of state in and out and t 256 B of records beside
 // its emissions, and its block reads the 32 KB of costs once.
 //
 // THE RING.  A stream owns its wave, so the column, its ring position and the wrap are wave-uniform: the position starts from
@@ -179,59 +179,18 @@ __global__ __launch_bounds__(64 * OBW_WAVES) void viterbi_bigram_online_wide_ker
     for (int s = 0; s < N; ++s) st[s * 64] = prev[s];
 }
 
-// End costs and end selection of n streams from their carried columns: the tail of viterbi_bigram_wide_kernel ('>=': the last
-// of equal minima, decode.py:129-134; no frames: +inf / -1) in the bigram row numbering -- state 0 of word w is row
-// loop_row + W + w.  One wave per stream, lane = word.
-__global__ __launch_bounds__(64) void online_bigram_wide_end_kernel(const gh_layerform* __restrict__ lf, const int32_t* __restrict__ end_slot,
-                                                                    int n_end, const double* __restrict__ prev, const int64_t* __restrict__ ids,
-                                                                    const int64_t* __restrict__ utt_off, double* __restrict__ end_cost,
-                                                                    int32_t* __restrict__ best_end) {
-    const int lane = threadIdx.x, w = lane;
-    const int64_t i = blockIdx.x;                             // (grid = n)
-    const int W = lf->W, N = lf->N, Lr = lf->loop_row;
-    const int64_t stream = ids[i];
-    const int64_t T = utt_off[i + 1] - utt_off[i];
-    const double INF = INFINITY;
-    double best_v = INF;
-    int best_slot = -1;
-    if (w < W)
-        for (int s = 0; s < N; ++s) {
-            const int r = s == 0 ? Lr + W + w : 1 + w * (N - 1) + (s - 1);
-            const int es = end_slot[r];
-            if (es >= 0) {
-                const double v = T > 0 ? prev[(stream * N + s) * 64 + w] : INF;
-                end_cost[i * n_end + es] = v;
-                if (v < best_v || (v == best_v && es > best_slot)) { best_v = v; best_slot = es; }
-            }
-        }
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) {
-        const double ov = __shfl_xor(best_v, o);
-        const int os = __shfl_xor(best_slot, o);
-        if (ov < best_v || (ov == best_v && os > best_slot)) { best_v = ov; best_slot = os; }
-    }
-    if (lane == 0) best_end[i] = T > 0 ? best_slot : -1;
-}
-
 }  // namespace
 
-int gh_launch_online_bigram_wide(gh_ctx* ctx, const gh_online_args& a, const gh_layerform& f, const gh_bigram_wide* wide, bool f64) {
+int gh_launch_online_bigram_wide(gh_ctx* ctx, const gh_online* on, const gh_online_args& a, bool f64) {
     if (a.n_slots <= 0) return GH_OK;
+    const gh_layerform& f = on->lat->h_layers;
+    const gh_bigram_wide* wide = on->lat->d_bigram_wide;
     GH_REQUIRE(wide, "gh_online_push: internal: wide bigram form without its cost table");
     const dim3 grid((unsigned)((a.n_slots + OBW_WAVES - 1) / OBW_WAVES)), blk(64 * OBW_WAVES);
 #define GH_OBW(ET, NN, SK) hipLaunchKernelGGL((viterbi_bigram_online_wide_kernel<ET, NN, SK>), grid, blk, 0, ctx->stream, a, wide)
     if (f64) { GH_NSKIP_SWITCH(f.N, f.skip, 8, GH_OBW, double, "gh_online_push: wide bigram form with %d states per word", f.N) }
     else { GH_NSKIP_SWITCH(f.N, f.skip, 8, GH_OBW, float, "gh_online_push: wide bigram form with %d states per word", f.N) }
 #undef GH_OBW
-    GH_HIP(hipGetLastError());
-    return GH_OK;
-}
-
-int gh_launch_online_bigram_wide_end(gh_ctx* ctx, const gh_online* on, const int64_t* d_ids, const int64_t* d_utt_off, int64_t n,
-                                     double* d_end_cost, int32_t* d_best_end) {
-    if (n <= 0) return GH_OK;
-    hipLaunchKernelGGL(online_bigram_wide_end_kernel, dim3((unsigned)n), dim3(64), 0, ctx->stream, on->lat->d_layers,
-                       on->lat->d_lf_end_slot, on->lat->lat[0].n_end, on->d_prev, d_ids, d_utt_off, d_end_cost, d_best_end);
     GH_HIP(hipGetLastError());
     return GH_OK;
 }

@@ -143,57 +143,16 @@ __global__ __launch_bounds__(64) void viterbi_online_wide_kernel(gh_online_args 
     for (int s = 0; s < N; ++s) st[s * 64] = prev[s];
 }
 
-// End costs and end selection of n streams from their carried columns: the tail of viterbi_loop_wide_kernel ('>=': the last
-// of equal minima, decode.py:129-134; no frames: +inf / -1).  One wave per stream, lane = word.
-__global__ __launch_bounds__(64) void online_wide_end_kernel(const gh_layerform* __restrict__ lf, const int32_t* __restrict__ end_slot,
-                                                             int n_end, const double* __restrict__ prev, const int64_t* __restrict__ ids,
-                                                             const int64_t* __restrict__ utt_off, double* __restrict__ end_cost,
-                                                             int32_t* __restrict__ best_end) {
-    const int lane = threadIdx.x, w = lane;
-    const int64_t i = blockIdx.x;                             // (grid = n)
-    const int W = lf->W, N = lf->N, Lr = lf->loop_row;
-    const int64_t stream = ids[i];
-    const int64_t T = utt_off[i + 1] - utt_off[i];
-    const double INF = INFINITY;
-    double best_v = INF;
-    int best_slot = -1;
-    if (w < W)
-        for (int s = 0; s < N; ++s) {
-            const int r = s == 0 ? Lr + 1 + w : 1 + w * (N - 1) + (s - 1);
-            const int es = end_slot[r];
-            if (es >= 0) {
-                const double v = T > 0 ? prev[(stream * N + s) * 64 + w] : INF;
-                end_cost[i * n_end + es] = v;
-                if (v < best_v || (v == best_v && es > best_slot)) { best_v = v; best_slot = es; }
-            }
-        }
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) {
-        const double ov = __shfl_xor(best_v, o);
-        const int os = __shfl_xor(best_slot, o);
-        if (ov < best_v || (ov == best_v && os > best_slot)) { best_v = ov; best_slot = os; }
-    }
-    if (lane == 0) best_end[i] = T > 0 ? best_slot : -1;
-}
-
 }  // namespace
 
-int gh_launch_online_wide(gh_ctx* ctx, const gh_online_args& a, const gh_layerform& f, bool f64) {
+int gh_launch_online_wide(gh_ctx* ctx, const gh_online* on, const gh_online_args& a, bool f64) {
     if (a.n_slots <= 0) return GH_OK;
+    const gh_layerform& f = on->lat->h_layers;
     const dim3 grid((unsigned)a.n_slots), blk(64);
 #define GH_ONW(ET, NN, SK) hipLaunchKernelGGL((viterbi_online_wide_kernel<ET, NN, SK>), grid, blk, 0, ctx->stream, a)
     if (f64) { GH_NSKIP_SWITCH(f.N, f.skip, 8, GH_ONW, double, "gh_online_push: wide loop form with %d states per word", f.N) }
     else { GH_NSKIP_SWITCH(f.N, f.skip, 8, GH_ONW, float, "gh_online_push: wide loop form with %d states per word", f.N) }
 #undef GH_ONW
-    GH_HIP(hipGetLastError());
-    return GH_OK;
-}
-
-int gh_launch_online_wide_end(gh_ctx* ctx, const gh_online* on, const int64_t* d_ids, const int64_t* d_utt_off, int64_t n,
-                              double* d_end_cost, int32_t* d_best_end) {
-    if (n <= 0) return GH_OK;
-    hipLaunchKernelGGL(online_wide_end_kernel, dim3((unsigned)n), dim3(64), 0, ctx->stream, on->lat->d_layers, on->lat->d_lf_end_slot,
-                       on->lat->lat[0].n_end, on->d_prev, d_ids, d_utt_off, d_end_cost, d_best_end);
     GH_HIP(hipGetLastError());
     return GH_OK;
 }

@@ -1472,6 +1472,11 @@ class OnlineSession:
     `tail` is the rest of the running hypothesis; with a window, `result` is `Unsupported` (no paths, use `tail`)."""
 
     def __init__(self, ctx, lat, n_streams, max_frames=None, window=None):
+        self._open(ctx, lat, n_streams, max_frames, window, "gh_online_create" if window is None else "gh_online_create_window")
+
+    def _open(self, ctx, lat, n_streams, max_frames, window, create, *flags):
+        """What every session class does to come up: `create` names the library's entry point, called with the frame count
+        (max_frames, or the window) and `flags`."""
         if (max_frames is None) == (window is None):
             raise ValueError("exactly one of max_frames and window must be given")
         self.ctx, self.lat = ctx, lat
@@ -1479,16 +1484,19 @@ class OnlineSession:
         self.max_frames = None if max_frames is None else int(max_frames)
         self.window = None if window is None else int(window)
         h = C.c_void_p()
-        if window is None:
-            rc = ctx.lib.gh_online_create(ctx.h, lat.h, self.n_streams, self.max_frames, C.byref(h))
-        else:
-            rc = ctx.lib.gh_online_create_window(ctx.h, lat.h, self.n_streams, self.window, C.byref(h))
+        rc = getattr(ctx.lib, create)(ctx.h, lat.h, self.n_streams, self.max_frames if window is None else self.window, *flags, C.byref(h))
         if rc == GH_ERR_UNSUPPORTED:
             raise Unsupported(ctx.lib.gh_last_error().decode("utf-8", "replace"))
         _check(ctx.lib, rc)
         self.h = h
         self.n_end, self.R = int(lat.n_end[0]), int(lat.R[0])
         self._nlev = lat.path_cap(0, 1)
+
+    def _open_settle(self, ctx, lat, n_streams, max_frames, window, settle):
+        """`_open` of the subclasses, which settle on request: the class's `_create_settle` (it takes a window flag) where
+        `settle` or a window asks for it, its `_create` otherwise."""
+        self.settles = bool(settle) or window is not None
+        self._open(ctx, lat, n_streams, max_frames, window, *((self._create_settle, int(window is not None)) if self.settles else (self._create,)))
 
     @staticmethod
     def _i64(a):
@@ -1634,81 +1642,41 @@ class OnlineBigramSession(OnlineSession):
     instead of `max_frames=` implies it and keeps history for that many UNSETTLED frames per stream in a ring, so a stream
     may run for any length (`result` is then `Unsupported`: no paths, use `tail`)."""
 
-    def __init__(self, ctx, lat, n_streams, max_frames=None, window=None, settle=False):
-        if (max_frames is None) == (window is None):
-            raise ValueError("exactly one of max_frames and window must be given")
-        self.ctx, self.lat = ctx, lat
-        self.n_streams = int(n_streams)
-        self.max_frames = None if max_frames is None else int(max_frames)
-        self.window = None if window is None else int(window)
-        self.settles = bool(settle) or window is not None
-        h = C.c_void_p()
-        if self.settles:
-            rc = ctx.lib.gh_online_create_bigram_settle(ctx.h, lat.h, self.n_streams, self.max_frames if window is None else self.window,
-                                                        int(window is not None), C.byref(h))
-        else:
-            rc = ctx.lib.gh_online_create_bigram(ctx.h, lat.h, self.n_streams, self.max_frames, C.byref(h))
-        if rc == GH_ERR_UNSUPPORTED:
-            raise Unsupported(ctx.lib.gh_last_error().decode("utf-8", "replace"))
-        _check(ctx.lib, rc)
-        self.h = h
-        self.n_end, self.R = int(lat.n_end[0]), int(lat.R[0])
-        self._nlev = lat.path_cap(0, 1)
+    _create, _create_settle = "gh_online_create_bigram", "gh_online_create_bigram_settle"
 
-    def commit(self, ids=None, row_label=None, max_labels=None, want_begin=False):
+    def __init__(self, ctx, lat, n_streams, max_frames=None, window=None, settle=False):
+        self._open_settle(ctx, lat, n_streams, max_frames, window, settle)
+
+    def _unsettled(self):
         if not self.settles:
             raise Unsupported("a bigram session has no settled prefix: result() gives the running hypothesis (settle=True or window= "
                               "makes one that has)")
+
+    def commit(self, ids=None, row_label=None, max_labels=None, want_begin=False):
+        self._unsettled()
         return super().commit(ids, row_label, max_labels, want_begin)
 
     def tail(self, ids=None, row_label=None, max_labels=None, want_begin=False):
-        if not self.settles:
-            raise Unsupported("a bigram session has no settled prefix: result() gives the running hypothesis (settle=True or window= "
-                              "makes one that has)")
+        self._unsettled()
         return super().tail(ids, row_label, max_labels, want_begin)
 
 
-class OnlineWideSession(OnlineSession):
-    """Online decode over ONE word-loop graph of 17 to 64 words (gh_online_create_wide): the `OnlineSession` of a larger
-    vocabulary, one wave per stream.  `push`, `result` (labels, begins, paths), `reset` and `frames` are the parent's, and
-    `result` is bitwise the one-shot decode of the frames a stream has taken.  A loop graph of 16 words or fewer (that is
-    `OnlineSession`'s), a bigram graph, a K-layer lattice, a beam or several graphs raise `Unsupported`.
-    By default the session keeps its full history -- 256 B per frame and stream, `max_frames` is a hard capacity -- and
-    does not settle: `commit` and `tail` raise `Unsupported`.  `settle=True` (gh_online_create_wide_settle) gives it the
-    parent's `commit` and `tail`; `window=` instead of `max_frames=` implies it and keeps history for that many UNSETTLED
-    frames per stream in a ring of columns, so a stream may run for any length (`result` is then `Unsupported`: no
-    paths, use `tail`)."""
+class _WideSession(OnlineSession):
+    """What the two wide session classes share: where the session does not settle, `commit` and `tail` ask the library and
+    raise its refusal."""
 
     def __init__(self, ctx, lat, n_streams, max_frames=None, window=None, settle=False):
-        if (max_frames is None) == (window is None):
-            raise ValueError("exactly one of max_frames and window must be given")
-        self.ctx, self.lat = ctx, lat
-        self.n_streams = int(n_streams)
-        self.max_frames = None if max_frames is None else int(max_frames)
-        self.window = None if window is None else int(window)
-        self.settles = bool(settle) or window is not None
-        h = C.c_void_p()
-        if self.settles:
-            rc = ctx.lib.gh_online_create_wide_settle(ctx.h, lat.h, self.n_streams, self.max_frames if window is None else self.window,
-                                                      int(window is not None), C.byref(h))
-        else:
-            rc = ctx.lib.gh_online_create_wide(ctx.h, lat.h, self.n_streams, self.max_frames, C.byref(h))
-        if rc == GH_ERR_UNSUPPORTED:
-            raise Unsupported(ctx.lib.gh_last_error().decode("utf-8", "replace"))
-        _check(ctx.lib, rc)
-        self.h = h
-        self.n_end, self.R = int(lat.n_end[0]), int(lat.R[0])
-        self._nlev = lat.path_cap(0, 1)
+        self._open_settle(ctx, lat, n_streams, max_frames, window, settle)
 
     def _refused(self, rc):
         if rc == GH_ERR_UNSUPPORTED:
             raise Unsupported(self.ctx.lib.gh_last_error().decode("utf-8", "replace"))
         _check(self.ctx.lib, rc)
-        raise Unsupported("a wide session keeps its full history and does not settle: result() gives the running hypothesis")
+        raise Unsupported(self._does_not_settle)
 
     def commit(self, ids=None, row_label=None, max_labels=None, want_begin=False):
         """The parent's `commit` where the session settles (settle=True or window=); otherwise `Unsupported` (the library's
-        own refusal: a wide session from gh_online_create_wide does not settle)."""
+        own refusal: a wide session made without `settle` does not settle)."""
         if self.settles:
             return super().commit(ids, row_label, max_labels, want_begin)
         settled = np.zeros(1, dtype=np.int64)
@@ -1721,7 +1689,22 @@ class OnlineWideSession(OnlineSession):
         self._refused(self.ctx.lib.gh_online_tail(self.ctx.h, self.h, 0, None, None, None, None, None, None, None))
 
 
-class OnlineBigramWideSession(OnlineSession):
+class OnlineWideSession(_WideSession):
+    """Online decode over ONE word-loop graph of 17 to 64 words (gh_online_create_wide): the `OnlineSession` of a larger
+    vocabulary, one wave per stream.  `push`, `result` (labels, begins, paths), `reset` and `frames` are the parent's, and
+    `result` is bitwise the one-shot decode of the frames a stream has taken.  A loop graph of 16 words or fewer (that is
+    `OnlineSession`'s), a bigram graph, a K-layer lattice, a beam or several graphs raise `Unsupported`.
+    By default the session keeps its full history -- 256 B per frame and stream, `max_frames` is a hard capacity -- and
+    does not settle: `commit` and `tail` raise `Unsupported`.  `settle=True` (gh_online_create_wide_settle) gives it the
+    parent's `commit` and `tail`; `window=` instead of `max_frames=` implies it and keeps history for that many UNSETTLED
+    frames per stream in a ring of columns, so a stream may run for any length (`result` is then `Unsupported`: no
+    paths, use `tail`)."""
+
+    _create, _create_settle = "gh_online_create_wide", "gh_online_create_wide_settle"
+    _does_not_settle = "a wide session keeps its full history and does not settle: result() gives the running hypothesis"
+
+
+class OnlineBigramWideSession(_WideSession):
     """Online decode over ONE graph in the wide bigram form, the bigram grammar with 17 to 64 words of 2 to 8 states
     (gh_online_create_bigram_wide): one wave per stream, four streams per block around one LDS image of the word-to-word
     costs.  `push`, `result` (labels, begins, paths), `reset` and `frames` are the parent's, and `result` is bitwise the
@@ -1733,47 +1716,8 @@ class OnlineBigramWideSession(OnlineSession):
     UNSETTLED frames per stream in a ring of columns, so a stream may run for any length (`result` is then `Unsupported`:
     no paths, use `tail`)."""
 
-    def __init__(self, ctx, lat, n_streams, max_frames=None, window=None, settle=False):
-        if (max_frames is None) == (window is None):
-            raise ValueError("exactly one of max_frames and window must be given")
-        self.ctx, self.lat = ctx, lat
-        self.n_streams = int(n_streams)
-        self.max_frames = None if max_frames is None else int(max_frames)
-        self.window = None if window is None else int(window)
-        self.settles = bool(settle) or window is not None
-        h = C.c_void_p()
-        if self.settles:
-            rc = ctx.lib.gh_online_create_bigram_wide_settle(ctx.h, lat.h, self.n_streams,
-                                                             self.max_frames if window is None else self.window,
-                                                             int(window is not None), C.byref(h))
-        else:
-            rc = ctx.lib.gh_online_create_bigram_wide(ctx.h, lat.h, self.n_streams, self.max_frames, C.byref(h))
-        if rc == GH_ERR_UNSUPPORTED:
-            raise Unsupported(ctx.lib.gh_last_error().decode("utf-8", "replace"))
-        _check(ctx.lib, rc)
-        self.h = h
-        self.n_end, self.R = int(lat.n_end[0]), int(lat.R[0])
-        self._nlev = lat.path_cap(0, 1)
-
-    def _refused(self, rc):
-        if rc == GH_ERR_UNSUPPORTED:
-            raise Unsupported(self.ctx.lib.gh_last_error().decode("utf-8", "replace"))
-        _check(self.ctx.lib, rc)
-        raise Unsupported("a wide bigram session keeps its full history and does not settle: result() gives the running hypothesis")
-
-    def commit(self, ids=None, row_label=None, max_labels=None, want_begin=False):
-        """The parent's `commit` where the session settles (settle=True or window=); otherwise `Unsupported` (the library's
-        own refusal: a session from gh_online_create_bigram_wide does not settle)."""
-        if self.settles:
-            return super().commit(ids, row_label, max_labels, want_begin)
-        settled = np.zeros(1, dtype=np.int64)
-        self._refused(self.ctx.lib.gh_online_commit(self.ctx.h, self.h, 0, None, _ptr(settled, _c_i64p), None, None, None, None))
-
-    def tail(self, ids=None, row_label=None, max_labels=None, want_begin=False):
-        """The parent's `tail` where the session settles; otherwise `Unsupported` (the library's own refusal)."""
-        if self.settles:
-            return super().tail(ids, row_label, max_labels, want_begin)
-        self._refused(self.ctx.lib.gh_online_tail(self.ctx.h, self.h, 0, None, None, None, None, None, None, None))
+    _create, _create_settle = "gh_online_create_bigram_wide", "gh_online_create_bigram_wide_settle"
+    _does_not_settle = "a wide bigram session keeps its full history and does not settle: result() gives the running hypothesis"
 
 
 class WordStreamSession:
