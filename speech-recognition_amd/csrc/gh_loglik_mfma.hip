@@ -15,7 +15,9 @@
 //   * the Gaussians stream past as 16-row tiles.  The host packs P so that every A fragment is 64
 //     consecutive elements in lane order (one coalesced 512-byte / 256-byte load per k-step); all
 //     waves read the same 256 KB, which lives in L2 (~60 % of it is served by the CU's L1).  The
-//     fragments travel through a register ring a whole tile (fp64) / half a tile (fp32) ahead;
+//     fragments travel through a register ring of a whole tile (fp64) / half a tile (fp32) of k-steps.  Only where the
+//     refills are held behind their k-step (KSTEP, below: the default fp64 mixtures) is that also the run-ahead of
+//     every load; elsewhere the scheduler batches the refills late in the tile (8 to 38 MFMAs ahead of their use);
 //   * the first k-step of a tile takes C[g] as its addend, so the accumulators finish as component
 //     log-densities -- in a SCALED log domain (see below) that makes the log-sum-exp cheap.  The
 //     row order inside a tile is chosen per dtype (host side) such that lane group q = lane>>4
@@ -479,10 +481,12 @@ __device__ __forceinline__ void tile_epilogue(const V& acc0, const V& acc1, int 
     }
 }
 
-// KS = number of k-steps (K = 4*KS = 2*KP).  A fragments travel through a ring of R = KS/2
-// registers: slot j serves k-step j, is refilled with k-step j+R of the same tile, serves it,
-// and is refilled with k-step j of the NEXT tile -- every load has half a tile of MFMAs
-// (R*2 instructions, >= 1280 cycles in fp64) to return from L2.
+// KS = number of k-steps (K = 4*KS = 2*KP).  A fragments travel through a ring of R registers (fp64: R = KS, slot j
+// serves k-step j and is refilled with k-step j of the NEXT tile; fp32: R = KS/2, slot j serves k-steps j and j + R).
+// What the SOURCE says -- every slot refilled as it is consumed, R k-steps of run-ahead -- is not what the scheduler
+// makes of it by itself: it sinks a tile's refills into two bursts behind MFMA 32 and MFMA 38 of 40, 8 to 38 MFMAs of
+// run-ahead instead of 40, and the tile waits for a burst, not for a slot (tools/tile_waits.py).  The
+// instantiations named at KSTEP below hold the order of the source; the others keep the scheduler's.
 // Measured on MI355X (tools/variant_bench.sh): forcing an MFMA/VALU interleave with
 // sched_group_barrier is 6-10 % SLOWER than letting the MFMAs issue back to back (fp32/fp64
 // MFMA and VALU share one pipeline: nothing overlaps, the interleave only adds bubbles), and a
@@ -490,6 +494,17 @@ __device__ __forceinline__ void tile_epilogue(const V& acc0, const V& acc1, int 
 #ifndef GH_MF_SGB
 #define GH_MF_SGB 0
 #endif
+// GH_MF_KSTEP: hold every ring refill behind the MFMA pair of its k-step (a sched_barrier per k-step).  1 (default): the
+// instantiations with the log-sum-exp against the pack-time bound (BND: the default fp64 mixtures of 2 to 16 components,
+// the headline among them) -- measured faster there.  The others keep the scheduler's order: with the barriers the
+// max-shifted fp64 forms take 18 more registers and <double,20,8> runs 1.7 % slower, M_pad = 1 at 8 blocks per wave
+// (HBM-bound) 0.7 % slower, fp32 does not move.  0: nowhere; 2: everywhere (diagnostic builds).
+// The mask names what MAY cross a barrier: VALU, SALU, transcendentals, LDS traffic and stores; not MFMAs, not global
+// loads -- the epilogue of the tile before still moves as a whole and is NOT interleaved with the MFMAs.
+#ifndef GH_MF_KSTEP
+#define GH_MF_KSTEP 1
+#endif
+#define GH_MF_KSTEP_MASK (0x002 | 0x004 | 0x040 | 0x080 | 0x100 | 0x200 | 0x400)
 // MULTI: the wave walks `bpw` blocks (light models); false = one block per wave, the block loop folds away.
 // BND: fp64 log-sum-exp against the pack-time bound (Cpk = the model's CpkRel64, st_glob = its per-state table)
 template <typename T, int KS, int MP, bool MULTI, bool FE = false, bool BND = false>
@@ -509,7 +524,8 @@ __global__ __launch_bounds__(64, (sizeof(T) == 4 ? 3 : 1)) void loglik_mfma_kern
 #ifndef GH_MF_RING64
 #define GH_MF_RING64 1
 #endif
-    constexpr int R = KS / (sizeof(T) == 4 ? GH_MF_RING32 : GH_MF_RING64);  // ring depth: half a tile (2) or a whole tile (1) of run-ahead
+    constexpr int R = KS / (sizeof(T) == 4 ? GH_MF_RING32 : GH_MF_RING64);  // ring depth: half a tile (2) or a whole tile (1) of k-steps
+    constexpr bool KSTEP = GH_MF_KSTEP >= 2 || (GH_MF_KSTEP == 1 && BND);       // refills held behind their k-step (above)
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     T* lds = reinterpret_cast<T*>(smem_raw);
     const int lane = threadIdx.x;
@@ -554,6 +570,12 @@ __global__ __launch_bounds__(64, (sizeof(T) == 4 ? 3 : 1)) void loglik_mfma_kern
             st_s0 = s0;
         }
     };
+    // A restage between two tiles ends with an explicit vmcnt(0) (expcnt / lgkmcnt left alone).  stage_states() loads under
+    // `lane < cnt` and stores under the same test, so the control-flow graph holds a path on which the load is issued and
+    // the store's wait is skipped; the wait-count pass then sees a load in flight into registers the next tile's first
+    // MFMA overwrites and drains EVERY load -- the operand ring included -- at the head of that tile, restage or not.
+    // The restage runs once per 64-state chunk; the drain in it is free and gives the tile loop its counted waits back.
+    auto states_landed = [&]() { if constexpr (BND) __builtin_amdgcn_s_waitcnt(0x0F70); };
     if (BND) stage_states(t_lo * (16 / (MP <= 16 ? MP : 16)));   // the first block's chunk, with the prologue's other loads
     if (sizeof(T) == 8 && MP != 1) {   // (a single-component state needs no exp / log)
         double tr[6];
@@ -613,6 +635,9 @@ __global__ __launch_bounds__(64, (sizeof(T) == 4 ? 3 : 1)) void loglik_mfma_kern
 
     // ---- stream the Gaussian tiles; the epilogue of tile t-1 runs under the MFMAs of tile t ----
     // (the host pads Apk / Cpk with one all-zero tile, so the run-ahead loads stay in bounds)
+    // (the order of these two prologue loads does not reach the tile loop: the frame loads that follow are waited for
+    //  before the first tile, and the loop is entered from the peeled first tile, which has issued its own refills.
+    //  C before the ring was measured on its own: the tile blocks of the listing and the step time did not move)
     T ring[R];
 #pragma unroll
     for (int j = 0; j < R; ++j) ring[j] = Apk[((int64_t)t_lo * KS + j) * 64 + lane];
@@ -622,6 +647,7 @@ __global__ __launch_bounds__(64, (sizeof(T) == 4 ? 3 : 1)) void loglik_mfma_kern
 
     // one tile of MFMAs: the first k-step takes the (prefetched) C values as its addend -- no accumulator
     // initialisation copies --, the next tile's C travels into the other register set; ring refilled as it is consumed
+    // (in the source; in the listing only under KSTEP)
     auto mfma_tile = [&](int t, V& acc0, V& acc1, const V& c_use, V& c_load) {
         const int tn = (!MULTI || t + 1 < t_hi) ? t + 1 : nxt_t0;   // one block per wave: run on into the zero pad tile
         const global_ptr<T> cp = uniform_ptr(Cpk + (unsigned)(tn * 16));
@@ -654,6 +680,9 @@ __global__ __launch_bounds__(64, (sizeof(T) == 4 ? 3 : 1)) void loglik_mfma_kern
             ring[ks % R] = (ks + R < KS) ? a_cur[(ks + R) / WIN][((ks + R) % WIN) * 64 + lane]
                                          : a_nxt[(ks + R - KS) / WIN][((ks + R - KS) % WIN) * 64 + lane];
 #endif
+            // (KSTEP) the k-step is a unit for the scheduler: no MFMA and no global load crosses this point, so the refill
+            // stays behind the MFMA pair that freed its slot and every pair waits on a count, for its own slot
+            if constexpr (KSTEP) __builtin_amdgcn_sched_barrier(GH_MF_KSTEP_MASK);
         }
     };
     auto flush = [&]() {
@@ -715,7 +744,7 @@ __global__ __launch_bounds__(64, (sizeof(T) == 4 ? 3 : 1)) void loglik_mfma_kern
             const int s_end = (MP <= 16) ? t_hi * (16 / (MP <= 16 ? MP : 16)) : t_hi / tiles_per_state;
             subset_cnt = ((s_end < S) ? s_end : S) - chunk_s0;
         }
-        if (BND && st_s0 != chunk_s0) { stage_states(chunk_s0); __syncthreads(); }
+        if (BND && st_s0 != chunk_s0) { stage_states(chunk_s0); states_landed(); __syncthreads(); }
 #ifdef GH_MF_TIMING
         tk[1] = clock64();
         tk[2] = tk[1];
@@ -732,7 +761,7 @@ __global__ __launch_bounds__(64, (sizeof(T) == 4 ? 3 : 1)) void loglik_mfma_kern
             }
             if (!subset && (t + 1) % chunk_tiles == 0 && t + 1 < n_tiles) {
                 flush();
-                if (BND) { stage_states(chunk_s0); __syncthreads(); }   // the next chunk's states
+                if (BND) { stage_states(chunk_s0); states_landed(); __syncthreads(); }   // the next chunk's states
             }
         };
         V r0, r1;
