@@ -850,6 +850,28 @@ int gh_online_create_bigram_wide(gh_ctx* ctx, const gh_lattices* lat, int64_t n_
 int gh_online_create_bigram_wide_settle(gh_ctx* ctx, const gh_lattices* lat, int64_t n_streams, int64_t frames, int window,
                                         gh_online** out);
 
+/* ------------------------------------------------ online decode on the K-layer word lattice
+ * The same session object over ONE graph in the LAYER form (gh_lattices_forms bit 1: the reference's own continuous recogniser,
+ * build_state_sequences(models, [[0..W-1]] * K) as main.py:35 builds it and main.py:59-67 reads its path; decode_hmm_states,
+ * decode.py:80-146) without a beam: the carried form of the layer sweep, one wave per stream, lane = (layer mod 4, word), two
+ * register sets.  Taken: 1 to 8 layers of up to 16 words of 2 to 8 states, with and without skip arcs, fp64 and fp32
+ * likelihoods.  CONTRACT as gh_online_create: after k >= 2 frames gh_online_result / gh_online_result_timed return bitwise what
+ * gh_viterbi / gh_viterbi_labels / gh_viterbi_labels_timed return for those k frames on the layer kernel (its own back-trace
+ * reads the history).  A stream that holds exactly ONE frame reports the causal column 0 -- the end costs after the first frame,
+ * the chosen end among them, no labels and an empty path -- as every other session does; a one-shot batch with a one-frame
+ * utterance leaves the layer kernel for the reference's column wrap, which on a layer lattice reads the column being filled,
+ * and a session cannot know that a stream will stay at one frame.
+ * A loop graph, a bigram graph, several graphs, a beam, and -- NOT OFFERED YET -- more than 16 words per layer, 9 to 16 layers and
+ * words of 12 or 16 states are GH_ERR_UNSUPPORTED before anything is allocated; every other gh_online_create* goes on refusing
+ * a K-layer lattice.  Per stream: 2 x 512 N B of state (both register sets of all 64 lanes, live or not; fp64 for fp32
+ * likelihoods too), 256 B of open word and 256 B of history per gh_layer_cpw(N, skip, 2) frames (5 columns per word at N = 2
+ * down to 1 at N = 8; N = 5 without skip arcs: 2, i.e. 128 B per frame); a size the device cannot give is GH_ERR_NOMEM, the
+ * message holds the byte count.  max_frames is a hard capacity as in gh_online_create: an utterance of exactly K words is
+ * bounded in length, so the session keeps its FULL HISTORY and DOES NOT SETTLE -- gh_online_commit* / gh_online_tail* on it are
+ * GH_ERR_UNSUPPORTED, and there is no window.  gh_online_push, gh_online_result*, gh_online_reset, gh_online_frames and
+ * gh_online_destroy serve the session as they serve every other, with the same checks. */
+int gh_online_create_layers(gh_ctx* ctx, const gh_lattices* lat, int64_t n_streams, int64_t max_frames, gh_online** out);
+
 /* ------------------------------------------------ online isolated-word recognition: A5 while the audio is still arriving
  * HMM.evaluate (hmm.py:126-135) of every word model, carried across the chunks of n_streams live utterances: the cost of a
  * word is the last state's cell of the last column, and a column depends on the previous column only, so a stream keeps

@@ -1,8 +1,8 @@
 // The online session (gh_online_*).  gh_online.hip is the session itself: create, push, result, commit, tail and the end kernel.
 // What a session does with a chunk and with its history depends on its FORM alone, and the table below says per form which
 // launcher does it: the carried sweeps (gh_viterbi_online.hip, gh_viterbi_bigram_online.hip, gh_viterbi_online_wide.hip,
-// gh_viterbi_bigram_online_wide.hip) and the settle and segment walks of commit and tail (gh_online_settle.hip: both narrow
-// forms; gh_online_wide_settle.hip, gh_online_bigram_wide_settle.hip).
+// gh_viterbi_bigram_online_wide.hip, gh_viterbi_layers_online.hip) and the settle and segment walks of commit and tail
+// (gh_online_settle.hip: both narrow forms; gh_online_wide_settle.hip, gh_online_bigram_wide_settle.hip).
 #pragma once
 #include "gh_internal.h"
 #include "gh_host.h"
@@ -21,15 +21,15 @@ struct gh_online_anchor {
 };
 
 // argument block of the carried sweeps (viterbi_online_kernel, viterbi_bigram_online_kernel, viterbi_online_wide_kernel,
-// viterbi_bigram_online_wide_kernel)
+// viterbi_bigram_online_wide_kernel, viterbi_layers_online_kernel)
 struct gh_online_args {
     const gh_layerform* lf;
     const void* nll;
     int S;
     const gh_online_slot* slots;
     int64_t n_slots;
-    double* prev;          // [n_streams][N][lanes of the form]
-    uint32_t* open;        // [n_streams][16] (a form without an open word: null)
+    double* prev;          // [n_streams][register sets of the form][N][lanes of the form]
+    uint32_t* open;        // [n_streams][lanes of the form] (a form without an open word: null)
     uint16_t* hist;        // decision words, stream k at k * hist_stride (uint16 units, as gh_layers_args::bp)
     int64_t hist_stride;
     int ring_words;        // word index i of a stream lives at i % ring_words (gh_online::ring_words)
@@ -65,7 +65,7 @@ struct gh_settle_args {
 
 struct gh_online;
 
-// ------------------------------------------------------------------------------------------------------- the four forms
+// ------------------------------------------------------------------------------------------------------- the five forms
 // Every launcher of a family has the family's signature; the graph (on->lat->h_layers, and the cost table on->lat->d_bigram_wide
 // of the wide bigram form) comes from the session.
 //   sweep: the chunks of a.slots continue their streams (f64: the batch's likelihoods are doubles);
@@ -76,33 +76,39 @@ struct gh_online;
 typedef int gh_online_sweep_fn(gh_ctx* ctx, const gh_online* on, const gh_online_args& a, bool f64);
 typedef int gh_online_walk_fn(gh_ctx* ctx, const gh_online* on, const gh_settle_args& a, bool settle, const char* who);
 typedef int gh_online_trace_fn(gh_ctx* ctx, const gh_online* on, const gh_layers_args& a, int64_t n, bool timed);
-gh_online_sweep_fn gh_launch_online_loop, gh_launch_online_bigram, gh_launch_online_wide, gh_launch_online_bigram_wide;
+gh_online_sweep_fn gh_launch_online_loop, gh_launch_online_bigram, gh_launch_online_wide, gh_launch_online_bigram_wide,
+    gh_launch_online_layers;
 gh_online_walk_fn gh_launch_online_loop_settle, gh_launch_online_bigram_settle, gh_launch_online_wide_settle,
     gh_launch_online_bigram_wide_settle;
 gh_online_trace_fn gh_online_loop_trace, gh_online_bigram_trace;     // (gh_online.hip; each hands a wide graph on by itself)
 constexpr int gh_one_cpw(int, bool) { return 1; }
+constexpr int gh_layer2_cpw(int N, bool skip) { return gh_layer_cpw(N, skip, 2); }   // layer form, two register sets (up to 8 layers)
 
 struct gh_online_form {
-    const char* grammar;             // "loop" or "bigram": the rows of the graph and the word of gh_online_push's messages
-    int lanes;                       // word lanes per stream: 16 -- up to GH_LAYERS_ROWW words, four streams to a wave, DPP row = stream
-                                     // -- or 64 -- 17 .. GH_LAYERS_MAXW words, a wave per stream.  State: [n_streams][N][lanes] doubles
-    bool open_word;                  // a decision word holds several columns, so a chunk may end inside one: [n_streams][16] open words
-                                     // are carried beside the state.  false: one complete word per column and lane
+    const char* grammar;             // "loop", "bigram" or "layers": the rows of the graph and the word of gh_online_push's messages
+    int lanes;                       // lanes per stream: 16 -- up to GH_LAYERS_ROWW words, four streams to a wave, DPP row = stream
+                                     // -- or 64 -- a wave per stream: 17 .. GH_LAYERS_MAXW words, lane = word, or the K-layer lattice,
+                                     // lane = (layer mod 4, word)
+    int sets;                        // register sets per lane: 1, or 2 in the K-layer lattice (layers 0-3 and 4-7).
+                                     // State: [n_streams][sets][N][lanes] doubles
+    bool open_word;                  // a decision word holds several columns, so a chunk may end inside one: [n_streams][lanes] open
+                                     // words are carried beside the state.  false: one complete word per column and lane
     bool bigram_rows;                // state 0 of word w is row loop_row + W + w (the loop numbering: loop_row + 1 + w)
     int (*cpw)(int N, bool skip);    // columns per decision word.  A history of `frames` frames is ceil(frames / cpw) words -- one
                                      // more where it is a window: the word the anchor lies in is kept -- of `lanes` x 4 B each, and
                                      // that count is ring_words: full history never wraps
     gh_online_sweep_fn* sweep;
-    gh_online_walk_fn* walk;
+    gh_online_walk_fn* walk;         // (null: no entry point makes a session of this form that settles)
     gh_online_trace_fn* trace;
 };
 
-enum gh_online_form_id { GH_ONLINE_LOOP, GH_ONLINE_BIGRAM, GH_ONLINE_WIDE, GH_ONLINE_BIGRAM_WIDE };
+enum gh_online_form_id { GH_ONLINE_LOOP, GH_ONLINE_BIGRAM, GH_ONLINE_WIDE, GH_ONLINE_BIGRAM_WIDE, GH_ONLINE_LAYERS };
 inline constexpr gh_online_form gh_online_forms[] = {
-    {"loop", 16, true, false, gh_loop_cpw, gh_launch_online_loop, gh_launch_online_loop_settle, gh_online_loop_trace},
-    {"bigram", 16, true, true, gh_bigram_cpw, gh_launch_online_bigram, gh_launch_online_bigram_settle, gh_online_bigram_trace},
-    {"loop", 64, false, false, gh_one_cpw, gh_launch_online_wide, gh_launch_online_wide_settle, gh_online_loop_trace},
-    {"bigram", 64, false, true, gh_one_cpw, gh_launch_online_bigram_wide, gh_launch_online_bigram_wide_settle, gh_online_bigram_trace},
+    {"loop", 16, 1, true, false, gh_loop_cpw, gh_launch_online_loop, gh_launch_online_loop_settle, gh_online_loop_trace},
+    {"bigram", 16, 1, true, true, gh_bigram_cpw, gh_launch_online_bigram, gh_launch_online_bigram_settle, gh_online_bigram_trace},
+    {"loop", 64, 1, false, false, gh_one_cpw, gh_launch_online_wide, gh_launch_online_wide_settle, gh_online_loop_trace},
+    {"bigram", 64, 1, false, true, gh_one_cpw, gh_launch_online_bigram_wide, gh_launch_online_bigram_wide_settle, gh_online_bigram_trace},
+    {"layers", 64, 2, true, false, gh_layer2_cpw, gh_launch_online_layers, nullptr, gh_online_loop_trace},
 };
 
 struct gh_online {
@@ -110,7 +116,7 @@ struct gh_online {
     const gh_lattices* lat;        // must outlive the session
     const gh_online_form* form;    // a row of gh_online_forms: push, end, back-trace and the walks each ask it, nothing else
     bool settles;                  // gh_online_commit / gh_online_tail serve the session: it has anchors (a narrow loop session
-                                   // always, the others from their gh_online_create_*_settle)
+                                   // always, the others from their gh_online_create_*_settle; a layer session never)
     int64_t n_streams, max_frames, hist_stride;
     int64_t window;                // > 0: the history is a ring that holds `window` unsettled frames; gh_online_result is refused
     int32_t ring_words;            // decision words per lane in a stream's history: word index i lives at i % ring_words

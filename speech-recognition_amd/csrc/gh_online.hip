@@ -8,8 +8,9 @@
 // UNCHANGED on the history, and "the result after k frames" is bitwise the whole decode of the first k frames: end costs,
 // chosen end, path and labels (main.py:59-67).
 //
-// The FORM of a session -- narrow or wide, loop or bigram rows: gh_online_forms in gh_online.h -- is fixed by the entry point
-// that made it and says how many lanes a stream has, how its history is sized, and which sweep, walks and back-trace serve it.
+// The FORM of a session -- narrow or wide, loop or bigram rows, or the K-layer lattice: gh_online_forms in gh_online.h -- is fixed
+// by the entry point that made it and says how many lanes a stream has, how its history is sized, and which sweep, walks and
+// back-trace serve it.
 // Independent of the form, a session either keeps its FULL HISTORY (max_frames is its capacity, nothing ever wraps) or has a
 // WINDOW: the history is addressed as a ring, decision word index i of a stream at i % ring_words, and holds `window`
 // unsettled frames and the word the anchor lies in.  A session that SETTLES has anchors: gh_online_commit moves them on and
@@ -55,13 +56,50 @@ __global__ __launch_bounds__(64) void online_end_kernel(const gh_layerform* __re
     if (w == 0) best_end[i] = T > 0 ? best_slot : -1;
 }
 
+// The same for the K-layer lattice (two register sets): the tail of viterbi_layers_kernel.  A block per stream, lane = (layer mod 4,
+// word); state s of word w in layer 4 h + kk is row layer * (P + 1) + 1 + w * N + s and lives in set h of the lane.
+__global__ __launch_bounds__(64) void online_layers_end_kernel(const gh_layerform* __restrict__ lf, const int32_t* __restrict__ end_slot,
+                                                               int n_end, const double* __restrict__ prev, const int64_t* __restrict__ ids,
+                                                               const int64_t* __restrict__ utt_off, int64_t n, double* __restrict__ end_cost,
+                                                               int32_t* __restrict__ best_end) {
+    const int lane = threadIdx.x, kk = lane >> 4, w = lane & 15;
+    const int64_t i = blockIdx.x;                              // (grid = n)
+    const int W = lf->W, N = lf->N, K = lf->K, P = lf->P;
+    const int64_t stream = ids[i];
+    const int64_t T = utt_off[i + 1] - utt_off[i];
+    const double INF = INFINITY;
+    double best_v = INF;
+    int best_slot = -1;
+    if (w < W)
+        for (int h = 0; h < 2; ++h) {
+            const int layer = 4 * h + kk;
+            if (layer >= K) continue;
+            for (int s = 0; s < N; ++s) {
+                const int es = end_slot[layer * (P + 1) + 1 + w * N + s];
+                if (es >= 0) {
+                    const double v = T > 0 ? prev[((stream * 2 + h) * N + s) * 64 + lane] : INF;
+                    end_cost[i * n_end + es] = v;
+                    if (v < best_v || (v == best_v && es > best_slot)) { best_v = v; best_slot = es; }
+                }
+            }
+        }
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) {
+        const double ov = __shfl_xor(best_v, o);
+        const int os = __shfl_xor(best_slot, o);
+        if (ov < best_v || (ov == best_v && os > best_slot)) { best_v = ov; best_slot = os; }
+    }
+    if (lane == 0) best_end[i] = T > 0 ? best_slot : -1;
+}
+
 int launch_online_end(gh_ctx* ctx, const gh_online* on, const int64_t* d_ids, const int64_t* d_utt_off, int64_t n, double* d_end_cost,
                       int32_t* d_best_end) {
     if (n <= 0) return GH_OK;
     const gh_online_form& fm = *on->form;
     const int per_block = 64 / fm.lanes;
-    const auto kernel = fm.lanes == 16 ? (fm.bigram_rows ? online_end_kernel<16, true> : online_end_kernel<16, false>)
-                                       : (fm.bigram_rows ? online_end_kernel<64, true> : online_end_kernel<64, false>);
+    const auto kernel = fm.sets == 2   ? online_layers_end_kernel
+                        : fm.lanes == 16 ? (fm.bigram_rows ? online_end_kernel<16, true> : online_end_kernel<16, false>)
+                                         : (fm.bigram_rows ? online_end_kernel<64, true> : online_end_kernel<64, false>);
     hipLaunchKernelGGL(kernel, dim3((unsigned)((n + per_block - 1) / per_block)), dim3(64), 0, ctx->stream, on->lat->d_layers,
                        on->lat->d_lf_end_slot, on->lat->lat[0].n_end, on->d_prev, d_ids, d_utt_off, n, d_end_cost, d_best_end);
     GH_HIP(hipGetLastError());
@@ -85,7 +123,7 @@ int check_loop(const char* who, const gh_lattices* lat) {
     const char* why = not_one_plain_graph(lat);
     if (why) {}
     else if (lat->bigram_ok) why = "a bigram grammar (gh_online_create_bigram takes it, with full history)";
-    else if (lat->layers_ok && !lat->h_layers.loop) why = "a K-layer word lattice";
+    else if (lat->layers_ok && !lat->h_layers.loop) why = "a K-layer word lattice (gh_online_create_layers takes it)";
     else if (!lat->layers_ok || lat->h_layers.loop != 1) why = "a graph that is not in loop form";
     else if (lat->h_layers.W > GH_LAYERS_ROWW) why = "more than 16 words";
     return why ? refuse(who, "online decoding takes the word-loop grammar with up to 16 words", why) : GH_OK;
@@ -95,7 +133,7 @@ int check_bigram(const char* who, const gh_lattices* lat) {
     const char* why = not_one_plain_graph(lat);
     if (why) {}
     else if (lat->layers_ok && lat->h_layers.loop) why = "a word-loop graph (gh_online_create takes it)";
-    else if (lat->layers_ok) why = "a K-layer word lattice";
+    else if (lat->layers_ok) why = "a K-layer word lattice (gh_online_create_layers takes it)";
     else if (!lat->bigram_ok) why = "a graph that is not in bigram form (more than 16 words, and 16 states with skip arcs, are not)";
     else if (!gh_bigram_n_ok(lat->h_layers.N, lat->h_layers.skip)) why = "a word size the bigram sweep is not built for";
     return why ? refuse(who, "online decoding takes the bigram grammar with up to 16 words", why) : GH_OK;
@@ -105,7 +143,7 @@ int check_wide(const char* who, const gh_lattices* lat) {
     const char* why = not_one_plain_graph(lat);
     if (why) {}
     else if (lat->bigram_ok) why = "a bigram grammar (gh_online_create_bigram takes it)";
-    else if (lat->layers_ok && !lat->h_layers.loop) why = "a K-layer word lattice";
+    else if (lat->layers_ok && !lat->h_layers.loop) why = "a K-layer word lattice (gh_online_create_layers takes it)";
     else if (!lat->layers_ok || lat->h_layers.loop != 1) why = "a graph that is not in loop form";
     else if (lat->h_layers.W <= GH_LAYERS_ROWW) why = "16 words or fewer (gh_online_create takes it)";
     else if (lat->h_layers.W > GH_LAYERS_MAXW) why = "more than 64 words";
@@ -119,11 +157,23 @@ int check_bigram_wide(const char* who, const gh_lattices* lat) {
     else if (lat->bigram_ok) why = "a bigram grammar of 16 words or fewer (gh_online_create_bigram takes it)";
     else if (lat->layers_ok && lat->h_layers.loop)
         why = lat->h_layers.W > GH_LAYERS_ROWW ? "a word-loop graph (gh_online_create_wide takes it)" : "a word-loop graph (gh_online_create takes it)";
-    else if (lat->layers_ok) why = "a K-layer word lattice";
+    else if (lat->layers_ok) why = "a K-layer word lattice (gh_online_create_layers takes it)";
     else if (!lat->bigram_wide_ok) why = "a graph that is not in wide bigram form (more than 64 words, and more than 8 states per word, are not)";
     if (why) return refuse(who, "wide online bigram decoding takes the bigram grammar with 17 to 64 words of 2 to 8 states", why);
     GH_REQUIRE(lat->d_bigram_wide, "%s: internal: wide bigram form without its cost table", who);
     return GH_OK;
+}
+// (two register sets and 32-bit decision words: up to 8 layers of words of up to 8 states -- gh_viterbi_layers_online.hip)
+int check_layers(const char* who, const gh_lattices* lat) {
+    const char* why = not_one_plain_graph(lat);
+    if (why) {}
+    else if (lat->bigram_ok || lat->bigram_wide_ok) why = "a bigram grammar (gh_online_create_bigram and gh_online_create_bigram_wide take it)";
+    else if (lat->layers_ok && lat->h_layers.loop) why = "a word-loop graph (gh_online_create and gh_online_create_wide take it)";
+    else if (!lat->layers_ok) why = "a graph that is not in layer form";
+    else if (lat->h_layers.W > GH_LAYERS_ROWW) why = "more than 16 words per layer (not offered yet)";
+    else if (lat->h_layers.K > 8) why = "more than 8 layers (not offered yet)";
+    else if (lat->h_layers.N > 8) why = "more than 8 states per word (not offered yet)";
+    return why ? refuse(who, "online decoding of a K-layer word lattice takes 1 to 8 layers of up to 16 words of 2 to 8 states", why) : GH_OK;
 }
 static_assert(GH_LAYERS_ROWW == 16 && GH_LAYERS_MAXW == 64, "the word counts the messages above name");
 
@@ -141,6 +191,7 @@ int online_create(const char* who, gh_online_form_id id, bool settles, bool wind
         case GH_ONLINE_BIGRAM: rc = check_bigram(who, lat); break;
         case GH_ONLINE_WIDE: rc = check_wide(who, lat); break;
         case GH_ONLINE_BIGRAM_WIDE: rc = check_bigram_wide(who, lat); break;
+        case GH_ONLINE_LAYERS: rc = check_layers(who, lat); break;
     }
     if (rc) return rc;
     const gh_online_form& fm = gh_online_forms[id];
@@ -149,7 +200,7 @@ int online_create(const char* who, gh_online_form_id id, bool settles, bool wind
     // streams x stride is checked before anything is allocated
     const int cpw = fm.cpw(f.N, f.skip != 0);
     const int64_t words = (frames + cpw - 1) / cpw + (window ? 1 : 0), stride = words * fm.lanes * 2;
-    const size_t stream_bytes = (size_t)stride * 2 + (size_t)f.N * fm.lanes * sizeof(double) + (fm.open_word ? fm.lanes * 4 : 0) +
+    const size_t stream_bytes = (size_t)stride * 2 + (size_t)fm.sets * f.N * fm.lanes * sizeof(double) + (fm.open_word ? fm.lanes * 4 : 0) +
                                 sizeof(gh_online_slot) + (settles ? sizeof(gh_online_anchor) : 0);
     if ((size_t)n_streams > (SIZE_MAX / 2 - 2048) / stream_bytes) {
         gh_set_error("%s: %lld streams x %lld frames (%.0f bytes): the size does not fit a size_t", who, (long long)n_streams,
@@ -167,7 +218,7 @@ int online_create(const char* who, gh_online_form_id id, bool settles, bool wind
     on->settled.assign((size_t)n_streams, 0);
     on->seen.assign((size_t)n_streams, 0);
     auto pad = [](size_t b) { return (b + 255) & ~size_t(255); };
-    const size_t b_prev = pad((size_t)n_streams * f.N * fm.lanes * sizeof(double)), b_open = fm.open_word ? pad((size_t)n_streams * fm.lanes * 4) : 0;
+    const size_t b_prev = pad((size_t)n_streams * fm.sets * f.N * fm.lanes * sizeof(double)), b_open = fm.open_word ? pad((size_t)n_streams * fm.lanes * 4) : 0;
     const size_t b_hist = pad((size_t)n_streams * (size_t)stride * 2), b_slots = pad((size_t)n_streams * sizeof(gh_online_slot));
     const size_t b_anchor = settles ? pad((size_t)n_streams * sizeof(gh_online_anchor)) : 0;
     const size_t total = b_prev + b_open + b_hist + b_slots + b_anchor;
@@ -193,7 +244,10 @@ int online_create(const char* who, gh_online_form_id id, bool settles, bool wind
 // a wide session that does not settle is refused with its own sentence, whatever its rows; then a narrow bigram one
 int refuse_unsettled(const gh_online* on, const char* who) {
     if (on->settles) return GH_OK;
-    if (on->form->lanes == 64)
+    if (on->form->sets == 2)
+        gh_set_error("%s: a session on a K-layer word lattice keeps its full history and does not settle (an utterance of exactly K "
+                     "words is bounded in length); gh_online_result gives the running hypothesis", who);
+    else if (on->form->lanes == 64)
         gh_set_error("%s: a wide session (more than 16 words) keeps its full history and does not settle; gh_online_result "
                      "gives the running hypothesis", who);
     else
@@ -314,6 +368,10 @@ extern "C" int gh_online_create_bigram_wide(gh_ctx* ctx, const gh_lattices* lat,
 extern "C" int gh_online_create_bigram_wide_settle(gh_ctx* ctx, const gh_lattices* lat, int64_t n_streams, int64_t frames, int window,
                                                    gh_online** out) {
     return online_create("gh_online_create_bigram_wide_settle", GH_ONLINE_BIGRAM_WIDE, true, window != 0, ctx, lat, n_streams, frames, out);
+}
+
+extern "C" int gh_online_create_layers(gh_ctx* ctx, const gh_lattices* lat, int64_t n_streams, int64_t max_frames, gh_online** out) {
+    return online_create("gh_online_create_layers", GH_ONLINE_LAYERS, false, false, ctx, lat, n_streams, max_frames, out);
 }
 
 extern "C" void gh_online_destroy(gh_online* on) {

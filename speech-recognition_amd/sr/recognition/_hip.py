@@ -182,6 +182,7 @@ SIGNATURES = {
     "gh_online_create_wide_settle": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.POINTER(C.c_void_p)]),
     "gh_online_create_bigram_wide": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.POINTER(C.c_void_p)]),
     "gh_online_create_bigram_wide_settle": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.POINTER(C.c_void_p)]),
+    "gh_online_create_layers": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.POINTER(C.c_void_p)]),
     "gh_online_commit": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, _c_i64p, _c_i64p, _c_i32p, _c_i32p, _c_i64p, _c_i32p]),
     "gh_online_commit_timed": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, _c_i64p, _c_i64p, _c_i32p, _c_i32p, _c_i64p, _c_i32p, _c_i32p]),
     "gh_online_tail": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, _c_i64p, _c_f64p, _c_i32p, _c_i32p, _c_i32p, _c_i64p, _c_i32p]),
@@ -1662,8 +1663,8 @@ class OnlineBigramSession(OnlineSession):
 
 
 class _WideSession(OnlineSession):
-    """What the two wide session classes share: where the session does not settle, `commit` and `tail` ask the library and
-    raise its refusal."""
+    """What the two wide session classes and the layer session share: where the session does not settle, `commit` and `tail`
+    ask the library and raise its refusal."""
 
     def __init__(self, ctx, lat, n_streams, max_frames=None, window=None, settle=False):
         self._open_settle(ctx, lat, n_streams, max_frames, window, settle)
@@ -1718,6 +1719,24 @@ class OnlineBigramWideSession(_WideSession):
 
     _create, _create_settle = "gh_online_create_bigram_wide", "gh_online_create_bigram_wide_settle"
     _does_not_settle = "a wide bigram session keeps its full history and does not settle: result() gives the running hypothesis"
+
+
+class OnlineLayersSession(_WideSession):
+    """Online decode over ONE K-layer word lattice (gh_online_create_layers): the `OnlineSession` of the reference's own
+    continuous recogniser (main.py:35), one wave per stream, lane = (layer mod 4, word).  `push`, `result` (labels,
+    begins, paths), `reset` and `frames` are the parent's, and from two frames on `result` is bitwise the one-shot
+    layer-form decode of the frames a stream has taken; a stream that holds exactly one frame reports the causal column 0
+    (end costs, chosen end, no labels, an empty path).  Taken: 1 to 8 layers of up to 16 words of 2 to 8 states.  A loop
+    graph, a bigram graph, a beam, several graphs and -- not offered yet -- 9 to 16 layers, words of 12 or 16 states and
+    17 to 64 words per layer raise `Unsupported`.
+    The session keeps its full history -- `max_frames` is a hard capacity; an utterance of exactly K words is bounded in
+    length -- and does not settle: `commit` and `tail` raise `Unsupported`, and there is no window."""
+
+    _does_not_settle = "a session on a K-layer lattice keeps its full history and does not settle: result() gives the running hypothesis"
+
+    def __init__(self, ctx, lat, n_streams, max_frames):
+        self.settles = False
+        self._open(ctx, lat, n_streams, max_frames, None, "gh_online_create_layers")
 
 
 class WordStreamSession:

@@ -460,6 +460,15 @@ class ContinuousDecoder:
         without them, and without them a larger decoder is refused as before.  Any other value of `wide` is a ValueError."""
         return OnlineBigramDecoder(self, n_streams, max_frames, window, frontend, endpointer, times, settle, wide)
 
+    def online_layers(self, n_streams, max_frames, frontend=None, endpointer=None, times=False):
+        """An `OnlineLayersDecoder` of `n_streams` live utterances sharing this decoder's packed mixtures and K-layer
+        lattice (grammar="layers" only: anything else raises `_hip.Unsupported` before the GPU is touched).  `max_frames`
+        is a hard capacity per stream: an utterance of exactly `n_layers` words is bounded in length, so the whole
+        history is kept, nothing settles (`commit`, `settled` and `settled_times` raise `_hip.Unsupported`) and there is
+        no window.  frontend / endpointer / times: as in `online`.  Taken: 1 to 8 layers of up to 16 words of 2 to 8
+        states; 9 to 16 layers, words of 12 or 16 states and 17 to 64 words are not offered yet (`_hip.Unsupported`)."""
+        return OnlineLayersDecoder(self, n_streams, max_frames, frontend, endpointer, times)
+
 
 class _OnlineStreams:
     """The stream plumbing `OnlineDecoder` and `OnlineWordRecognizer` share: `n_streams` live utterances that take feature
@@ -705,7 +714,8 @@ class OnlineDecoder(_OnlineStreams):
     def __init__(self, decoder, n_streams, max_frames=None, window=None, frontend=None, endpointer=None, times=False, settle=False):
         if decoder.grammar != "loop":
             raise _hip.Unsupported("online decoding takes the word-loop grammar (grammar='loop'), not %r%s"
-                                   % (decoder.grammar, " (online_bigram takes it)" if decoder.grammar == "bigram" else ""))
+                                   % (decoder.grammar, " (online_bigram takes it)" if decoder.grammar == "bigram" else
+                                      " (online_layers takes it)" if decoder.grammar == "layers" else ""))
         if (max_frames is None) == (window is None):
             raise ValueError("exactly one of max_frames and window must be given")
         if int(n_streams) < 1 or int(window if max_frames is None else max_frames) < 1:
@@ -916,7 +926,8 @@ class OnlineBigramDecoder(OnlineDecoder):
                  wide=False):
         if decoder.grammar != "bigram":
             raise _hip.Unsupported("online_bigram takes the bigram grammar (grammar='bigram'), not %r%s"
-                                   % (decoder.grammar, " (online takes it)" if decoder.grammar == "loop" else ""))
+                                   % (decoder.grammar, " (online takes it)" if decoder.grammar == "loop" else
+                                      " (online_layers takes it)" if decoder.grammar == "layers" else ""))
         if (max_frames is None) == (window is None):
             raise ValueError("exactly one of max_frames and window must be given")
         if int(n_streams) < 1 or int(window if max_frames is None else max_frames) < 1:
@@ -971,6 +982,57 @@ class OnlineBigramDecoder(OnlineDecoder):
         if not self.settles:
             self._refuse()
         return super().settled_times(ids)
+
+
+class OnlineLayersDecoder(OnlineDecoder):
+    """`OnlineDecoder` for a decoder with the K-layer lattice, the reference's own continuous recogniser (main.py:35): the
+    same streams, the same `push` / `push_batch` / `push_audio` / `push_recording` / `result` / `finish` / `reset` /
+    `frames` and word times, over the carried layer sweep (gh_online_create_layers: one wave per stream, lane = (layer
+    mod 4, word)).
+
+        dec = ContinuousDecoder(models, n_layers=7)
+        on = dec.online_layers(n_streams=64, max_frames=1000, times=True)
+        on.push([3, 7], [frames_of_3, frames_of_7])
+        words, info = on.result([3]); info["begins"][0]
+
+    From two frames on `result` gives what `decode_batch` gives for the frames pushed so far: exactly `n_layers` words
+    once the frames hold that many, no words (and +inf end costs) before.  A stream that holds exactly ONE frame reports
+    the causal column 0: its end costs, the chosen end among them, no words and an empty path (`decode_batch` of a
+    one-frame utterance takes the reference's column wrap instead, which on a layer lattice reads the column being
+    filled; a stream cannot know that it will stay at one frame).
+
+    An utterance of exactly K words is bounded in length, so the whole history is kept, `max_frames` is a hard capacity
+    (128 B per frame and stream at 5 states without skip arcs) and NOTHING SETTLES: there is no `window=`, and `commit`,
+    `settled` and `settled_times` raise `_hip.Unsupported`.  Taken: 1 to 8 layers of up to 16 words of 2 to 8 states.  Not
+    offered yet, refused by the library by name: 9 to 16 layers, words of 12 or 16 states, 17 to 64 words per layer."""
+
+    settles = False
+
+    def __init__(self, decoder, n_streams, max_frames, frontend=None, endpointer=None, times=False):
+        if decoder.grammar != "layers":
+            raise _hip.Unsupported("online_layers takes the K-layer lattice (grammar='layers'), not %r%s"
+                                   % (decoder.grammar, " (online takes it)" if decoder.grammar == "loop" else
+                                      " (online_bigram takes it)" if decoder.grammar == "bigram" else ""))
+        if max_frames is None or int(n_streams) < 1 or int(max_frames) < 1:
+            raise ValueError("n_streams and max_frames must be positive")
+        self._attach(decoder.ctx, decoder.dtype, decoder.gmm, n_streams, frontend, endpointer)
+        self.decoder = decoder
+        self.max_frames, self.window = int(max_frames), None
+        self.session = _hip.OnlineLayersSession(decoder.ctx, decoder.lat, self.n_streams, self.max_frames)
+        self._init_words(decoder, times)                              # (nothing settles: the settled words stay empty)
+
+    def _refuse(self):
+        raise _hip.Unsupported("a decoder on the K-layer lattice has no settled prefix: it keeps its full history, and result() gives "
+                               "the running hypothesis")
+
+    def commit(self, ids=None, want_times=False):
+        self._refuse()
+
+    def settled(self, ids=None):
+        self._refuse()
+
+    def settled_times(self, ids=None):
+        self._refuse()
 
 
 class OnlineWordRecognizer(_OnlineStreams):
