@@ -736,8 +736,8 @@ int gh_online_result_timed(gh_ctx* ctx, gh_online* on, int64_t n, const int64_t*
  * frames), rounded up to whole decision words plus one word for the anchor's own: device memory per stream no longer
  * depends on how long the stream runs, which is bounded by the 32-bit column only.  Same graph forms and refusals as
  * gh_online_create.  A push that would take any of its streams past the window is refused as a whole (GH_ERR_INVALID,
- * the message names the stream).  THERE IS NO FORCED COMMIT: a stream whose traces have not met within the window cannot
- * take more frames; it can be read (gh_online_tail) and reset.  On such a session gh_online_result is
+ * the message names the stream).  A COMMIT FORCES NOTHING: a stream whose traces have not met within the window cannot
+ * take more frames; it can be read (gh_online_tail) and reset, or gh_online_force (below) bounds its tail.  On such a session gh_online_result is
  * GH_ERR_UNSUPPORTED (paths are not offered); gh_online_commit and gh_online_tail work on both kinds of session, and on
  * one with full history a commit frees nothing and gh_online_result goes on covering the whole history. */
 int gh_online_create_window(gh_ctx* ctx, const gh_lattices* lat, int64_t n_streams, int64_t window_frames, gh_online** out);
@@ -768,6 +768,20 @@ int gh_online_commit_timed(gh_ctx* ctx, gh_online* on, int64_t n, const int64_t*
 int gh_online_tail_timed(gh_ctx* ctx, gh_online* on, int64_t n, const int64_t* ids /*[n] or NULL*/, double* end_cost, int32_t* best_end,
                          const int32_t* row_label, int32_t* labels, const int64_t* label_off /*[n+1]*/, int32_t* n_labels,
                          int32_t* out_begin /*like labels, or NULL*/);
+/* THE FORCED COMMIT (no counterpart in the reference, which decodes whole utterances): bounds the unsettled tail of the
+ * streams ids[0..n) (NULL: all; distinct) to max_tail >= 1 frames.  For a stream with T frames, anchor column lo (-1: none)
+ * and c = T - 1 - max_tail: nothing happens where T < 2, c < 0, c <= lo, or the chosen end of the newest column (the
+ * best_end of gh_online_tail) is +inf.  Otherwise let A be the cell in which the trace of the chosen end arrives in column
+ * c; every live cell of the newest column whose trace does not pass A is set to +inf in the carried column, and pruned[i]
+ * is their number (0 where nothing had to be done).  Nothing else is written: the gh_online_commit called NEXT finds an
+ * anchor in a column >= c, so that frames - settled_frames <= max_tail, and hands out the words.  The chosen end survives,
+ * so gh_online_tail gives the same words before and after; the settled words stay a prefix of every later result.  From
+ * the forced tick on, a stream is the carried decode with those cells removed, no longer the one-shot decode of its prefix.
+ * With a window W and a commit + force + commit after every push of at most W - max_tail frames, no push is refused for
+ * the window.  All checks come before anything is enqueued: max_tail < 1 and a stream out of range or named twice are
+ * GH_ERR_INVALID; a bigram, wide, wide bigram or K-layer session is GH_ERR_UNSUPPORTED (not built yet; the narrow loop
+ * session of gh_online_create / gh_online_create_window has it).  Synchronises. */
+int gh_online_force(gh_ctx* ctx, gh_online* on, int64_t n, const int64_t* ids /*[n] or NULL*/, int64_t max_tail, int32_t* pruned /*[n]*/);
 
 /* ------------------------------------------------ online decode with a bigram grammar
  * The same session object over ONE graph in bigram form (gh_lattices_forms bit 5: the word loop with word-to-word costs, up

@@ -63,6 +63,22 @@ struct gh_settle_args {
     int32_t* begins;               // timed twins: the begin column of every label, laid out like `labels` (appended: no older field moves)
 };
 
+// argument block of the forced commit (online_force_kernel, gh_online_force.hip): the narrow loop form only
+struct gh_force_args {
+    const gh_layerform* lf;
+    const int32_t* end_slot;       // [R]: the end slot of a row, -1 where it is no end row (gh_lattices::d_lf_end_slot)
+    const gh_settle_task* tasks;
+    int64_t n;
+    double* prev;                  // [n_streams][N][16]: the carried column, the ONE thing the kernel writes besides `pruned`
+    const uint16_t* hist;          // as gh_settle_args
+    int64_t hist_stride;
+    int ring_words;
+    int max_tail;                  // M: the column to force is T - 1 - M
+    const gh_online_anchor* anchor;
+    int32_t* pruned;               // [n]: cells set to +inf
+    int* flag;
+};
+
 struct gh_online;
 
 // ------------------------------------------------------------------------------------------------------- the five forms
@@ -81,6 +97,7 @@ gh_online_sweep_fn gh_launch_online_loop, gh_launch_online_bigram, gh_launch_onl
 gh_online_walk_fn gh_launch_online_loop_settle, gh_launch_online_bigram_settle, gh_launch_online_wide_settle,
     gh_launch_online_bigram_wide_settle;
 gh_online_trace_fn gh_online_loop_trace, gh_online_bigram_trace;     // (gh_online.hip; each hands a wide graph on by itself)
+int gh_launch_online_loop_force(gh_ctx* ctx, const gh_online* on, const gh_force_args& a);   // gh_online_force.hip
 constexpr int gh_one_cpw(int, bool) { return 1; }
 constexpr int gh_layer2_cpw(int N, bool skip) { return gh_layer_cpw(N, skip, 2); }   // layer form, two register sets (up to 8 layers)
 

@@ -661,3 +661,52 @@ extern "C" int gh_online_tail(gh_ctx* ctx, gh_online* on, int64_t n, const int64
                               const int32_t* row_label, int32_t* labels, const int64_t* label_off, int32_t* n_labels) {
     return gh_online_tail_timed(ctx, on, n, ids, end_cost, best_end, row_label, labels, label_off, n_labels, nullptr);
 }
+
+// The forced commit: prunes, in the carried column of the named streams, the live cells whose trace does not pass the cell in
+// which the chosen end's trace arrives in column T - 1 - max_tail (gh_online_force.hip).  The anchors do not move here: the
+// gh_online_commit called next finds them.  Everything is checked before anything is enqueued.
+extern "C" int gh_online_force(gh_ctx* ctx, gh_online* on, int64_t n, const int64_t* ids, int64_t max_tail, int32_t* pruned) {
+    GH_REQUIRE(ctx && on, "gh_online_force: NULL argument");
+    GH_REQUIRE(ctx == on->ctx, "gh_online_force: the session belongs to another context");
+    GH_REQUIRE(max_tail >= 1, "gh_online_force: max_tail=%lld (at least one frame stays unsettled)", (long long)max_tail);
+    std::vector<gh_settle_task> tasks;
+    int rc = tasks_of(on, "gh_online_force", n, ids, true, tasks);
+    if (rc) return rc;
+    const gh_online_form& fm = *on->form;
+    const char* why = nullptr;
+    if (fm.sets == 2) why = "a session on a K-layer word lattice does not settle, and a forced commit for it is not built yet";
+    else if (fm.lanes == 64 && fm.bigram_rows) why = "the forced commit of a wide bigram session (17 to 64 words) is not built yet";
+    else if (fm.lanes == 64) why = "the forced commit of a wide session (17 to 64 words) is not built yet";
+    else if (fm.bigram_rows) why = "the forced commit of a bigram session is not built yet (its records need their own marking)";
+    if (why) {
+        gh_set_error("gh_online_force: %s; the narrow loop session (gh_online_create, gh_online_create_window) has it", why);
+        return GH_ERR_UNSUPPORTED;
+    }
+    rc = refuse_unsettled(on, "gh_online_force");
+    if (rc) return rc;
+    if (n <= 0) return GH_OK;
+    GH_REQUIRE(pruned, "gh_online_force: pruned is NULL");
+    GH_HIP(hipSetDevice(ctx->device));
+    int* d_flag;
+    gh_settle_task* d_tasks;
+    int32_t* d_pruned;
+    Carver cv;
+    cv.add(&d_flag, 64); cv.add(&d_tasks, (size_t)n); cv.add(&d_pruned, (size_t)n);
+    rc = cv.commit(ctx);
+    if (rc) return rc;
+    hipStream_t st = ctx->stream;
+    GH_HIP(hipMemsetAsync(d_flag, 0, sizeof(int), st));
+    GH_HIP(hipMemcpyAsync(d_tasks, tasks.data(), (size_t)n * sizeof(gh_settle_task), hipMemcpyHostToDevice, st));
+    gh_force_args a;
+    memset(&a, 0, sizeof a);
+    a.lf = on->lat->d_layers; a.end_slot = on->lat->d_lf_end_slot; a.tasks = d_tasks; a.n = n; a.prev = on->d_prev; a.hist = on->d_hist;
+    a.hist_stride = on->hist_stride; a.ring_words = on->ring_words; a.max_tail = (int)std::min<int64_t>(max_tail, 0x7fffffff);
+    a.anchor = on->d_anchor; a.pruned = d_pruned; a.flag = d_flag;
+    rc = gh_launch_online_loop_force(ctx, on, a);
+    if (rc) return rc;
+    int flag = 0;
+    GH_HIP(hipMemcpyAsync(&flag, d_flag, sizeof(int), hipMemcpyDeviceToHost, st));
+    GH_HIP(hipMemcpyAsync(pruned, d_pruned, (size_t)n * 4, hipMemcpyDeviceToHost, st));
+    GH_HIP(hipStreamSynchronize(st));
+    return flag_error("gh_online_force", flag, "the trace of the chosen end reached a cell without predecessor");
+}

@@ -185,6 +185,7 @@ SIGNATURES = {
     "gh_online_create_layers": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.POINTER(C.c_void_p)]),
     "gh_online_commit": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, _c_i64p, _c_i64p, _c_i32p, _c_i32p, _c_i64p, _c_i32p]),
     "gh_online_commit_timed": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, _c_i64p, _c_i64p, _c_i32p, _c_i32p, _c_i64p, _c_i32p, _c_i32p]),
+    "gh_online_force": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, _c_i64p, C.c_int64, _c_i32p]),
     "gh_online_tail": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, _c_i64p, _c_f64p, _c_i32p, _c_i32p, _c_i32p, _c_i64p, _c_i32p]),
     "gh_online_tail_timed": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, _c_i64p, _c_f64p, _c_i32p, _c_i32p, _c_i32p, _c_i64p, _c_i32p, _c_i32p]),
     "gh_wordstream_create": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_void_p)]),
@@ -1594,6 +1595,21 @@ class OnlineSession:
         if begins is not None:
             out["begins"] = [begins[label_off[i]:label_off[i] + n_labels[i]] for i in range(n)]
         return out
+
+    def force(self, ids=None, max_tail=1):
+        """The forced commit of the streams `ids` (None: all; distinct), gh_online_force: where a stream holds more than
+        `max_tail` frames behind its anchor, the live cells of its newest column whose trace does not pass the chosen end's
+        cell in column frames - 1 - max_tail are set to +inf, so that the `commit` called next settles up to that column
+        at least.  Returns pruned [n] int32, the number of cells removed (0: nothing had to be done).  A bigram, wide or
+        layer session raises `Unsupported`."""
+        lib = self.ctx.lib
+        ids = np.arange(self.n_streams, dtype=np.int64) if ids is None else self._i64(ids)
+        pruned = np.zeros(len(ids), dtype=np.int32)
+        rc = lib.gh_online_force(self.ctx.h, self.h, len(ids), _ptr(ids, _c_i64p), int(max_tail), _ptr(pruned, _c_i32p))
+        if rc == GH_ERR_UNSUPPORTED:
+            raise Unsupported(lib.gh_last_error().decode("utf-8", "replace"))
+        _check(lib, rc)
+        return pruned
 
     def tail(self, ids=None, row_label=None, max_labels=None, want_begin=False):
         """dict(end_cost [n, n_end], best_end [n], frames [n][, labels: the labels behind the anchor, list of int32 arrays])

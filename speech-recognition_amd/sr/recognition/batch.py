@@ -429,7 +429,8 @@ class ContinuousDecoder:
         """Decode `xs` and tally against the label strings like main.py:54-84 -- see `sequence_report`."""
         return sequence_report(self.decode(xs), labels, verbose=verbose)
 
-    def online(self, n_streams, max_frames=None, window=None, frontend=None, endpointer=None, times=False, settle=False):
+    def online(self, n_streams, max_frames=None, window=None, frontend=None, endpointer=None, times=False, settle=False,
+               max_tail=None):
         """An `OnlineDecoder` of `n_streams` live utterances sharing this decoder's packed mixtures and graph
         (grammar="loop" only: anything else raises `_hip.Unsupported`).  Exactly one of `max_frames` (utterances of up to
         that many frames, whole history kept) and `window` (utterances of any length, history for that many unsettled
@@ -440,8 +441,10 @@ class ContinuousDecoder:
         decoder also keeps and reports the frame every word begins in (see `OnlineDecoder`).  A decoder of more than 16
         words (up to 64, of 2..8 states) by default takes `max_frames` only, keeps its full history and does not settle;
         `settle=True` gives it the settled prefix (`commit`, `settled`, `settled_times`) with `max_frames=` and lets it
-        take `window=`.  A decoder of up to 16 words always settles and ignores `settle`."""
-        return OnlineDecoder(self, n_streams, max_frames, window, frontend, endpointer, times, settle)
+        take `window=`.  A decoder of up to 16 words always settles and ignores `settle`.  max_tail=M (a decoder of up to
+        16 words; 1 <= M < window) makes `commit` a FORCED commit: afterwards a stream holds at most M unsettled frames,
+        whether its traces met or not (see `OnlineDecoder`); with None nothing changes anywhere."""
+        return OnlineDecoder(self, n_streams, max_frames, window, frontend, endpointer, times, settle, max_tail)
 
 
     def online_bigram(self, n_streams, max_frames=None, window=None, frontend=None, endpointer=None, times=False, settle=False,
@@ -653,8 +656,23 @@ class OnlineDecoder(_OnlineStreams):
 
     With `window=` instead of `max_frames=` a stream may run for any length: the history is a ring that holds the frames
     behind the settled prefix, and a push that would take a stream's unsettled frames (frames - settled_frames) past the
-    window raises ValueError like one past `max_frames`.  There is NO forced commit: a stream whose traces have not met
-    within the window cannot take more frames and can only be finished.  A windowed decoder offers no paths.
+    window raises ValueError like one past `max_frames`.  By default a commit forces nothing: a stream whose traces have
+    not met within the window cannot take more frames and can only be finished (`max_tail=`, below, bounds the tail).  A
+    windowed decoder offers no paths.
+
+    THE FORCED COMMIT.  `online(..., max_tail=M)` (a decoder of up to 16 words, 1 <= M < window) bounds the unsettled tail:
+
+        on = dec.online(n_streams=64, window=400, max_tail=300)
+        on.push(ids, chunks); new_words = on.commit(ids)      # afterwards frames - settled_frames <= 300, always
+
+    `commit` then runs the natural commit as ever; a stream that still holds more than M unsettled frames is FORCED
+    (gh_online_force): the cell A in which the trace of its chosen end arrives in column frames - 1 - M is found, every
+    live cell of the newest column whose trace does not pass A is removed (+inf), and a second commit settles up to A at
+    least.  The words of both commits come back in order, in the usual shape.  The chosen end survives, so `result` gives
+    the same words before and after, and the settled words stay a prefix of every later `result`; but from its first
+    forced tick on a stream is the carried decode with those cells removed, no longer the one-shot decode of its prefix.
+    `n_forced` counts per stream the commits that removed something (`reset` / `finish` clear it).  GUARANTEE: with a
+    `commit` after every push of at most window - M frames, no push is ever refused for the window.
 
     AUDIO.  With a `sr.feature.StreamingFrontend` the streams take int16 PCM instead of feature frames:
 
@@ -711,7 +729,10 @@ class OnlineDecoder(_OnlineStreams):
     wide = False                                          # more than 16 words: the wide session
     settles = True                                        # ... which settles only where `settle=True` asked for it
 
-    def __init__(self, decoder, n_streams, max_frames=None, window=None, frontend=None, endpointer=None, times=False, settle=False):
+    max_tail = None                                       # the bound of the forced commit (None: commits force nothing)
+
+    def __init__(self, decoder, n_streams, max_frames=None, window=None, frontend=None, endpointer=None, times=False, settle=False,
+                 max_tail=None):
         if decoder.grammar != "loop":
             raise _hip.Unsupported("online decoding takes the word-loop grammar (grammar='loop'), not %r%s"
                                    % (decoder.grammar, " (online_bigram takes it)" if decoder.grammar == "bigram" else
@@ -724,6 +745,14 @@ class OnlineDecoder(_OnlineStreams):
         # settle=True asks for it
         self.wide = int(np.max(decoder.row_state)) // int(decoder.n) + 1 > 16
         self.settles = not self.wide or bool(settle)
+        if max_tail is not None:
+            if int(max_tail) < 1:
+                raise ValueError("max_tail must be at least 1 (the newest column never settles), not %r" % (max_tail,))
+            if window is not None and int(max_tail) >= int(window):
+                raise ValueError("max_tail=%d must be smaller than window=%d: a push needs room" % (int(max_tail), int(window)))
+            if self.wide:
+                raise _hip.Unsupported("the forced commit (max_tail=) of a decoder with more than 16 words is not built yet")
+            self.max_tail = int(max_tail)
         if not self.settles and window is not None:
             raise _hip.Unsupported("a decoder with more than 16 words keeps its full history: online(..., max_frames=), not window= "
                                    "(online(..., window=, settle=True) makes one that settles)")
@@ -748,6 +777,7 @@ class OnlineDecoder(_OnlineStreams):
         self._words = [[] for _ in range(self.n_streams)]             # ... and its settled words
         self.times = bool(times)
         self._begins = [[] for _ in range(self.n_streams)]            # times=True: the begin frames of the settled words
+        self.n_forced = np.zeros(self.n_streams, dtype=np.int64)      # max_tail=: commits of a stream that pruned something
         self._row_word = np.where(decoder.row_state >= 0, decoder.row_state // decoder.n, -1).astype(np.int32)
 
     def _room(self, ids, counts):
@@ -793,12 +823,30 @@ class OnlineDecoder(_OnlineStreams):
         """Settles what can no longer change of the streams `ids` (None: all; distinct): the list of the words that became
         final with THIS call, per stream.  Nothing is settled while a stream has fewer than two frames or no live cell, or
         while its traces do not meet.  want_times=True (a decoder with times=True): (new_words, new_begins), the begin
-        frame of every newly settled word beside it."""
+        frame of every newly settled word beside it.  With `max_tail=` the streams that still hold more than that many
+        unsettled frames are forced and committed again; what both commits settled comes back in order."""
         if not self.settles:
             self._refuse_wide()
         if want_times and not self.times:
             raise ValueError("this decoder keeps no word times: online(..., times=True)")
         ids = np.arange(self.n_streams, dtype=np.int64) if ids is None else self._ids(ids)
+        new, new_begins = self._commit(ids)
+        if self.max_tail is not None:
+            over = np.flatnonzero(self._frames[ids] - self._settled[ids] > self.max_tail)
+            if len(over):
+                pruned = self.session.force(ids[over], self.max_tail)
+                self.n_forced[ids[over]] += np.asarray(pruned) > 0
+                more, more_begins = self._commit(ids[over])
+                for k, i in enumerate(over):
+                    new[i] = new[i] + more[k]
+                    if self.times:
+                        new_begins[i] = new_begins[i] + more_begins[k]
+        if not self.times:
+            return new
+        return (new, new_begins) if want_times else new
+
+    def _commit(self, ids):
+        """One commit of the session: (new words, new begins -- None without times) per stream, book-keeping done."""
         tm = dict(want_begin=True) if self.times else {}
         # (room for a word per unsettled frame: with skip arcs a word can pass in fewer than n - 1 column steps)
         r = self.session.commit(ids, row_label=self._row_word, max_labels=self._frames[ids] - self._settled[ids] + 2, **tm)
@@ -807,11 +855,11 @@ class OnlineDecoder(_OnlineStreams):
             self._settled[k] = s
             self._words[k] = self._words[k] + ws
         if not self.times:
-            return new
+            return new, None
         new_begins = [[int(b) for b in bl] for bl in r["begins"]]
         for k, bs in zip(ids, new_begins):
             self._begins[k] = self._begins[k] + bs
-        return (new, new_begins) if want_times else new
+        return new, new_begins
 
     def settled(self, ids=None):
         """(all settled words so far, settled_frames [n]) of the streams `ids` (None: all): stream k's first
@@ -859,8 +907,10 @@ class OnlineDecoder(_OnlineStreams):
         super()._reset_utterance(ids)                     # ... and nothing is settled
         if ids is None:
             self._settled[:] = 0
+            self.n_forced[:] = 0
         else:
             self._settled[ids] = 0
+            self.n_forced[ids] = 0
         for k in (range(self.n_streams) if ids is None else ids):
             self._words[int(k)] = []
             self._begins[int(k)] = []
