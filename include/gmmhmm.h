@@ -934,7 +934,8 @@ int gh_wordstream_result(gh_ctx* ctx, gh_wordstream* ws, int64_t n, const int64_
  * NORMALISATION: per-utterance standardize is not causal; a front-end created with mean / std [39] applies the fixed map
  * "round the raw value to the batch dtype, evaluate (x - mean) / std in fp64, round to the dtype" (NULL, NULL: raw
  * features).  gh_batch_affine is that map in place on any resident batch (mean / std [D]; likelihoods the batch holds
- * are forgotten), e.g. on a mode-1 batch of whole utterances for training.
+ * are forgotten), e.g. on a mode-1 batch of whole utterances for training.  The causal alternative that adapts to the
+ * stream, gh_stream_create_running, is declared below.
  * gh_stream_push: stream ids[u] takes samples [sample_off[u], sample_off[u+1]) of `samples` (any length from 0 to
  * max_chunk_samples); end[u] != 0 (end may be NULL) ends its utterance with this chunk.  *out is a resident batch of n
  * utterances in the order of ids with ragged frame counts, 0 allowed.  Everything is checked before anything is enqueued
@@ -956,6 +957,33 @@ int gh_stream_phase_ms(const gh_stream* fe, double* out /*[4]*/);
 int gh_stream_push(gh_ctx* ctx, gh_stream* fe, int64_t n, const int64_t* ids /*[n], distinct*/, const int16_t* samples,
                    const int64_t* sample_off /*[n+1]*/, const uint8_t* end /*[n] or NULL*/, gh_batch** out);
 int gh_batch_affine(gh_ctx* ctx, gh_batch* b, const double* mean /*[D]*/, const double* std_ /*[D]*/);
+
+/* ------------------------------------------------ causal running mean / variance normalisation
+ * In place of the fixed map: start at a prior (mean, std) worth prior_frames frames and move to the stream's own
+ * statistics as frames arrive.  Per stream (offline: per utterance) and coefficient k two fp64 sums S, Q and the count c
+ * of the frames they hold, all 0 at the start; per frame, in frame order, on the raw value rounded to the batch dtype:
+ *     d = r - mean ;  S += d ;  Q += d d ;  c += 1 ;  n = prior_frames + c ;  a = S / n
+ *     v = (prior_frames std std + Q) / n - a a ;  y = (d - a) / sqrt(max(v, (min_std std)^2)), rounded to the dtype
+ * every operation one correctly rounded fp64 operation in the order written, so a stream's output is a function of its
+ * frames alone, however the audio was cut, and bitwise gh_batch_running_norm of its utterance's mode-1 batch.
+ * gh_stream_create_running: gh_stream_create with that rule.  Refused before anything is allocated: a non-finite value,
+ * std <= 0, prior_frames < 0 or not whole, min_std outside (0, 1].  S and Q live on the device ([n_streams][2][39] fp64),
+ * c on the host; a stream with c = 0 reads no carried state.  keep_across_resets = 0: gh_stream_reset also zeroes c, every
+ * utterance is normalised alone; 1: gh_stream_reset leaves the statistics alone (successive utterances of one microphone
+ * keep adapting) and only gh_stream_reset_stats clears them.  gh_stream_push checks everything before anything is
+ * enqueued, as ever: c advances only where the samples advance.  The pass is counted in the "stack" phase.
+ * gh_stream_reset_stats: zeroes c of streams ids[0..n) (NULL: all); nothing happens on the device.  On a front-end
+ * without the rule there is nothing to clear.  gh_stream_norm_frames: the counts c (zeros without the rule).
+ * gh_batch_running_norm: the rule in place on every utterance of any resident batch, each alone (mean / std [D], any D);
+ * likelihoods the batch holds are forgotten, as by gh_batch_affine. */
+int gh_stream_create_running(gh_ctx* ctx, int64_t n_streams, int sample_rate, double frame_size, double frame_stride,
+                             double low_freq, double high_freq, int64_t max_chunk_samples, gh_dtype dtype,
+                             const double* mean /*[39]*/, const double* std_ /*[39]*/, double prior_frames, double min_std,
+                             int keep_across_resets, gh_stream** out);
+int gh_stream_reset_stats(gh_stream* fe, int64_t n, const int64_t* ids /*[n] or NULL*/);
+int gh_stream_norm_frames(const gh_stream* fe, int64_t* out /*[n_streams]*/);
+int gh_batch_running_norm(gh_ctx* ctx, gh_batch* b, const double* mean /*[D]*/, const double* std_ /*[D]*/, double prior_frames,
+                          double min_std);
 
 /* ------------------------------------------------ streaming endpoint detection: audio chunks in, start / end events out
  * gh_endpoints for n_streams live recordings whose int16 audio arrives in pieces of any size: the reference's

@@ -28,7 +28,9 @@ EXTRA = {"gh_loglik_mfma.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"],
          # no contraction at all: the endpoint classifier rounds every product and sum like the reference's numpy scalars
          "gh_endpoint.hip": ["-ffp-contract=off"],
          # ... and the streaming detector rounds like the one-shot one
-         "gh_endpoint_stream.hip": ["-ffp-contract=off"]}
+         "gh_endpoint_stream.hip": ["-ffp-contract=off"],
+         # the running normalisation is defined operation by operation: numpy scalars round the same
+         "gh_norm_running.hip": ["-ffp-contract=off"]}
 
 
 def _sources():

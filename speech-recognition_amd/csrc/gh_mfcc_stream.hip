@@ -11,11 +11,15 @@
 //     A stream at sample 0 reads no carry: a reset touches nothing on the device.
 // Normalisation is a FIXED affine map (per-utterance `standardize` is not causal): the raw value is rounded to the batch
 // dtype, (x - mean) / std is evaluated in fp64 on that and rounded to the dtype; gh_batch_affine is the same map on any
-// resident batch.
+// resident batch.  A front-end made by gh_stream_create_running applies the causal running mean / variance normalisation
+// instead (gh_norm_running.hip): the stack kernel writes the raw rows, as it does without a map, and the
+// running pass follows it in place; per stream it carries two fp64 sums per coefficient on the device (624 B) and the
+// count of the frames they hold on the host.  A stream whose count is 0 reads no carried sums.
 // The kernel body from the FFT to the DCT, the tables and build_tables are gh_mfcc_core.h's, the ones gh_mfcc.hip uses, and
 // the delta rules are gh_delta.h's, the ones gh_frontend.hip uses: one text each, compiled here under the same flags.
 #include "gh_mfcc_core.h"
 #include "gh_delta.h"
+#include "gh_norm_running.h"
 #include <climits>
 
 namespace {
@@ -188,6 +192,10 @@ struct gh_stream {
     double *d_mean, *d_sd;         // [3 NCEPS] (unused without a map)
     int16_t* d_carry;              // [2][n_streams][cap]
     double* d_cc;                  // [n_streams][4][NCEPS]
+    bool running = false, keep = false;    // the running normalisation; whether its statistics survive gh_stream_reset
+    double prior_frames = 0.0;
+    double *d_prior = nullptr, *d_norm = nullptr;   // [3][3 NCEPS] constants of the rule; [n_streams][2][3 NCEPS] carried sums
+    std::vector<int64_t> norm_c;   // per stream: frames its carried sums hold (empty without the rule)
     std::vector<int64_t> samples;  // per stream: samples taken since its last reset
     std::vector<uint8_t> ended, rd;    // ... whether it has ended; which carry buffer holds its samples
     hipEvent_t ev[5] = {};         // gh_stream_profile: around upload, MFCC, stack, carry of a push
@@ -198,24 +206,29 @@ struct gh_stream {
     int64_t carry_base(int64_t n) const { return std::min(std::max<int64_t>(pairs_done(n) * fstep - 1, 0), n); }
 };
 
-extern "C" int gh_stream_create(gh_ctx* ctx, int64_t n_streams, int sample_rate, double frame_size, double frame_stride,
-                                double low_freq, double high_freq, int64_t max_chunk_samples, gh_dtype dtype,
-                                const double* mean, const double* std_, gh_stream** out) {
-    GH_REQUIRE(ctx && out, "gh_stream_create: NULL argument");
-    GH_REQUIRE(dtype == GH_F32 || dtype == GH_F64, "gh_stream_create: bad dtype %d", (int)dtype);
-    GH_REQUIRE(n_streams >= 1 && max_chunk_samples >= 1, "gh_stream_create: n_streams=%lld max_chunk_samples=%lld",
+// the rule of a front-end with the running normalisation (mean / std are then its prior)
+struct RunningRule { double prior_frames, min_std; bool keep; };
+
+static int stream_create(const char* who, gh_ctx* ctx, int64_t n_streams, int sample_rate, double frame_size, double frame_stride,
+                         double low_freq, double high_freq, int64_t max_chunk_samples, gh_dtype dtype, const double* mean,
+                         const double* std_, const RunningRule* run, gh_stream** out) {
+    GH_REQUIRE(ctx && out, "%s: NULL argument", who);
+    GH_REQUIRE(dtype == GH_F32 || dtype == GH_F64, "%s: bad dtype %d", who, (int)dtype);
+    GH_REQUIRE(n_streams >= 1 && max_chunk_samples >= 1, "%s: n_streams=%lld max_chunk_samples=%lld", who,
                (long long)n_streams, (long long)max_chunk_samples);
-    GH_REQUIRE((mean == nullptr) == (std_ == nullptr), "gh_stream_create: mean and std come together");
+    GH_REQUIRE((mean == nullptr) == (std_ == nullptr), "%s: mean and std come together", who);
     HostTables h;
     int rc = build_tables("gh_stream", sample_rate, frame_size, frame_stride, low_freq, high_freq, h);
     if (rc) return rc;
-    if (mean && (rc = check_affine("gh_stream_create", mean, std_, 3 * NCEPS))) return rc;
+    if (run) {
+        if ((rc = gh_norm_check(who, mean, std_, 3 * NCEPS, run->prior_frames, run->min_std))) return rc;
+    } else if (mean && (rc = check_affine(who, mean, std_, 3 * NCEPS))) return rc;
     GH_HIP(hipSetDevice(ctx->device));
     gh_stream* fe = new gh_stream();
     fe->ctx = ctx; fe->dtype = dtype; fe->n_streams = n_streams; fe->max_chunk = max_chunk_samples;
     fe->flen = h.flen; fe->fstep = h.fstep; fe->pad_left = h.pad_left;
     fe->cap = h.flen + 2 * h.fstep + 2;
-    fe->normalise = mean != nullptr;
+    fe->normalise = mean != nullptr && !run;
     fe->samples.assign((size_t)n_streams, 0);
     fe->ended.assign((size_t)n_streams, 0);
     fe->rd.assign((size_t)n_streams, 0);
@@ -230,11 +243,33 @@ extern "C" int gh_stream_create(gh_ctx* ctx, int64_t n_streams, int sample_rate,
     ar.add(&d_seg, h.seg); ar.add(&d_dct, h.dct);
     ar.add(&fe->d_mean, vm); ar.add(&fe->d_sd, vs);
     ar.add(&fe->d_carry, carry); ar.add(&fe->d_cc, cc);
+    if (run) {
+        fe->running = true; fe->keep = run->keep; fe->prior_frames = run->prior_frames;
+        fe->norm_c.assign((size_t)n_streams, 0);
+        ar.add(&fe->d_prior, gh_norm_prior(mean, std_, 3 * NCEPS, run->prior_frames, run->min_std));
+        ar.add(&fe->d_norm, std::vector<double>((size_t)n_streams * 2 * 3 * NCEPS, 0.0));
+    }
     rc = ar.commit(&fe->d_arena);
     if (rc) { if (fe->d_arena) (void)hipFree(fe->d_arena); delete fe; return rc; }
     fe->t.window = d_window; fe->t.tw = d_tw; fe->t.wup = d_wup; fe->t.wdn = d_wdn; fe->t.seg = d_seg; fe->t.dct = d_dct;
     *out = fe;
     return GH_OK;
+}
+
+extern "C" int gh_stream_create(gh_ctx* ctx, int64_t n_streams, int sample_rate, double frame_size, double frame_stride,
+                                double low_freq, double high_freq, int64_t max_chunk_samples, gh_dtype dtype,
+                                const double* mean, const double* std_, gh_stream** out) {
+    return stream_create("gh_stream_create", ctx, n_streams, sample_rate, frame_size, frame_stride, low_freq, high_freq,
+                         max_chunk_samples, dtype, mean, std_, nullptr, out);
+}
+
+extern "C" int gh_stream_create_running(gh_ctx* ctx, int64_t n_streams, int sample_rate, double frame_size, double frame_stride,
+                                        double low_freq, double high_freq, int64_t max_chunk_samples, gh_dtype dtype,
+                                        const double* mean, const double* std_, double prior_frames, double min_std,
+                                        int keep_across_resets, gh_stream** out) {
+    const RunningRule run{prior_frames, min_std, keep_across_resets != 0};
+    return stream_create("gh_stream_create_running", ctx, n_streams, sample_rate, frame_size, frame_stride, low_freq, high_freq,
+                         max_chunk_samples, dtype, mean, std_, &run, out);
 }
 
 extern "C" void gh_stream_destroy(gh_stream* fe) {
@@ -262,14 +297,36 @@ extern "C" int gh_stream_phase_ms(const gh_stream* fe, double* out) {
 
 extern "C" int gh_stream_reset(gh_stream* fe, int64_t n, const int64_t* ids) {
     GH_REQUIRE(fe && n >= 0, "gh_stream_reset: NULL argument");
+    const bool stats = fe->running && !fe->keep;           // every utterance is normalised alone
     if (!ids) {
         std::fill(fe->samples.begin(), fe->samples.end(), 0);
         std::fill(fe->ended.begin(), fe->ended.end(), 0);
+        if (stats) std::fill(fe->norm_c.begin(), fe->norm_c.end(), 0);
         return GH_OK;
     }
     for (int64_t i = 0; i < n; ++i)
         GH_REQUIRE(ids[i] >= 0 && ids[i] < fe->n_streams, "gh_stream_reset: stream %lld of %lld", (long long)ids[i], (long long)fe->n_streams);
-    for (int64_t i = 0; i < n; ++i) { fe->samples[(size_t)ids[i]] = 0; fe->ended[(size_t)ids[i]] = 0; }
+    for (int64_t i = 0; i < n; ++i) {
+        fe->samples[(size_t)ids[i]] = 0; fe->ended[(size_t)ids[i]] = 0;
+        if (stats) fe->norm_c[(size_t)ids[i]] = 0;
+    }
+    return GH_OK;
+}
+
+extern "C" int gh_stream_reset_stats(gh_stream* fe, int64_t n, const int64_t* ids) {
+    GH_REQUIRE(fe && n >= 0, "gh_stream_reset_stats: NULL argument");
+    for (int64_t i = 0; ids && i < n; ++i)
+        GH_REQUIRE(ids[i] >= 0 && ids[i] < fe->n_streams, "gh_stream_reset_stats: stream %lld of %lld", (long long)ids[i], (long long)fe->n_streams);
+    if (!fe->running) return GH_OK;                        // nothing to clear
+    if (!ids) std::fill(fe->norm_c.begin(), fe->norm_c.end(), 0);
+    else for (int64_t i = 0; i < n; ++i) fe->norm_c[(size_t)ids[i]] = 0;
+    return GH_OK;
+}
+
+extern "C" int gh_stream_norm_frames(const gh_stream* fe, int64_t* out) {
+    GH_REQUIRE(fe && out, "gh_stream_norm_frames: NULL argument");
+    if (fe->running) memcpy(out, fe->norm_c.data(), (size_t)fe->n_streams * 8);
+    else memset(out, 0, (size_t)fe->n_streams * 8);
     return GH_OK;
 }
 
@@ -292,6 +349,7 @@ extern "C" int gh_stream_push(gh_ctx* ctx, gh_stream* fe, int64_t n, const int64
     std::vector<StreamSlot> slot((size_t)n);
     std::vector<int64_t> f_off((size_t)n + 1, 0);
     std::vector<int32_t> pair_slot;
+    std::vector<NormSlot> nslot(fe->running ? (size_t)n : 0);
     int64_t n_ceps = 0;
     for (int64_t u = 0; u < n; ++u) {
         const int64_t id = ids[u], len = sample_off[u + 1] - sample_off[u];
@@ -326,6 +384,7 @@ extern "C" int gh_stream_push(gh_ctx* ctx, gh_stream* fe, int64_t n, const int64
                    "%s: internal: stream %lld would carry %lld samples, room for %d", who, (long long)id, (long long)(s.n_after - s.cnew), fe->cap);
         s.out_off = f_off[(size_t)u];
         f_off[(size_t)u + 1] = s.out_off + (s.f_end - s.f_first);
+        if (fe->running) nslot[(size_t)u] = NormSlot{s.out_off, s.f_end - s.f_first, fe->norm_c[(size_t)id], id};
         s.ceps_off = n_ceps;
         n_ceps += s.c_end - s.c_first;
         s.pair_off = (int64_t)pair_slot.size();
@@ -347,11 +406,13 @@ extern "C" int gh_stream_push(gh_ctx* ctx, gh_stream* fe, int64_t n, const int64
         StreamSlot* d_slot;
         int32_t* d_pair;
         double* d_ceps;
+        NormSlot* d_nslot = nullptr;
         Carver cv;
         cv.add(&d_chunk, (size_t)total + 1);
         cv.add(&d_slot, (size_t)n);
         cv.add(&d_pair, (size_t)n_pairs + 1);
         cv.add(&d_ceps, (size_t)(n_ceps + 1) * NCEPS);
+        if (fe->running) cv.add(&d_nslot, (size_t)n);
         if ((rc = cv.commit(ctx))) { gh_batch_destroy(b); return rc; }
         hipStream_t st = ctx->stream;
         hipError_t e = hipSuccess;
@@ -361,6 +422,7 @@ extern "C" int gh_stream_push(gh_ctx* ctx, gh_stream* fe, int64_t n, const int64
         if (total && e == hipSuccess) e = hipMemcpyAsync(d_chunk, samples, (size_t)total * 2, hipMemcpyHostToDevice, st);
         if (e == hipSuccess) e = hipMemcpyAsync(d_slot, slot.data(), (size_t)n * sizeof(StreamSlot), hipMemcpyHostToDevice, st);
         if (e == hipSuccess && n_pairs) e = hipMemcpyAsync(d_pair, pair_slot.data(), (size_t)n_pairs * 4, hipMemcpyHostToDevice, st);
+        if (e == hipSuccess && fe->running) e = hipMemcpyAsync(d_nslot, nslot.data(), (size_t)n * sizeof(NormSlot), hipMemcpyHostToDevice, st);
         tick();
         if (e == hipSuccess && n_pairs) {
             StreamMfccArgs a;
@@ -379,6 +441,9 @@ extern "C" int gh_stream_push(gh_ctx* ctx, gh_stream* fe, int64_t n, const int64
             else
                 hipLaunchKernelGGL((stream_stack_kernel<float>), dim3((unsigned)n), dim3(256), 0, st, d_slot, d_ceps, fe->d_cc, m, fe->d_sd, (float*)feats);
             e = hipGetLastError();
+            // the running normalisation, in place on the raw rows (counted in this phase)
+            if (e == hipSuccess && fe->running)
+                e = gh_norm_launch(st, fe->dtype, feats, 3 * NCEPS, d_nslot, n, fe->d_prior, fe->prior_frames, fe->d_norm);
         }
         tick();
         if (e == hipSuccess) {
@@ -403,6 +468,7 @@ extern "C" int gh_stream_push(gh_ctx* ctx, gh_stream* fe, int64_t n, const int64
         const size_t id = (size_t)ids[u];
         fe->samples[id] = slot[(size_t)u].n_after;
         fe->rd[id] ^= 1;
+        if (fe->running) fe->norm_c[id] += nslot[(size_t)u].nf;
         if (end && end[u]) fe->ended[id] = 1;
     }
     *out = b;

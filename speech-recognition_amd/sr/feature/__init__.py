@@ -7,13 +7,14 @@
 batch (what `load_wav_as_mfcc`, sr/core.py:25-44, returns -- for many utterances, without a host round trip).
 `StreamingFrontend` is the same front-end for audio that is still arriving: int16 chunks in, the frames that became final
 out, with a FIXED normalisation `(mean, std)` in place of the per-utterance one (`feature_stats` computes a pair,
-`features_from_signals(..., normalize=)` applies it to whole utterances)."""
+`features_from_signals(..., normalize=)` applies it to whole utterances) or a `RunningNorm`: the causal running mean /
+variance normalisation that starts at such a pair and moves to the stream's own statistics."""
 import numpy as np
 
 from ..recognition import _hip
 
 __all__ = ["standardize", "mfcc_features", "mfcc_from_signals", "features_from_signals", "feature_stats", "frames_ready",
-           "StreamingFrontend"]
+           "StreamingFrontend", "RunningNorm"]
 
 
 def standardize(data):
@@ -57,6 +58,37 @@ def _normalize_pair(normalize):
     return mean, std
 
 
+class RunningNorm:
+    """The causal running mean / variance normalisation as a `normalize=` value: the statistics start at
+    `prior` = (mean [39], std [39]) (e.g. `feature_stats` of training audio), which counts as `prior_frames` frames, and
+    move to the stream's own as frames arrive; the deviation never falls below `min_std` times the prior's.  Per frame,
+    in fp64 on the raw value rounded to the batch dtype: d = r - mean, S += d, Q += d d, n = prior_frames + c, a = S / n,
+    v = (prior_frames std^2 + Q) / n - a^2, y = (d - a) / sqrt(max(v, (min_std std)^2)).  prior_frames -> infinity gives
+    the fixed map (r - mean) / std; with prior_frames = 0 the last frame of an utterance is the last row of `standardize`.
+    per = "utterance": a `StreamingFrontend`'s `reset` clears a stream's statistics, every utterance is normalised alone
+    (what `features_from_signals` computes for training); per = "stream": they survive `reset` -- successive utterances of
+    one microphone keep adapting -- until `reset_stats` (an online decoder's `reset` calls it: a new recording)."""
+
+    def __init__(self, prior, prior_frames=100, min_std=0.1, per="utterance"):
+        try:
+            mean, std = (np.asarray(a, dtype=np.float64).reshape(-1) for a in prior)
+        except (TypeError, ValueError):
+            raise ValueError("prior = (mean [39], std [39])")
+        if len(mean) != 39 or len(std) != 39 or not (np.all(np.isfinite(mean)) and np.all(np.isfinite(std)) and np.all(std > 0)):
+            raise ValueError("prior = (mean [39], std [39]), finite, std > 0")
+        try:
+            pf, ms = float(prior_frames), float(min_std)
+        except (TypeError, ValueError):
+            raise ValueError("prior_frames and min_std are numbers")
+        if not (np.isfinite(pf) and pf >= 0 and pf == np.floor(pf) and pf <= 2.0 ** 52):
+            raise ValueError("prior_frames = %r: a whole number >= 0" % (prior_frames,))
+        if not (np.isfinite(ms) and 0 < ms <= 1):
+            raise ValueError("min_std = %r: 0 < min_std <= 1" % (min_std,))
+        if per not in ("utterance", "stream"):
+            raise ValueError("per = %r: 'utterance' or 'stream'" % (per,))
+        self.prior, self.prior_frames, self.min_std, self.per = (mean, std), pf, ms, per
+
+
 def features_from_signals(signals, sample_rate=16000, dtype=np.float64, device=None, endpoints=None, max_segments=1, normalize=None,
                           **mfcc_kw):
     """Audio in, resident 39-dimensional batch out: MFCC -> [ceps | delta | delta-delta] -> standardize,
@@ -66,6 +98,9 @@ def features_from_signals(signals, sample_rate=16000, dtype=np.float64, device=N
     `standardize` -- the raw stacked features (rounded to `dtype`) go through `Batch.affine`: for an utterance alone in its
     batch bitwise what a stream with the same pair emits (in a batch of several, an utterance behind an odd number of frames
     shares its FFTs with other partners: equal to rounding).  `feature_stats` computes such a pair from training audio.
+    normalize=RunningNorm(...): the causal running normalisation instead, through `Batch.running_norm` on the same raw
+    batch, every utterance alone from zero statistics (`per` plays no part here) -- the features to train the models of
+    a `StreamingFrontend(normalize=RunningNorm(...))` with, and bitwise what such a stream emits for the utterance.
 
     endpoints: an AudioRecorder config (sr.audio_capture; True: the reference's default config at `sample_rate`) -- the
     1-D int16 recordings are first cut down to their speech on the device (`detect_endpoints`, up to `max_segments`
@@ -76,12 +111,18 @@ def features_from_signals(signals, sample_rate=16000, dtype=np.float64, device=N
     prm = (mfcc_kw.get("frame_size", 0.025), mfcc_kw.get("frame_stride", 0.01), mfcc_kw.get("low_freq", 80),
            mfcc_kw.get("high_freq"))
     mode = {}
-    if normalize is not None:
-        normalize = _normalize_pair(normalize)
+    finish = lambda b: b
+    if isinstance(normalize, RunningNorm):
+        run = normalize
+        finish = lambda b: b.running_norm(run.prior[0], run.prior[1], run.prior_frames, run.min_std)
+        mode = dict(frontend_mode=1)
+    elif normalize is not None:
+        pair = _normalize_pair(normalize)
+        finish = lambda b: b.affine(*pair)
         mode = dict(frontend_mode=1)
     if endpoints is None or endpoints is False:
         b = _hip.Batch(_hip.default_context(device), pcm=signals, sample_rate=sample_rate, mfcc_params=prm, dtype=dtype, **mode)
-        return b if normalize is None else b.affine(*normalize)
+        return finish(b)
     from ..audio_capture.record import _check_signals, _derived      # (`sr.audio_capture.record` the name is the function)
     cfg = _derived(None if endpoints is True else endpoints, sample_rate)
     if cfg['sample rate'] != sample_rate:
@@ -91,7 +132,7 @@ def features_from_signals(signals, sample_rate=16000, dtype=np.float64, device=N
     sigs = _check_signals(signals)
     b = _hip.Batch(_hip.default_context(device), pcm=sigs, sample_rate=sample_rate, mfcc_params=prm, dtype=dtype,
                    endpoints=cfg, max_segments=int(max_segments), **mode)
-    return b if normalize is None else b.affine(*normalize)
+    return finish(b)
 
 
 def feature_stats(signals, sample_rate=16000, device=None, **mfcc_kw):
@@ -123,8 +164,10 @@ class StreamingFrontend:
     A stream's concatenated frames are bitwise `features_from_signals([signal], normalize=...)` of its utterance alone,
     however it was cut.  While a stream is open it has emitted `frames_ready(n)` frames after n samples (a frame is final
     when the cepstra of the two frames behind it exist, and those are computed in pairs); the end flushes the rest.
-    `normalize` is a FIXED `(mean [39], std [39])` or None for raw features: per-utterance `standardize` needs the whole
-    utterance.  Bad arguments -- an id twice or out of range, a chunk that is not 1-D int16 or longer than `max_chunk`
+    `normalize` is a FIXED `(mean [39], std [39])`, None for raw features, or a `RunningNorm`: per-utterance `standardize`
+    needs the whole utterance, the running normalisation is its causal stand-in (the front-end then has `reset_stats` and
+    `norm_frames`, and `features_from_signals(..., normalize=` the same `RunningNorm)` gives the matching training
+    features).  Bad arguments -- an id twice or out of range, a chunk that is not 1-D int16 or longer than `max_chunk`
     samples, audio for a stream that has ended, an end with fewer than 2 frames -- raise ValueError before the GPU is
     touched, and no stream moves."""
 
@@ -133,14 +176,21 @@ class StreamingFrontend:
             raise ValueError("n_streams and max_chunk must be positive")
         self.n_streams, self.sample_rate, self.max_chunk = int(n_streams), int(sample_rate), int(max_chunk)
         self.dtype = np.dtype(dtype)
-        self.normalize = None if normalize is None else _normalize_pair(normalize)
+        self.running = normalize if isinstance(normalize, RunningNorm) else None
+        self.normalize = None if normalize is None or self.running else _normalize_pair(normalize)
         self.mfcc_params = _mfcc_params(mfcc_kw)
         self.flen = int(float(self.mfcc_params[0]) * self.sample_rate)
         self.step = int(float(self.mfcc_params[1]) * self.sample_rate)
         self.D = 39
         self.ctx = _hip.default_context(device)
-        self.backend = _hip.StreamFrontend(self.ctx, self.n_streams, self.sample_rate, self.mfcc_params, self.max_chunk, self.dtype,
-                                           self.normalize)
+        if self.running is None:
+            self.backend = _hip.StreamFrontend(self.ctx, self.n_streams, self.sample_rate, self.mfcc_params, self.max_chunk, self.dtype,
+                                               self.normalize)
+        else:
+            self.backend = _hip.RunningStreamFrontend(self.ctx, self.n_streams, self.sample_rate, self.mfcc_params, self.max_chunk,
+                                                      self.dtype, self.running.prior, self.running.prior_frames, self.running.min_std,
+                                                      self.running.per == "stream")
+            self._norm_frames = np.zeros(self.n_streams, dtype=np.int64)  # what the backend's statistics hold
         self._samples = np.zeros(self.n_streams, dtype=np.int64)      # what the backend holds, for the checks below
         self._ended = np.zeros(self.n_streams, dtype=bool)
 
@@ -201,6 +251,8 @@ class StreamingFrontend:
         assert np.array_equal(batch.lengths, counts)
         self._samples[ids] = self._samples[ids] + np.diff(off)
         self._ended[ids] |= end
+        if self.running is not None:
+            self._norm_frames[ids] = self._norm_frames[ids] + counts
         return batch
 
     def reset(self, ids=None):
@@ -213,6 +265,22 @@ class StreamingFrontend:
         else:
             self._samples[ids] = 0
             self._ended[ids] = False
+        if self.running is not None and self.running.per == "utterance":
+            self._norm_frames[slice(None) if ids is None else ids] = 0
+
+    @property
+    def norm_frames(self):
+        """Frames the running statistics of every stream hold: int64 [n_streams] (zeros without a `RunningNorm`)."""
+        return self._norm_frames.copy() if self.running is not None else np.zeros(self.n_streams, dtype=np.int64)
+
+    def reset_stats(self, ids=None):
+        """The running statistics of streams `ids` (None: all) start again at the prior -- a new speaker or microphone on the
+        stream.  With per="utterance" `reset` has done that already; without a `RunningNorm` there is nothing to clear."""
+        ids = None if ids is None else self._ids(ids, distinct=False)
+        if self.running is None:
+            return
+        self.backend.reset_stats(ids)
+        self._norm_frames[slice(None) if ids is None else ids] = 0
 
     def close(self):
         self.backend.close()

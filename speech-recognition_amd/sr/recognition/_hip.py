@@ -203,6 +203,11 @@ SIGNATURES = {
     "gh_stream_phase_ms": (C.c_int, [C.c_void_p, _c_f64p]),
     "gh_stream_push": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, _c_i64p, C.c_void_p, _c_i64p, _c_u8p, C.POINTER(C.c_void_p)]),
     "gh_batch_affine": (C.c_int, [C.c_void_p, C.c_void_p, _c_f64p, _c_f64p]),
+    "gh_stream_create_running": (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_double, C.c_double, C.c_double, C.c_double, C.c_int64,
+                                           C.c_int, _c_f64p, _c_f64p, C.c_double, C.c_double, C.c_int, C.POINTER(C.c_void_p)]),
+    "gh_stream_reset_stats": (C.c_int, [C.c_void_p, C.c_int64, _c_i64p]),
+    "gh_stream_norm_frames": (C.c_int, [C.c_void_p, _c_i64p]),
+    "gh_batch_running_norm": (C.c_int, [C.c_void_p, C.c_void_p, _c_f64p, _c_f64p, C.c_double, C.c_double]),
     "gh_epstream_create": (C.c_int, [C.c_void_p, C.c_int64, C.POINTER(EndpointParams), C.c_int64, C.POINTER(C.c_void_p)]),
     "gh_epstream_destroy": (None, [C.c_void_p]),
     "gh_epstream_reset": (C.c_int, [C.c_void_p, C.c_int64, _c_i64p]),
@@ -929,6 +934,17 @@ class Batch:
         if len(mean) != self.D or len(std) != self.D:
             raise ValueError("mean and std must have %d entries" % self.D)
         _check(self.ctx.lib, self.ctx.lib.gh_batch_affine(self.ctx.h, self.h, _ptr(mean, _c_f64p), _ptr(std, _c_f64p)))
+        self.S = None
+        return self
+
+    def running_norm(self, mean, std, prior_frames=100, min_std=0.1):
+        """The causal running mean / variance normalisation in place, every utterance alone from zero statistics
+        (gh_batch_running_norm; the rule: DESIGN.md 4.23); mean / std [D].  Likelihoods the batch holds are forgotten."""
+        mean, std = _f64(mean).reshape(-1), _f64(std).reshape(-1)
+        if len(mean) != self.D or len(std) != self.D:
+            raise ValueError("mean and std must have %d entries" % self.D)
+        _check(self.ctx.lib, self.ctx.lib.gh_batch_running_norm(self.ctx.h, self.h, _ptr(mean, _c_f64p), _ptr(std, _c_f64p),
+                                                                float(prior_frames), float(min_std)))
         self.S = None
         return self
 
@@ -1848,15 +1864,17 @@ class StreamFrontend:
             if len(mean) != 39 or len(std) != 39:
                 raise ValueError("normalize = (mean [39], std [39])")
         h = C.c_void_p()
-        rc = ctx.lib.gh_stream_create(ctx.h, self.n_streams, int(sample_rate), float(fs), float(st), float(lo),
-                                      0.0 if hi is None else float(hi), int(max_chunk),
-                                      GH_F64 if self.np_dtype == np.float64 else GH_F32, _ptr(mean, _c_f64p), _ptr(std, _c_f64p),
-                                      C.byref(h))
+        rc = self._create(ctx, (ctx.h, self.n_streams, int(sample_rate), float(fs), float(st), float(lo),
+                                0.0 if hi is None else float(hi), int(max_chunk),
+                                GH_F64 if self.np_dtype == np.float64 else GH_F32, _ptr(mean, _c_f64p), _ptr(std, _c_f64p)), C.byref(h))
         if rc == GH_ERR_UNSUPPORTED:
             raise Unsupported(ctx.lib.gh_last_error().decode("utf-8", "replace"))
         _check(ctx.lib, rc)
         self.h = h
         self.flen, self.step = int(float(fs) * int(sample_rate)), int(float(st) * int(sample_rate))   # as build_tables truncates
+
+    def _create(self, ctx, args, out):
+        return ctx.lib.gh_stream_create(*args, out)
 
     def push(self, ids, samples, sample_off, end=None):
         """Stream ids[u] takes samples[sample_off[u]:sample_off[u + 1]] (int16); end [n] (uint8 / bool) ends utterances."""
@@ -1907,6 +1925,34 @@ class StreamFrontend:
             self.close()
         except Exception:
             pass
+
+
+class RunningStreamFrontend(StreamFrontend):
+    """`StreamFrontend` with the causal running mean / variance normalisation (gh_stream_create_running; the rule:
+    DESIGN.md 4.23): prior = (mean [39], std [39]) worth `prior_frames` frames, `min_std` the floor of the deviation as a
+    fraction of the prior's.  keep_across_resets False: `reset` also clears a stream's statistics (every utterance is
+    normalised alone); True: only `reset_stats` does."""
+
+    def __init__(self, ctx, n_streams, sample_rate=16000, mfcc_params=None, max_chunk=16000, dtype=np.float64, prior=None,
+                 prior_frames=100, min_std=0.1, keep_across_resets=False):
+        if prior is None:
+            raise ValueError("prior = (mean [39], std [39])")
+        self._rule = (float(prior_frames), float(min_std), 1 if keep_across_resets else 0)
+        StreamFrontend.__init__(self, ctx, n_streams, sample_rate, mfcc_params, max_chunk, dtype, prior)
+
+    def _create(self, ctx, args, out):
+        return ctx.lib.gh_stream_create_running(*args, *self._rule, out)
+
+    def reset_stats(self, ids=None):
+        """The statistics of streams `ids` (None: all) start again at the prior; nothing happens on the device."""
+        ids = None if ids is None else np.ascontiguousarray(ids, dtype=np.int64)
+        _check(self.ctx.lib, self.ctx.lib.gh_stream_reset_stats(self.h, 0 if ids is None else len(ids), _ptr(ids, _c_i64p)))
+
+    def norm_frames(self):
+        """Frames every stream's statistics hold: int64 [n_streams]."""
+        out = np.empty(self.n_streams, dtype=np.int64)
+        _check(self.ctx.lib, self.ctx.lib.gh_stream_norm_frames(self.h, _ptr(out, _c_i64p)))
+        return out
 
 
 def endpoint_event_room(new_frames, speech_frames, silence_frames):

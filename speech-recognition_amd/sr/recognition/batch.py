@@ -612,11 +612,13 @@ class _OnlineStreams:
 
     def reset(self, ids=None):
         """The streams `ids` (None: all) start again at frame 0 -- and, with an endpointer, at sample 0 of a new
-        recording."""
+        recording, where a front-end with running statistics (`RunningNorm`) starts them again at the prior."""
         ids = None if ids is None else self._ids(ids, distinct=False)
         if self.endpointer is not None:
             self.endpointer.reset(ids)
         self._reset_utterance(ids)
+        if getattr(self.frontend, "reset_stats", None) is not None:
+            self.frontend.reset_stats(ids)
 
     def _reset_utterance(self, ids):
         self.session.reset(ids)
