@@ -15,8 +15,9 @@ namespace {
 struct MfccArgs {
     const void* pcm; int fmt;
     const int64_t* s_beg; const int64_t* s_end;   // first sample of every utterance in `pcm`, one past its last
-    const int64_t* f_off; const int32_t* f_utt;
-    int64_t U, N;
+    const int64_t* f_off;                         // first frame of every utterance in the outputs
+    const int64_t* p_off; const int32_t* p_utt;   // first frame pair of every utterance; the utterance of every pair
+    int64_t U, P;
     int flen, fstep, pad_left;
     MfccTables t;
     double* out_fb; double* out_mfcc;
@@ -28,8 +29,10 @@ template <int FMT> __device__ __forceinline__ double sample_at(const void* pcm, 
     return static_cast<const double*>(pcm)[i];
 }
 
-// One wave per PAIR of frames (A, B), four pairs per workgroup: the samples of an utterance are addressed through the
-// host-built frame -> utterance table, windowed here, and mfcc_pair_tail does the rest.
+// One wave per PAIR of frames (A, B), four pairs per workgroup.  Frames are paired by their index INSIDE the utterance
+// (2m, 2m + 1), through the host-built pair -> utterance table, and an odd last frame gets a dead partner: a frame's bits
+// depend on its partner in the FFT, so an utterance comes out the same wherever it stands in the batch, alone, or streamed
+// (stream_mfcc_kernel pairs the same way).  The samples are windowed here, and mfcc_pair_tail does the rest.
 template <int FMT>
 __global__ __launch_bounds__(256) void mfcc_kernel(MfccArgs a) {
     constexpr int S1 = MFCC_S1;
@@ -40,18 +43,21 @@ __global__ __launch_bounds__(256) void mfcc_kernel(MfccArgs a) {
     for (int k = threadIdx.x; k < NBIN; k += 256) { s_wup[k] = a.t.wup[k]; s_wdn[k] = a.t.wdn[k]; }
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     double* ex = s_x[wv];
-    const int64_t n0 = ((int64_t)blockIdx.x * 4 + wv) * 2;   // frames n0 (A) and n0 + 1 (B)
-    int64_t s0[2] = {0, 0}, slen[2] = {0, 0}, sbase[2] = {0, 0};
-    bool live[2];
+    const int64_t pr = (int64_t)blockIdx.x * 4 + wv;     // a wave past the last pair is dead in both slots
+    int64_t n0 = 0, s0[2] = {0, 0}, slen[2] = {0, 0}, sbase[2] = {0, 0};   // rows n0 (A) and n0 + 1 (B) of the outputs
+    bool live[2] = {false, false};
+    if (pr < a.P) {
+        const int u = a.p_utt[pr];             // utterance of this pair (host-built table)
+        const int64_t f0 = a.f_off[u], t0 = 2 * (pr - a.p_off[u]), T = a.f_off[u + 1] - f0;
+        n0 = f0 + t0;
 #pragma unroll
-    for (int h = 0; h < 2; ++h) {
-        const int64_t n = n0 + h;
-        live[h] = n < a.N;
-        if (live[h]) {
-            const int u = a.f_utt[n];          // utterance of this frame (host-built table)
-            sbase[h] = a.s_beg[u];
-            slen[h] = a.s_end[u] - sbase[h];
-            s0[h] = (n - a.f_off[u]) * a.fstep;
+        for (int h = 0; h < 2; ++h) {
+            live[h] = t0 + h < T;              // (the odd last frame of an utterance has no partner)
+            if (live[h]) {
+                sbase[h] = a.s_beg[u];
+                slen[h] = a.s_end[u] - sbase[h];
+                s0[h] = (t0 + h) * a.fstep;
+            }
         }
     }
     // ---- windowed, zero padded frames: lane l holds z[l + 64 j], j = 0..7 ----
@@ -99,8 +105,8 @@ __global__ __launch_bounds__(256) void mfcc_kernel(MfccArgs a) {
         });
 }
 
-void launch_mfcc(const MfccArgs& a, int64_t N, hipStream_t st) {
-    const dim3 grid((unsigned)((N + 7) / 8)), block(256);
+void launch_mfcc(const MfccArgs& a, hipStream_t st) {
+    const dim3 grid((unsigned)((a.P + 3) / 4)), block(256);
     if (a.fmt == 0) hipLaunchKernelGGL(mfcc_kernel<0>, grid, block, 0, st, a);
     else if (a.fmt == 1) hipLaunchKernelGGL(mfcc_kernel<1>, grid, block, 0, st, a);
     else hipLaunchKernelGGL(mfcc_kernel<2>, grid, block, 0, st, a);
@@ -108,14 +114,23 @@ void launch_mfcc(const MfccArgs& a, int64_t N, hipStream_t st) {
 
 size_t fmt_size(int fmt) { return fmt == 0 ? 2 : (fmt == 1 ? 4 : 8); }
 
-// the utterance of every frame, the table mfcc_kernel finds its samples with
-void fill_f_utt(int64_t U, const int64_t* f_off, std::vector<int32_t>& f_utt) {
-    f_utt.resize((size_t)f_off[U]);
-    for (int64_t u = 0; u < U; ++u) std::fill(f_utt.begin() + f_off[u], f_utt.begin() + f_off[u + 1], (int32_t)u);
+// the frame pairs of a batch, ceil(T_u / 2) per utterance: where every utterance's pairs begin and the utterance of every
+// pair, the tables mfcc_kernel finds its frames and samples with
+struct PairTable {
+    std::vector<int64_t> off;      // [U + 1]
+    std::vector<int32_t> utt;      // [off[U]]
+    int64_t pairs() const { return off.empty() ? 0 : off.back(); }
+};
+
+void fill_pairs(int64_t U, const int64_t* f_off, PairTable& pt) {
+    pt.off.assign((size_t)U + 1, 0);
+    for (int64_t u = 0; u < U; ++u) pt.off[(size_t)u + 1] = pt.off[(size_t)u] + (f_off[u + 1] - f_off[u] + 1) / 2;
+    pt.utt.resize((size_t)pt.off[(size_t)U]);
+    for (int64_t u = 0; u < U; ++u) std::fill(pt.utt.begin() + pt.off[(size_t)u], pt.utt.begin() + pt.off[(size_t)u + 1], (int32_t)u);
 }
 
 int check_inputs(const char* who, int fmt, int64_t U, const void* samples, const int64_t* s_off, const int64_t* f_off,
-                 const HostTables& h, std::vector<int32_t>& f_utt) {
+                 const HostTables& h, PairTable& pt) {
     GH_REQUIRE(fmt >= 0 && fmt <= 2, "%s: sample_fmt=%d (0 int16, 1 float32, 2 float64)", who, fmt);
     GH_REQUIRE(U >= 0 && s_off && f_off && s_off[0] == 0 && f_off[0] == 0, "%s: offsets must start at 0", who);
     GH_REQUIRE(samples || s_off[U] == 0, "%s: samples is NULL", who);
@@ -126,21 +141,21 @@ int check_inputs(const char* who, int fmt, int64_t U, const void* samples, const
         GH_REQUIRE(f_off[u + 1] - f_off[u] == nf, "%s: frame_off gives utterance %lld %lld frames, ceil(%lld / %d) = %lld",
                    who, (long long)u, (long long)(f_off[u + 1] - f_off[u]), (long long)len, h.fstep, (long long)nf);
     }
-    fill_f_utt(U, f_off, f_utt);
+    fill_pairs(U, f_off, pt);
     return GH_OK;
 }
 
 // carve the inputs + tables out of one block, upload, return the kernel arguments
 // (resident: the samples are on the device already and the utterances are ranges of them -- the endpointed entry)
-size_t table_bytes(int fmt, int64_t n_samples, int64_t U, int64_t N, bool resident = false) {
+size_t table_bytes(int fmt, int64_t n_samples, int64_t U, int64_t P, bool resident = false) {
     auto al = [](size_t b) { return (b + 255) & ~size_t(255); };
-    return (resident ? 0 : al((size_t)n_samples * fmt_size(fmt))) + 2 * al((size_t)(U + 1) * 8) + (resident ? al((size_t)(U + 1) * 8) : 0) +
-           al((size_t)N * 4) + al(NFFT * 8) + al(2 * NFFT * 8) + 2 * al(NBIN * 8) + al((NFILT + 2) * 4) + al((size_t)NCEPS * NFILT * 8);
+    return (resident ? 0 : al((size_t)n_samples * fmt_size(fmt))) + 3 * al((size_t)(U + 1) * 8) + (resident ? al((size_t)(U + 1) * 8) : 0) +
+           al((size_t)P * 4) + al(NFFT * 8) + al(2 * NFFT * 8) + 2 * al(NBIN * 8) + al((NFILT + 2) * 4) + al((size_t)NCEPS * NFILT * 8);
 }
 
 // samples + s_off [U+1]: utterances back to back, uploaded here; or d_pcm + s_off / s_end [U]: ranges of resident samples
 hipError_t upload_inputs(char* base, hipStream_t st, int fmt, int64_t U, const void* samples, const int64_t* s_off,
-                         const int64_t* f_off, const HostTables& h, const std::vector<int32_t>& f_utt, MfccArgs& a,
+                         const int64_t* f_off, const HostTables& h, const PairTable& pt, MfccArgs& a,
                          const void* d_pcm = nullptr, const int64_t* s_end = nullptr) {
     auto al = [](size_t b) { return (b + 255) & ~size_t(255); };
     char* p = base;
@@ -161,14 +176,15 @@ hipError_t upload_inputs(char* base, hipStream_t st, int fmt, int64_t U, const v
         a.s_end = a.s_beg + 1;
     }
     a.f_off = (const int64_t*)put(f_off, (size_t)(U + 1) * 8);
-    a.f_utt = (const int32_t*)put(f_utt.data(), f_utt.size() * 4);
+    a.p_off = (const int64_t*)put(pt.off.data(), (size_t)(U + 1) * 8);
+    a.p_utt = (const int32_t*)put(pt.utt.data(), pt.utt.size() * 4);
     a.t.window = (const double*)put(h.window.data(), NFFT * 8);
     a.t.tw = (const double*)put(h.tw.data(), 2 * NFFT * 8);
     a.t.wup = (const double*)put(h.wup.data(), NBIN * 8);
     a.t.wdn = (const double*)put(h.wdn.data(), NBIN * 8);
     a.t.seg = (const int*)put(h.seg.data(), (NFILT + 2) * 4);
     a.t.dct = (const double*)put(h.dct.data(), (size_t)NCEPS * NFILT * 8);
-    a.fmt = fmt; a.U = U; a.N = f_off[U];
+    a.fmt = fmt; a.U = U; a.P = pt.pairs();
     a.flen = h.flen; a.fstep = h.fstep; a.pad_left = h.pad_left;
     return e;
 }
@@ -186,26 +202,26 @@ extern "C" int gh_mfcc(gh_ctx* ctx, int sample_fmt, int sample_rate, double fram
                        const int64_t* frame_off, double* out_fbank, double* out_mfcc) {
     GH_REQUIRE(ctx, "gh_mfcc: ctx is NULL");
     HostTables h;
-    std::vector<int32_t> f_utt;
+    PairTable pt;
     int rc = build_tables("gh_mfcc", sample_rate, frame_size, frame_stride, low_freq, high_freq, h);
     if (rc) return rc;
-    if ((rc = check_inputs("gh_mfcc", sample_fmt, U, samples, sample_off, frame_off, h, f_utt))) return rc;
+    if ((rc = check_inputs("gh_mfcc", sample_fmt, U, samples, sample_off, frame_off, h, pt))) return rc;
     const int64_t N = frame_off[U];
     if (N == 0) return GH_OK;
     GH_HIP(hipSetDevice(ctx->device));
     char* d_in;
     double *d_fb, *d_mf;
     Carver cv;
-    cv.add(&d_in, table_bytes(sample_fmt, sample_off[U], U, N));
+    cv.add(&d_in, table_bytes(sample_fmt, sample_off[U], U, pt.pairs()));
     cv.add(&d_fb, (size_t)N * NFILT);
     cv.add(&d_mf, (size_t)N * NCEPS);
     if ((rc = cv.commit(ctx))) return rc;
     hipStream_t st = ctx->stream;
     MfccArgs a;
-    GH_HIP(upload_inputs(d_in, st, sample_fmt, U, samples, sample_off, frame_off, h, f_utt, a));
+    GH_HIP(upload_inputs(d_in, st, sample_fmt, U, samples, sample_off, frame_off, h, pt, a));
     a.out_fb = d_fb;
     a.out_mfcc = d_mf;
-    launch_mfcc(a, N, st);
+    launch_mfcc(a, st);
     GH_HIP(hipGetLastError());
     if (out_fbank) GH_HIP(hipMemcpyAsync(out_fbank, d_fb, (size_t)N * NFILT * 8, hipMemcpyDeviceToHost, st));
     if (out_mfcc) GH_HIP(hipMemcpyAsync(out_mfcc, d_mf, (size_t)N * NCEPS * 8, hipMemcpyDeviceToHost, st));
@@ -219,21 +235,21 @@ extern "C" int gh_batch_create_from_pcm(gh_ctx* ctx, gh_dtype dtype, int mode, i
                                         const int64_t* frame_off, gh_batch** out) {
     GH_REQUIRE(ctx && out, "gh_batch_create_from_pcm: NULL argument");
     HostTables h;
-    std::vector<int32_t> f_utt;
+    PairTable pt;
     int rc = build_tables("gh_mfcc", sample_rate, frame_size, frame_stride, low_freq, high_freq, h);
     if (rc) return rc;
-    if ((rc = check_inputs("gh_batch_create_from_pcm", sample_fmt, U, samples, sample_off, frame_off, h, f_utt))) return rc;
+    if ((rc = check_inputs("gh_batch_create_from_pcm", sample_fmt, U, samples, sample_off, frame_off, h, pt))) return rc;
     const int64_t N = frame_off[U];
     void* extra = nullptr;
     return gh_batch_from_device_cepstra(
-        ctx, dtype, mode, NCEPS, N, U, frame_off, table_bytes(sample_fmt, sample_off[U], U, N), &extra,
+        ctx, dtype, mode, NCEPS, N, U, frame_off, table_bytes(sample_fmt, sample_off[U], U, pt.pairs()), &extra,
         [&](double* d_ceps, hipStream_t st) {
             MfccArgs a;
-            hipError_t e = upload_inputs(static_cast<char*>(extra), st, sample_fmt, U, samples, sample_off, frame_off, h, f_utt, a);
+            hipError_t e = upload_inputs(static_cast<char*>(extra), st, sample_fmt, U, samples, sample_off, frame_off, h, pt, a);
             if (e != hipSuccess) return e;
             a.out_fb = nullptr;
             a.out_mfcc = d_ceps;
-            launch_mfcc(a, N, st);
+            launch_mfcc(a, st);
             return hipGetLastError();
         },
         "gh_batch_create_from_pcm", out);
@@ -251,7 +267,7 @@ extern "C" int gh_batch_create_from_pcm_endpointed(gh_ctx* ctx, gh_dtype dtype, 
     GH_REQUIRE(U >= 0 && sample_off[0] == 0 && start_boundary >= 0 && max_segments >= 1, "%s: U=%lld start_boundary=%d max_segments=%d",
                who, (long long)U, start_boundary, max_segments);
     HostTables h;
-    std::vector<int32_t> f_utt;
+    PairTable pt;
     int rc = build_tables("gh_mfcc", sample_rate, frame_size, frame_stride, low_freq, high_freq, h);
     if (rc) return rc;
     for (int64_t u = 0; u < U; ++u)
@@ -290,17 +306,17 @@ extern "C" int gh_batch_create_from_pcm_endpointed(gh_ctx* ctx, gh_dtype dtype, 
     memcpy(utt_frame_off, f_off.data(), (size_t)(U2 + 1) * 8);
     s_beg.push_back(0);       // (both tables travel with U2 + 1 entries)
     s_end.push_back(0);
-    fill_f_utt(U2, f_off.data(), f_utt);
+    fill_pairs(U2, f_off.data(), pt);
     void* extra = nullptr;
     return gh_batch_from_device_cepstra(
-        ctx, dtype, mode, NCEPS, N, U2, f_off.data(), table_bytes(0, 0, U2, N, true), &extra,
+        ctx, dtype, mode, NCEPS, N, U2, f_off.data(), table_bytes(0, 0, U2, pt.pairs(), true), &extra,
         [&](double* d_ceps, hipStream_t st) {
             MfccArgs a;
-            hipError_t e = upload_inputs(static_cast<char*>(extra), st, 0, U2, nullptr, s_beg.data(), f_off.data(), h, f_utt, a, d_pcm, s_end.data());
+            hipError_t e = upload_inputs(static_cast<char*>(extra), st, 0, U2, nullptr, s_beg.data(), f_off.data(), h, pt, a, d_pcm, s_end.data());
             if (e != hipSuccess) return e;
             a.out_fb = nullptr;
             a.out_mfcc = d_ceps;
-            launch_mfcc(a, N, st);
+            launch_mfcc(a, st);
             return hipGetLastError();
         },
         who, out);

@@ -56,6 +56,13 @@ __device__ __forceinline__ void mfcc_pair_tail(const MfccTables& t, c2 (&v)[8], 
                                                const double* s_wup, const double* s_wdn, int lane, StoreFbank store_fbank,
                                                StoreCeps store_ceps) {
     constexpr int S1 = MFCC_S1, S2 = MFCC_S2;
+    // A frame without a non-zero windowed sample has power exactly 0 in the reference, which its `== 0` rule (feature.py:77)
+    // turns into eps.  Here its partner's rounding would leak into it (Z[k] and Z[N - k] are conjugates only up to rounding,
+    // some 1e-16 of the partner's spectrum): such a frame is found before the FFT and gets its zeros written below.
+    bool nz0 = false, nz1 = false;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) { nz0 |= v[j].x != 0.0; nz1 |= v[j].y != 0.0; }
+    const bool any0 = __any(nz0), any1 = __any(nz1);
     // ---- pass 1: DFT over j, twiddle W512^(l q); transpose so that lane (l1 + 8 q) holds l2 = 0..7 ----
     dft8(v);
 #pragma unroll
@@ -106,8 +113,9 @@ __device__ __forceinline__ void mfcc_pair_tail(const MfccTables& t, c2 (&v)[8], 
         const c2 z = (i < 4) ? v[i] : v[4];                  // k = 256 sits in lane 0, register 4
         const double ar = z.x + wx[i], ai = z.y - wy[i], br = z.x - wx[i], bi = z.y + wy[i];
         if (k < NBIN) {
-            pw[k] = (ar * ar + ai * ai) * (0.25 / NFFT);
-            pw[264 + k] = (br * br + bi * bi) * (0.25 / NFFT);
+            const double pa = (ar * ar + ai * ai) * (0.25 / NFFT), pb = (br * br + bi * bi) * (0.25 / NFFT);
+            pw[k] = any0 ? pa : 0.0;
+            pw[264 + k] = any1 ? pb : 0.0;
         }
     }
     __syncthreads();

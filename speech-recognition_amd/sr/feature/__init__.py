@@ -95,9 +95,9 @@ def features_from_signals(signals, sample_rate=16000, dtype=np.float64, device=N
     all on the device; returns the `_hip.Batch` ready for `loglik` / decoding.
 
     normalize=(mean [39], std [39]): the FIXED map (x - mean) / std of `StreamingFrontend` in place of the per-utterance
-    `standardize` -- the raw stacked features (rounded to `dtype`) go through `Batch.affine`: for an utterance alone in its
-    batch bitwise what a stream with the same pair emits (in a batch of several, an utterance behind an odd number of frames
-    shares its FFTs with other partners: equal to rounding).  `feature_stats` computes such a pair from training audio.
+    `standardize` -- the raw stacked features (rounded to `dtype`) go through `Batch.affine`: bitwise what a stream with the
+    same pair emits for the utterance, wherever it stands in the batch (frames share an FFT in pairs, and pair inside their
+    utterance).  `feature_stats` computes such a pair from training audio.
     normalize=RunningNorm(...): the causal running normalisation instead, through `Batch.running_norm` on the same raw
     batch, every utterance alone from zero statistics (`per` plays no part here) -- the features to train the models of
     a `StreamingFrontend(normalize=RunningNorm(...))` with, and bitwise what such a stream emits for the utterance.

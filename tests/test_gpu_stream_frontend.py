@@ -3,8 +3,8 @@
 
 The contract is BITWISE: whatever way a stream's audio is cut into chunks, its concatenated frames are the one-shot
 front-end's (`_hip.Batch(ctx, pcm=[signal], frontend_mode=1)`) for that utterance alone, in both dtypes -- same kernel
-arithmetic, frames paired by absolute index.  Against the numpy oracle the streamed features are held to the
-rtol = atol = 1e-7 that test_gpu_api.py holds `features_from_signals` to.  The fixed normalisation is one IEEE
+arithmetic, frames paired by their index inside the utterance by both.  Against the numpy oracle the streamed features are
+held to the rtol = atol = 1e-7 that test_gpu_api.py holds `features_from_signals` to.  The fixed normalisation is one IEEE
 subtraction and one division in fp64 on the dtype-rounded value, so it is compared bitwise with numpy as well."""
 import numpy as np
 import pytest
@@ -128,20 +128,20 @@ def test_normalisation_is_the_fixed_affine_map(hip, ctx, g15, one_shot):
     from sr.feature import StreamingFrontend, feature_stats, features_from_signals
     sigs, _ = g15
     rng = np.random.default_rng(16)
-    # (signal 5 has 26 frames, an even number: the utterance behind it keeps the frame pairs it has alone -- see below)
     train = [sigs[5], sigs[6]]
     mean, std = feature_stats(train, 16000)
     raw = np.concatenate([one_shot[5][np.float64], one_shot[6][np.float64]])
     np.testing.assert_array_equal(mean, raw.mean(axis=0))
     np.testing.assert_array_equal(std, raw.std(axis=0))
     for dtype in (np.float64, np.float32):
-        fe = StreamingFrontend(2, 16000, normalize=(mean, std), max_chunk=16000, dtype=dtype)
-        got = stream_all(fe, rng, [sigs[5], sigs[8]], [cut(rng, 4001, "random"), cut(rng, 800, 160)], [True, False])
+        fe = StreamingFrontend(3, 16000, normalize=(mean, std), max_chunk=16000, dtype=dtype)
+        got = stream_all(fe, rng, [sigs[8], sigs[5], sigs[4]], [cut(rng, 800, 160), cut(rng, 4001, "random"), cut(rng, 400, 37)],
+                         [False, True, False])
         fe.close()
-        # offline, both in ONE batch: the MFCC kernel pairs frames across the whole batch, so an utterance is bitwise what it
-        # is alone when an even number of frames precedes it (26 here); behind an odd number it is equal to rounding only
-        off = features_from_signals([sigs[5], sigs[8]], 16000, dtype=dtype, normalize=(mean, std))
-        for i, f, o in zip((5, 8), got, off.features()):
+        # offline, all in ONE batch: the MFCC kernel pairs frames inside their utterance, so an utterance is bitwise what it
+        # is alone wherever it stands (here behind 5 frames, and behind 5 + 26)
+        off = features_from_signals([sigs[8], sigs[5], sigs[4]], 16000, dtype=dtype, normalize=(mean, std))
+        for i, f, o in zip((8, 5, 4), got, off.features()):
             # the definition: the raw value rounded to the dtype, (x - mean) / std in fp64, rounded to the dtype
             want = ((one_shot[i][dtype].astype(np.float64) - mean) / std).astype(dtype)
             np.testing.assert_array_equal(f, want)

@@ -1,5 +1,6 @@
 # -*- coding: utf-8 -*-
-"""Front-end timing: U utterances of 1 s int16 audio -> resident 39-dim batch (MFCC, deltas, standardise)."""
+"""Front-end timing: U utterances of 1 s int16 audio -> resident 39-dim batch (MFCC, deltas, standardise).
+usage: time_frontend.py [U, default 2000] [samples per utterance, default 16000 = 100 frames; 15840 = 99, an odd count]"""
 import os, sys, time
 import numpy as np
 sys.path.insert(0, os.path.join(os.path.dirname(__file__), "..", "speech-recognition_amd"))
@@ -7,7 +8,8 @@ from sr.recognition import _hip
 
 U = int(sys.argv[1]) if len(sys.argv) > 1 else 2000
 rng = np.random.default_rng(0)
-sig = (rng.normal(size=(U, 16000)) * 3000).astype(np.int16)
+n = int(sys.argv[2]) if len(sys.argv) > 2 else 16000
+sig = (rng.normal(size=(U, n)) * 3000).astype(np.int16)
 sigs = list(sig)
 ctx = _hip.default_context(0)
 for k in range(4):
