@@ -498,6 +498,40 @@ int gh_forward_backward(gh_ctx* ctx, const gh_lattices* lat, gh_batch* b,
                         double* out_logp, double* out_alpha, double* out_beta, double* out_gamma,
                         const int64_t* mat_off /*[U+1]*/, double* out_occ, double* out_self_xi /*[S] or NULL*/);
 
+/* ------------------------- word posteriors and per-word confidence (loop form)
+ * NOT in the reference, like A13; pinned by brute-force path enumeration in the tests, not by reference outputs.
+ * For a handle whose graph 0 is in LOOP form (the word-loop grammar: W words of n states, 1 <= W <= 64, 2 <= n <= 8) and the
+ * batch's resident likelihood matrix (gh_loglik must have run, as for gh_viterbi): a forward-backward over the loop form
+ * with one wave per utterance, lane = word.
+ * DEFINITION.  With log alpha la, log beta lb, log P and costs trans[to, from] of A13, loop row Lr and last_w the last state
+ * of word w: every path visits one or more emitting cells per column, more than one exactly where it hops through the loop
+ * row; a path's WORD AT FRAME t is the word of the LAST emitting cell it visits in column t (the boundary frame belongs to
+ * the entering word: the begin rule of gh_viterbi_labels_timed).  Its posterior is
+ *     q_t(w) = sum_s gamma_t(w, s)  -  exp( la[last_w, t] - trans[Lr, last_w] + lb[Lr, t] - logP )
+ * (the subtracted term: leaving word w through the loop row in column t).  sum_w q_t(w) = 1 for every t, 0 <= q <= 1 (a
+ * result below 0 by rounding is stored as 0); an utterance without a path (log P = -inf, e.g. fewer frames than states) has
+ * q = 0 throughout.  The frame-wise sum of gamma -- what gh_forward_backward's occ holds -- is NOT this quantity: it counts a
+ * boundary frame for both words and exceeds 1.
+ *   out_logp  [U] or NULL       log P(utterance), -inf if no path
+ *   out_post  [N, W] or NULL    q, one row per frame of the batch, column = word of the loop form
+ *   labels, begins, label_off [U+1], n_labels [U]   the words of a decode and their begin frames, laid out as
+ *             gh_viterbi_labels_timed returns them (utterance u: n_labels[u] entries at label_off[u]); all four NULL: no
+ *             confidences.  A label is a word of the loop form, 0 <= label < W.
+ *   out_conf  laid out like labels, or NULL: conf_k = the mean of q_t(label_k) over the word's frames begin_k <= t < end_k,
+ *             end_k = begin_{k+1}, the last word ends at the utterance's frame count; in [0, 1], 0.0 where log P = -inf.
+ *             Summed in descending t inside the backward sweep: independent of batch position and chunking.  Entries of
+ *             a slot behind n_labels[u] come back 0.0.
+ * Everything is checked before anything is enqueued.  GH_ERR_UNSUPPORTED, with a sentence per case: graph 0 not in loop
+ * form (bigram, wide bigram, K-layer, transcripts, generic), words of 12 or 16 states, a rank beam on the handle.
+ * GH_ERR_INVALID: a batch without likelihoods; a span table with a label outside [0, W), a begin outside [0, T), begins
+ * that do not strictly increase inside an utterance, or n_labels beyond the slot.  Alpha scratch: 8 T n W bytes per
+ * utterance, cut into launches by the scratch budget, longest first (gh_ctx_last_chunks); U == 0: GH_OK, 0 launches. */
+int gh_word_posteriors(gh_ctx* ctx, const gh_lattices* lat, gh_batch* b,
+                       double* out_logp /*[U] or NULL*/, double* out_post /*[N, W] or NULL*/,
+                       const int32_t* labels, const int32_t* begins, const int64_t* label_off /*[U+1]*/,
+                       const int32_t* n_labels /*[U]*/,        /* all four NULL: no confidences */
+                       double* out_conf /*laid out like labels, or NULL*/);
+
 /* ------------------------------------ Baum-Welch (soft) sufficient statistics
  * After gh_forward_backward(want_occ = 1): for every frame n and state s,
  *   r_nsm = occ[n,s] * w_sm pdf_sm(x_n) / sum_m' w_sm' pdf_sm'(x_n)

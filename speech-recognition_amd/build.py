@@ -30,7 +30,9 @@ EXTRA = {"gh_loglik_mfma.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"],
          # ... and the streaming detector rounds like the one-shot one
          "gh_endpoint_stream.hip": ["-ffp-contract=off"],
          # the running normalisation is defined operation by operation: numpy scalars round the same
-         "gh_norm_running.hip": ["-ffp-contract=off"]}
+         "gh_norm_running.hip": ["-ffp-contract=off"],
+         # the loop-form forward-backward writes every sum the way the host statement of the word posteriors does
+         "gh_fb_loop.hip": ["-ffp-contract=off"]}
 
 
 def _sources():

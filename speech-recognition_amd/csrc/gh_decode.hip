@@ -1002,6 +1002,112 @@ extern "C" int gh_forward_backward(gh_ctx* ctx, const gh_lattices* lat, gh_batch
     return GH_OK;
 }
 
+// ------------------------------------------- word posteriors (loop form)
+extern "C" int gh_word_posteriors(gh_ctx* ctx, const gh_lattices* lat, gh_batch* b, double* out_logp, double* out_post,
+                                  const int32_t* labels, const int32_t* begins, const int64_t* label_off, const int32_t* n_labels,
+                                  double* out_conf) {
+    GH_REQUIRE(ctx && lat && b, "gh_word_posteriors: NULL argument");
+    // what the handle is, before anything else: every refusal has a sentence of its own
+    if (!(lat->layers_ok && lat->h_layers.loop == 1)) {
+        if (lat->bigram_wide_ok) gh_set_error("gh_word_posteriors: the graph is in wide bigram form: word posteriors are built for the loop form only");
+        else if (lat->bigram_ok) gh_set_error("gh_word_posteriors: the graph is in bigram form: word posteriors are built for the loop form only");
+        else if (lat->layers_ok) gh_set_error("gh_word_posteriors: the graph is a K-layer lattice (%d layers): word posteriors are built for the loop form only", lat->h_layers.K);
+        else if (lat->seq_ok || lat->deferred_src) gh_set_error("gh_word_posteriors: the handle holds transcript graphs (sequence form): word posteriors are built for the loop form only");
+        else gh_set_error("gh_word_posteriors: graph 0 is not in loop form (generic graph): word posteriors are built for the loop form only");
+        return GH_ERR_UNSUPPORTED;
+    }
+    const gh_layerform& f = lat->h_layers;
+    if (f.N > 8) {
+        gh_set_error("gh_word_posteriors: words of %d states: the loop-form forward-backward is built for 2 .. 8 states per word", f.N);
+        return GH_ERR_UNSUPPORTED;
+    }
+    if (lat->beam) {
+        gh_set_error("gh_word_posteriors: a rank beam (%d) is set on the handle: posteriors are sums over all paths, not over a pruned decode", lat->beam);
+        return GH_ERR_UNSUPPORTED;
+    }
+    GH_REQUIRE(b->nll || b->N == 0, "gh_word_posteriors: gh_loglik has not been run on this batch");
+    const int64_t U = b->U;
+    const int W = f.W, N = f.N;
+    const bool spans = labels || begins || label_off || n_labels;
+    GH_REQUIRE(!spans || (labels && begins && label_off && n_labels),
+               "gh_word_posteriors: the span table needs labels, begins, label_off and n_labels (all four, or none)");
+    GH_REQUIRE(!out_conf || spans, "gh_word_posteriors: out_conf needs the span table");
+    if (U == 0) { ctx->last_chunks = 0; return GH_OK; }
+    const int S = b->nll_S;
+    GH_REQUIRE(lat->lat[0].max_state < S, "gh_word_posteriors: the graph uses state %d but the model has %d", lat->lat[0].max_state, S);
+    if (spans) {
+        GH_REQUIRE(label_off[0] >= 0, "gh_word_posteriors: label_off[0] = %lld", (long long)label_off[0]);
+        for (int64_t u = 0; u < U; ++u) {
+            const int64_t cap = label_off[u + 1] - label_off[u], T = b->offsets[u + 1] - b->offsets[u];
+            GH_REQUIRE(cap >= 0, "gh_word_posteriors: label_off decreases at utterance %lld", (long long)u);
+            GH_REQUIRE(n_labels[u] >= 0 && n_labels[u] <= cap, "gh_word_posteriors: n_labels[%lld] = %d lies beyond the slot of %lld entries",
+                       (long long)u, n_labels[u], (long long)cap);
+            for (int k = 0; k < n_labels[u]; ++k) {
+                const int32_t l = labels[label_off[u] + k], bg = begins[label_off[u] + k];
+                GH_REQUIRE(l >= 0 && l < W, "gh_word_posteriors: utterance %lld, word %d: label %d outside [0, %d)", (long long)u, k, l, W);
+                GH_REQUIRE(bg >= 0 && bg < T, "gh_word_posteriors: utterance %lld, word %d: begin %d outside [0, %lld)", (long long)u, k, bg, (long long)T);
+                GH_REQUIRE(k == 0 || bg > begins[label_off[u] + k - 1], "gh_word_posteriors: utterance %lld, word %d: begins do not strictly increase (%d after %d)",
+                           (long long)u, k, bg, begins[label_off[u] + k - 1]);
+            }
+        }
+    }
+    GH_HIP(hipSetDevice(ctx->device));
+    // alpha scratch [T, N, W] doubles per utterance, chunked (<= gh_scratch_budget() bytes per launch), longest first
+    const size_t BUDGET = gh_scratch_budget(ctx);
+    std::vector<int64_t> soff(U, 0), chunk_begin{0};
+    size_t acc = 0, smax = 0;
+    for (int64_t k = 0; k < U; ++k) {
+        const int64_t u = b->perm[k];
+        const size_t need = (size_t)(b->offsets[u + 1] - b->offsets[u]) * N * W;
+        if (acc && (acc + need) * 8 > BUDGET) { chunk_begin.push_back(k); smax = std::max(smax, acc); acc = 0; }
+        soff[k] = (int64_t)acc;
+        acc += need;
+    }
+    smax = std::max(smax, acc);
+    chunk_begin.push_back(U);
+    ctx->last_chunks = (int)chunk_begin.size() - 1;
+    const bool want_conf = spans && out_conf;
+    const int64_t n_lab = spans ? label_off[U] : 0;
+    int64_t *d_soff, *d_laboff = nullptr;
+    int32_t *d_labels = nullptr, *d_begins = nullptr, *d_nlab = nullptr;
+    double *d_scratch, *d_logp, *d_post = nullptr, *d_conf = nullptr;
+    Carver cv;
+    cv.add(&d_soff, U); cv.add(&d_logp, U); cv.add(&d_scratch, smax);
+    if (out_post) cv.add(&d_post, (size_t)b->N * W);
+    if (want_conf) {
+        cv.add(&d_laboff, U + 1); cv.add(&d_nlab, U); cv.add(&d_labels, std::max<int64_t>(n_lab, 1)); cv.add(&d_begins, std::max<int64_t>(n_lab, 1));
+        cv.add(&d_conf, std::max<int64_t>(n_lab, 1));
+    }
+    int rc = cv.commit(ctx);
+    if (rc) return rc;
+    hipStream_t st = ctx->stream;
+    GH_HIP(hipMemcpyAsync(d_soff, soff.data(), U * 8, hipMemcpyHostToDevice, st));
+    if (want_conf) {
+        GH_HIP(hipMemcpyAsync(d_laboff, label_off, (U + 1) * 8, hipMemcpyHostToDevice, st));
+        GH_HIP(hipMemcpyAsync(d_nlab, n_labels, U * 4, hipMemcpyHostToDevice, st));
+        if (n_lab > 0) {
+            GH_HIP(hipMemcpyAsync(d_labels, labels, n_lab * 4, hipMemcpyHostToDevice, st));
+            GH_HIP(hipMemcpyAsync(d_begins, begins, n_lab * 4, hipMemcpyHostToDevice, st));
+            GH_HIP(hipMemsetAsync(d_conf, 0, n_lab * 8, st));     // entries behind n_labels[u] come back as 0.0
+        }
+    }
+    gh_fbloop_args a;
+    memset(&a, 0, sizeof a);
+    a.lf = lat->d_layers; a.end_slot = lat->d_lf_end_slot; a.nll = b->nll; a.S = S;
+    a.utt_off = b->d_offsets; a.perm = b->d_perm; a.alpha_scratch = d_scratch; a.scratch_off = d_soff; a.logp = d_logp;
+    a.post = d_post;
+    if (want_conf) { a.labels = d_labels; a.begins = d_begins; a.label_off = d_laboff; a.n_labels = d_nlab; a.conf = d_conf; }
+    for (size_t c = 0; c + 1 < chunk_begin.size(); ++c) {
+        rc = gh_launch_fb_loop(ctx, a, f, chunk_begin[c], chunk_begin[c + 1] - chunk_begin[c], b->dtype == GH_F64);
+        if (rc) return rc;
+    }
+    if (out_logp) GH_HIP(hipMemcpyAsync(out_logp, d_logp, U * 8, hipMemcpyDeviceToHost, st));
+    if (out_post && b->N > 0) GH_HIP(hipMemcpyAsync(out_post, d_post, (size_t)b->N * W * 8, hipMemcpyDeviceToHost, st));
+    if (want_conf && n_lab > 0) GH_HIP(hipMemcpyAsync(out_conf, d_conf, n_lab * 8, hipMemcpyDeviceToHost, st));
+    GH_HIP(hipStreamSynchronize(st));
+    return GH_OK;
+}
+
 
 extern "C" int gh_align_segments(gh_ctx* ctx, const gh_lattices* lat, const gh_batch* b, const int32_t* utt_lattice,
                                  double* out_end_cost, int32_t* out_best_end, int32_t* out_frame_state) {

@@ -96,5 +96,27 @@ struct gh_fbseq_args {
     int32_t* row_lo;             // optional [U, GH_SEQ_MAXK, GH_LAYERS_MAXN] (lane = cell kernel only): frame range of every
     int32_t* row_hi;             //   cell with occupancy above occ_floor
 };
+// loop form (gh_layerform with loop == 1): one utterance per wave, lane = word (fb_loop_kernel, gh_fb_loop.hip) -- log P,
+// the word posteriors q_t(w) and the confidences of given word spans (gh_word_posteriors)
+struct gh_fbloop_args {
+    const gh_layerform* lf;
+    const int32_t* end_slot;     // [R] >= 0 on end rows
+    const void* nll;
+    int S;
+    const int64_t* utt_off;
+    const int64_t* perm;
+    int64_t slot0;
+    double* alpha_scratch;       // [T, N, W] per launch slot
+    const int64_t* scratch_off;  // [slots]
+    double* logp;                // [U]
+    double* post;                // optional [frames of the batch, W]
+    const int32_t* labels;       // span table (with conf): utterance u at label_off[u], n_labels[u] spans
+    const int32_t* begins;
+    const int64_t* label_off;    // [U+1]
+    const int32_t* n_labels;     // [U]
+    double* conf;                // optional, laid out like labels
+};
+int gh_launch_fb_loop(gh_ctx* ctx, const gh_fbloop_args& a, const gh_layerform& f, int64_t u_begin, int64_t n_utts, bool f64);
+
 int gh_fb_seq_by_cell(const gh_fbseq_args& a, int N);
 int gh_launch_fb_seq(gh_ctx* ctx, const gh_fbseq_args& a, int N, int skip, int64_t u_begin, int64_t n_utts, bool f64);

@@ -123,6 +123,8 @@ SIGNATURES = {
                                          _c_f64p, _c_f64p, _c_f64p, _c_f64p, C.c_void_p]),
     "gh_forward_backward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, _c_i32p, C.c_int, _c_f64p, _c_f64p, _c_f64p,
                                       _c_f64p, _c_i64p, _c_f64p, _c_f64p]),
+    "gh_word_posteriors": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, _c_f64p, _c_f64p, _c_i32p, _c_i32p, _c_i64p, _c_i32p,
+                                     _c_f64p]),
     "gh_bw_accumulate": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, _c_f64p, C.c_void_p]),
     "gh_em_accumulate": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int, _c_f64p, _c_f64p,
                                    _c_f64p, _c_f64p, _c_f64p]),
@@ -1185,6 +1187,7 @@ class Lattices:
         arc_cost = cat("arc_cost", np.float64)
         start_rows, end_rows = cat("start_rows", np.int32), cat("end_rows", np.int32)
         self.end_rows = [np.asarray(g["end_rows"], dtype=np.int64) for g in graphs]
+        self._row_state0 = np.asarray(graphs[0]["row_state"], dtype=np.int64).ravel() if L else None
         h = C.c_void_p()
         _check(ctx.lib, ctx.lib.gh_lattices_create(
             ctx.h, L, _ptr(self.row_off, _c_i64p), _ptr(row_state, _c_i32p), _ptr(self.arc_off, _c_i64p),
@@ -1464,6 +1467,57 @@ class Lattices:
             out.update(alpha=cut(al), beta=cut(be), gamma=cut(ga))
         if occ is not None:
             out["occ"] = occ
+        return out
+
+    def _loop_words(self):
+        """Words of graph 0 when it has the rows of the loop form (start row, states 1 .. n-1 of every word, loop row, one
+        first state per word), else None -- the library decides what the graph is; this only sizes the posteriorgram."""
+        rs = getattr(self, "_row_state0", None)
+        if rs is None:
+            return None
+        nes = np.flatnonzero(rs < 0)
+        if len(nes) != 2 or nes[0] != 0 or len(rs) - 1 - nes[1] < 1:
+            return None
+        return int(len(rs) - 1 - nes[1])
+
+    def word_posteriors(self, batch, labels=None, begins=None, want_post=True):
+        """Word posteriors of a loop-form graph and the confidences of decoded words (gh_word_posteriors): dict(logp [U],
+        post [N, W] -- q_t(w), the posterior that frame t belongs to word w, rows in batch order, a row sums to 1 -- and
+        confidence, one float64 array per utterance).  labels / begins: per utterance the words of a decode and their begin
+        frames (`viterbi_labels(..., want_begin=True)`); the confidence of a word is the mean of its q over its frames.
+        Without them `confidence` is left out; want_post=False: no [N, W] copy-back.  Any other graph form, words of 12 or
+        16 states and a rank beam raise `Unsupported`."""
+        lib, U = self.ctx.lib, batch.U
+        if (labels is None) != (begins is None):
+            raise ValueError("labels and begins come together")
+        W = self._loop_words()
+        logp = np.empty(U)
+        post = np.empty((batch.N, W)) if (want_post and W is not None) else None
+        lab = beg = off = nl = conf = None
+        if labels is not None:
+            if len(labels) != U or len(begins) != U:
+                raise ValueError("labels and begins: one array per utterance")
+            nl = np.array([len(l) for l in labels], dtype=np.int32)
+            if any(len(bg) != n for bg, n in zip(begins, nl)):
+                raise ValueError("every label needs its begin")
+            off = np.concatenate([[0], np.cumsum(nl)]).astype(np.int64)
+            flat = lambda xs: np.ascontiguousarray(np.concatenate([np.asarray(x, dtype=np.int32).reshape(-1) for x in xs])
+                                                   if U else np.zeros(0, np.int32), dtype=np.int32)
+            lab, beg = flat(labels), flat(begins)
+            conf = np.zeros(int(off[-1]))
+        rc = lib.gh_word_posteriors(self.ctx.h, self.h, batch.h, _ptr(logp, _c_f64p) if W is not None else None,
+                                    _ptr(post, _c_f64p), _ptr(lab, _c_i32p), _ptr(beg, _c_i32p), _ptr(off, _c_i64p),
+                                    _ptr(nl, _c_i32p), _ptr(conf, _c_f64p))
+        if rc == GH_ERR_UNSUPPORTED:
+            raise Unsupported(lib.gh_last_error().decode("utf-8", "replace"))
+        _check(lib, rc)
+        if W is None:
+            raise BackendError("word_posteriors: the library took a graph whose rows are not those of the loop form")
+        out = dict(logp=logp)
+        if post is not None:
+            out["post"] = post
+        if conf is not None:
+            out["confidence"] = [conf[off[u]:off[u + 1]] for u in range(U)]
         return out
 
     def close(self):

@@ -391,13 +391,56 @@ class ContinuousDecoder:
         self.row_state = graph["row_state"]
         self.lat = _hip.Lattices(self.ctx, [graph])
 
-    def decode_batch(self, batch, want_path=False, want_times=False):
+    def _posteriors_refusal(self):
+        """Why this decoder has no word posteriors (None: it has).  Decided from what the decoder was built with, before the
+        GPU is touched; the library refuses the same cases on its own."""
+        if self.grammar == "bigram":
+            return ("word posteriors and confidences are built for the word-loop grammar (grammar='loop'); the bigram grammar "
+                    "(one entry row per word) is not built")
+        if self.grammar == "layers":
+            return ("word posteriors and confidences are built for the word-loop grammar (grammar='loop'); the K-layer lattice "
+                    "is not built")
+        if getattr(self.lat, "beam", 0):
+            return ("word posteriors are sums over all paths: a decoder with a rank beam (set_beam(%d)) has none"
+                    % self.lat.beam)
+        if self.n > 8:
+            return "word posteriors are built for words of 2 to 8 states, not %d" % self.n
+        return None
+
+    def word_posteriors(self, batch):
+        """(post, logp): the word posteriorgram post [N, W] of the batch (row = frame in batch order, post[t, w] = the posterior
+        that frame t belongs to word w -- a boundary frame belongs to the entering word, as in the begin times -- every row
+        of an utterance with a path sums to 1) and log P [U] per utterance, from one forward-backward over the loop grammar
+        (gh_word_posteriors).  grammar="loop" with words of 2 to 8 states and no beam; anything else raises `_hip.Unsupported`."""
+        why = self._posteriors_refusal()
+        if why:
+            raise _hip.Unsupported(why)
+        batch.loglik(self.gmm, fetch=False)
+        r = self.lat.word_posteriors(batch)
+        return r["post"], r["logp"]
+
+    def decode_batch(self, batch, want_path=False, want_times=False, want_confidence=False):
         """Word-index lists of every utterance (+ the raw result dict).  By default the paths stay on the device
         and only the decoded word sequences come back (gh_viterbi_labels); want_path=True also returns the
         reference-style (row, column) paths in `r["paths"]` and derives the words from them on the host.
         want_times=True: `r["begins"]` holds one int32 array per utterance, aligned with its words -- the frame every word
         begins in (`path_to_word_times`; gh_viterbi_labels_timed, or the host rule on the paths with want_path=True).
-        Word k ends where word k + 1 begins, the last one at the utterance's frame count (`word_spans`)."""
+        Word k ends where word k + 1 begins, the last one at the utterance's frame count (`word_spans`).
+        want_confidence=True (grammar="loop", words of 2 to 8 states, no beam; else `_hip.Unsupported`): the decode of
+        want_times=True, then one gh_word_posteriors call on the same likelihoods: `r["confidence"]` holds one float64 array
+        per utterance, aligned with its words -- the mean over the word's frames of the posterior that the frame belongs to
+        that word, in [0, 1] -- with `r["begins"]` and `r["logp"]` (log P per utterance).  Words, begins, end costs and
+        chosen ends are those of want_times=True bit for bit."""
+        if want_confidence:
+            why = self._posteriors_refusal()
+            if why:
+                raise _hip.Unsupported(why)
+            if want_path:
+                raise ValueError("want_confidence goes with the label decode, not with want_path")
+            words, r = self.decode_batch(batch, want_times=True)
+            wp = self.lat.word_posteriors(batch, labels=r["labels"], begins=r["begins"], want_post=False)
+            r["confidence"], r["logp"] = wp["confidence"], wp["logp"]
+            return words, r
         batch.loglik(self.gmm, fetch=False)
         if want_path:
             r = self.lat.viterbi(batch, want_path=True)
@@ -413,11 +456,19 @@ class ContinuousDecoder:
             r = self.lat.viterbi_labels(batch, row_word, max_labels=self._max_labels(batch.lengths))
         return [[int(w) for w in l] for l in r["labels"]], r
 
-    def decode(self, xs, want_times=False):
+    def decode(self, xs, want_times=False, want_confidence=False):
         """xs: list of [T_u, D] arrays -> list of word-index lists; want_times=True: (words, begins), begins one int32
-        array per utterance (see `decode_batch`)."""
+        array per utterance (see `decode_batch`); want_confidence=True: (words, begins, confidence), confidence one
+        float64 array per utterance."""
+        if want_confidence:
+            why = self._posteriors_refusal()
+            if why:
+                raise _hip.Unsupported(why)
         batch = _hip.Batch(self.ctx, xs, dtype=self.dtype)
         try:
+            if want_confidence:
+                words, r = self.decode_batch(batch, want_confidence=True)
+                return words, r["begins"], r["confidence"]
             if want_times:
                 words, r = self.decode_batch(batch, want_times=True)
                 return words, r["begins"]

@@ -13,8 +13,10 @@ CSRC = os.path.join(ROOT, "speech-recognition_amd", "csrc")
 files = sys.argv[1:] or sorted(glob.glob(os.path.join(CSRC, "*.hip")))
 KEYS = {"VGPRs": "V", "AGPRs": "A", "ScratchSize [bytes/lane]": "scratch", "Occupancy [waves/SIMD]": "occ",
         "LDS Size [bytes/block]": "lds"}
+sys.path.insert(0, os.path.join(ROOT, "speech-recognition_amd"))
+import build  # noqa: E402  (the per-file flags the library is built with)
 for f in files:
-    extra = ["-mllvm", "-amdgpu-mfma-vgpr-form=1"] if f.endswith("gh_loglik_mfma.hip") else []
+    extra = build.EXTRA.get(os.path.basename(f), [])
     p = subprocess.run(["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "--offload-arch=gfx950", "-fPIC", "-Wno-unused-value",
                         "-Wno-unused-result", "-Rpass-analysis=kernel-resource-usage", "-c", f, "-o", "/dev/null"] + extra,
                        capture_output=True, text=True)
