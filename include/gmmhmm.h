@@ -954,6 +954,34 @@ int gh_wordstream_push(gh_ctx* ctx, gh_wordstream* ws, const gh_batch* b, const 
 int gh_wordstream_result(gh_ctx* ctx, gh_wordstream* ws, int64_t n, const int64_t* ids /*[n] or NULL*/,
                          double* end_cost /*[n, n_end]*/, int32_t* best /*[n]*/);
 
+/* ------------------------------------------------ forward scores of word chains: what a posterior over the vocabulary needs
+ * NOT IN THE REFERENCE.  soft[u, w] = -log P(x_u | word w), summed over ALL paths of the word's chain -- the
+ * sum-product twin of the end costs above, stated by oracle/ref_numpy.forward_backward on one chain with its end row: log
+ * domain, fp64 (for fp32 likelihoods too); column 0: the start row holds -e, every other row -inf; column t, state s
+ * descending: a[s] = LSE(a[s-2] - c2[s], a[s-1] - c1[s], a[s] - c0[s]) - e[s][t], LSE(x..) = max + log(sum exp(x - max)) and
+ * -inf where the maximum is -inf.  No path (e.g. fewer frames than states without skip arcs) gives +inf.  One frame is the
+ * causal column 0: there is no one-frame special case.  The posterior itself (scale, prior, softmax over the W numbers of
+ * an utterance) is the caller's: U x W numbers are no hot path.
+ * gh_chain_forward: out_soft [U, n_end] for every utterance of the batch, whose likelihood matrix must be resident
+ * (gh_loglik).  `lat` as for gh_wordstream_create: ONE graph in the chain form whose chains all have the same number of
+ * rows, 1 .. 8, with consecutive states, without a beam; a loop, bigram or K-layer graph, a handle made from transcripts,
+ * chains of unequal length or of more than 8 rows, several graphs or a beam are GH_ERR_UNSUPPORTED and the message names the
+ * reason; a batch without likelihoods or a graph that uses a state the model lacks is GH_ERR_INVALID.  Everything is checked
+ * before anything is enqueued.  U = 0 is GH_OK.  An utterance without frames gives +inf.  Synchronises.
+ * gh_wordstream_create_soft: gh_wordstream_create of a session that carries the log-alpha column beside the cost column
+ * (another [N][C] doubles per stream, and the same again per tick in and out).  gh_wordstream_push on it enqueues the carried
+ * Viterbi sweep unchanged, then the forward sweep on the same slot table; reset, frames, result and destroy work as before,
+ * and gh_wordstream_result is bitwise what a plain session gives.
+ * gh_wordstream_result_soft: soft [n, n_end] of the streams ids[0..n) (NULL: all n_streams); a stream without frames gives
+ * +inf.  On a session not made by gh_wordstream_create_soft it is GH_ERR_INVALID.  Synchronises.
+ * CONTRACT: for a stream that holds k >= 1 frames, gh_wordstream_result_soft is bitwise gh_chain_forward of a one-utterance
+ * batch of those k frames from the same likelihoods (the same kernel runs both).
+ * NOT BUILT: a fused sweep that computes both columns from one read of the emissions. */
+int gh_chain_forward(gh_ctx* ctx, const gh_lattices* lat, const gh_batch* b, double* out_soft /*[U, n_end]*/);
+int gh_wordstream_create_soft(gh_ctx* ctx, const gh_lattices* lat, int64_t n_streams, gh_wordstream** out);
+int gh_wordstream_result_soft(gh_ctx* ctx, gh_wordstream* ws, int64_t n, const int64_t* ids /*[n] or NULL*/,
+                              double* soft /*[n, n_end]*/);
+
 /* ------------------------------------------------ streaming front-end: audio chunks in, final feature frames out
  * gh_batch_create_from_pcm(mode 1) for n_streams live utterances whose int16 audio arrives in pieces of any size: a push
  * returns exactly the frames [cepstra | delta | delta-delta] (39 columns) that have become final.

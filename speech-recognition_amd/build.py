@@ -32,7 +32,9 @@ EXTRA = {"gh_loglik_mfma.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"],
          # the running normalisation is defined operation by operation: numpy scalars round the same
          "gh_norm_running.hip": ["-ffp-contract=off"],
          # the loop-form forward-backward writes every sum the way the host statement of the word posteriors does
-         "gh_fb_loop.hip": ["-ffp-contract=off"]}
+         "gh_fb_loop.hip": ["-ffp-contract=off"],
+         # ... and so does the forward sweep of the word chains
+         "gh_forward_chain.hip": ["-ffp-contract=off"]}
 
 
 def _sources():

@@ -17,35 +17,9 @@
 // ONE FRAME: a stream that holds exactly one frame shows column 0 of every longer decode.  The reference's one-frame
 // decode is something else (its column wrap, decode.py:109-114, lets a row read the row above it in the same column)
 // and is not reproduced; from two frames on the result is the whole decode of the frames so far.
-#include "gh_online.h"
+#include "gh_wordstream.h"
 #include "gh_viterbi.h"
 #include "gh_wave.h"
-
-struct gh_wordstream {
-    gh_ctx* ctx;
-    const gh_lattices* lat;        // must outlive the session
-    int64_t n_streams;
-    int N, C;                      // states per chain, chains per stream
-    void* d_arena;
-    double* d_state;               // [n_streams][N][C]
-    gh_online_slot* d_slots;       // [n_streams]: the table of the push in flight
-    gh_online_slot* h_slots;       // page-locked staging of the same size
-    hipEvent_t copied;             // behind the last upload of h_slots
-    bool copy_pending;
-    std::vector<int64_t> frames;   // [n_streams] frames taken so far
-    std::vector<uint8_t> seen;     // [n_streams] scratch of the duplicate check
-};
-
-struct gh_wordstream_args {
-    const double *cost0, *cost1, *cost2;   // [R] arc costs of the chain form (gh_chain_args)
-    const uint8_t* row_info;               // [R] bit 2: start row
-    const int32_t* row_state;              // [R]
-    const void* nll;                       // [rows, S] likelihoods of the batch
-    int S, C;
-    const gh_online_slot* slots;
-    int64_t n_slots;
-    double* state;                         // [n_streams][N][C]
-};
 
 namespace {
 
@@ -230,23 +204,38 @@ int launch_wordstream(gh_ctx* ctx, const gh_wordstream_args& a, int N, bool skip
 }  // namespace
 
 // --------------------------------------------------------------------------------------------------------------- C ABI
-extern "C" int gh_wordstream_create(gh_ctx* ctx, const gh_lattices* lat, int64_t n_streams, gh_wordstream** out) {
-    GH_REQUIRE(ctx && lat && out, "gh_wordstream_create: NULL argument");
+void gh_wordchain_refusal(const gh_lattices* lat, char* why, size_t n) {
+    why[0] = 0;
+    if (lat->deferred_src) snprintf(why, n, "a handle made from transcripts");
+    else if (lat->L != 1) snprintf(why, n, "several graphs (one graph of stacked word chains serves all streams)");
+    else if (lat->beam > 0) snprintf(why, n, "a rank beam is set on the graph");
+    else if (lat->bigram_ok || lat->bigram_wide_ok) snprintf(why, n, "a bigram grammar");
+    else if (lat->layers_ok && lat->h_layers.loop) snprintf(why, n, "a word-loop grammar");
+    else if (lat->layers_ok) snprintf(why, n, "a K-layer word lattice");
+    else if (!lat->chain_ok) snprintf(why, n, "a graph that is not made of left-to-right chains");
+    else if (lat->chain_unit <= 0) snprintf(why, n, "chains of unequal length");
+    else if (!gh_chain_lanes_ok(lat->chain_unit)) snprintf(why, n, "chains of %d states", lat->chain_unit);
+    else if (!lat->chain_consecutive) snprintf(why, n, "chains whose states are not consecutive");
+}
+
+gh_wordstream_args gh_wordchain_args(const gh_lattices* lat, const gh_batch* b) {
+    gh_wordstream_args a;
+    memset(&a, 0, sizeof a);
+    a.cost0 = lat->d_ch_cost0; a.cost1 = lat->d_ch_cost1; a.cost2 = lat->d_ch_cost2; a.row_info = lat->d_ch_info;
+    a.row_state = lat->d_row_state; a.nll = b->nll; a.S = b->nll_S; a.C = lat->lat[0].R / lat->chain_unit;
+    return a;
+}
+
+// gh_wordstream_create and gh_wordstream_create_soft: a soft session carries a second column of the same size
+static int wordstream_create(gh_ctx* ctx, const gh_lattices* lat, int64_t n_streams, gh_wordstream** out, bool soft, const char* who) {
+    GH_REQUIRE(ctx && lat && out, "%s: NULL argument", who);
     *out = nullptr;
-    GH_REQUIRE(n_streams >= 1 && n_streams <= 0x7fffffff, "gh_wordstream_create: n_streams=%lld", (long long)n_streams);
-    char why[96] = "";
-    if (lat->L != 1 || lat->deferred_src) snprintf(why, sizeof why, "several graphs (one graph of stacked word chains serves all streams)");
-    else if (lat->beam > 0) snprintf(why, sizeof why, "a rank beam is set on the graph");
-    else if (lat->bigram_ok) snprintf(why, sizeof why, "a bigram grammar");
-    else if (lat->layers_ok && lat->h_layers.loop) snprintf(why, sizeof why, "a word-loop grammar");
-    else if (lat->layers_ok) snprintf(why, sizeof why, "a K-layer word lattice");
-    else if (!lat->chain_ok) snprintf(why, sizeof why, "a graph that is not made of left-to-right chains");
-    else if (lat->chain_unit <= 0) snprintf(why, sizeof why, "chains of unequal length");
-    else if (!gh_chain_lanes_ok(lat->chain_unit)) snprintf(why, sizeof why, "chains of %d states", lat->chain_unit);
-    else if (!lat->chain_consecutive) snprintf(why, sizeof why, "chains whose states are not consecutive");
+    GH_REQUIRE(n_streams >= 1 && n_streams <= 0x7fffffff, "%s: n_streams=%lld", who, (long long)n_streams);
+    char why[96];
+    gh_wordchain_refusal(lat, why, sizeof why);
     if (why[0]) {
-        gh_set_error("gh_wordstream_create: online word recognition takes one graph of word chains of equal length (1 .. 8 consecutive "
-                     "states each), not %s", why);
+        gh_set_error("%s: online word recognition takes one graph of word chains of equal length (1 .. 8 consecutive "
+                     "states each), not %s", who, why);
         return GH_ERR_UNSUPPORTED;
     }
     GH_HIP(hipSetDevice(ctx->device));
@@ -257,20 +246,31 @@ extern "C" int gh_wordstream_create(gh_ctx* ctx, const gh_lattices* lat, int64_t
     ws->frames.assign((size_t)n_streams, 0);
     ws->seen.assign((size_t)n_streams, 0);
     auto pad = [](size_t b) { return (b + 255) & ~size_t(255); };
-    const size_t b_state = pad((size_t)n_streams * ws->N * ws->C * sizeof(double)), b_slots = pad((size_t)n_streams * sizeof(gh_online_slot));
+    const size_t b_col = pad((size_t)n_streams * ws->N * ws->C * sizeof(double)), b_state = (soft ? 2 : 1) * b_col;
+    const size_t b_slots = pad((size_t)n_streams * sizeof(gh_online_slot));
     hipError_t e = hipMalloc(&ws->d_arena, b_state + b_slots);
     if (e == hipSuccess) e = hipHostMalloc((void**)&ws->h_slots, b_slots, hipHostMallocDefault);
     if (e == hipSuccess) e = hipEventCreateWithFlags(&ws->copied, hipEventDisableTiming);
     if (e != hipSuccess) {
-        gh_set_error("gh_wordstream_create: %lld streams (%zu bytes): %s", (long long)n_streams, b_state + b_slots, hipGetErrorString(e));
+        gh_set_error("%s: %lld streams (%zu bytes): %s", who, (long long)n_streams, b_state + b_slots, hipGetErrorString(e));
         gh_wordstream_destroy(ws);
         return e == hipErrorOutOfMemory ? GH_ERR_NOMEM : GH_ERR_HIP;
     }
     char* p = static_cast<char*>(ws->d_arena);
-    ws->d_state = reinterpret_cast<double*>(p); p += b_state;
+    ws->d_state = reinterpret_cast<double*>(p);
+    ws->d_alpha = soft ? reinterpret_cast<double*>(p + b_col) : nullptr;
+    p += b_state;
     ws->d_slots = reinterpret_cast<gh_online_slot*>(p);
     *out = ws;
     return GH_OK;
+}
+
+extern "C" int gh_wordstream_create(gh_ctx* ctx, const gh_lattices* lat, int64_t n_streams, gh_wordstream** out) {
+    return wordstream_create(ctx, lat, n_streams, out, false, "gh_wordstream_create");
+}
+
+extern "C" int gh_wordstream_create_soft(gh_ctx* ctx, const gh_lattices* lat, int64_t n_streams, gh_wordstream** out) {
+    return wordstream_create(ctx, lat, n_streams, out, true, "gh_wordstream_create_soft");
 }
 
 extern "C" void gh_wordstream_destroy(gh_wordstream* ws) {
@@ -350,13 +350,15 @@ extern "C" int gh_wordstream_push(gh_ctx* ctx, gh_wordstream* ws, const gh_batch
     GH_HIP(hipEventRecord(ws->copied, ctx->stream));
     ws->copy_pending = true;
     const gh_lattices* lat = ws->lat;
-    gh_wordstream_args a;
-    memset(&a, 0, sizeof a);
-    a.cost0 = lat->d_ch_cost0; a.cost1 = lat->d_ch_cost1; a.cost2 = lat->d_ch_cost2; a.row_info = lat->d_ch_info;
-    a.row_state = lat->d_row_state; a.nll = b->nll; a.S = b->nll_S; a.C = ws->C;
+    gh_wordstream_args a = gh_wordchain_args(lat, b);
     a.slots = ws->d_slots; a.n_slots = (int64_t)slots.size(); a.state = ws->d_state;
-    const int rc = launch_wordstream(ctx, a, ws->N, lat->chain_skip, b->dtype == GH_F64);
+    int rc = launch_wordstream(ctx, a, ws->N, lat->chain_skip, b->dtype == GH_F64);
     if (rc) return rc;
+    if (ws->d_alpha) {                              // a soft session: the log-alpha column on the same slot table
+        a.state = ws->d_alpha;
+        rc = gh_launch_forward_chain(ctx, a, ws->N, lat->chain_skip, b->dtype == GH_F64);
+        if (rc) return rc;
+    }
     for (const gh_online_slot& s : slots) ws->frames[(size_t)s.stream] += s.count;
     return GH_OK;
 }

@@ -196,6 +196,9 @@ SIGNATURES = {
     "gh_wordstream_frames": (C.c_int, [C.c_void_p, _c_i64p]),
     "gh_wordstream_push": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, _c_i64p, _c_i64p, _c_i64p]),
     "gh_wordstream_result": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, _c_i64p, _c_f64p, _c_i32p]),
+    "gh_chain_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, _c_f64p]),
+    "gh_wordstream_create_soft": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_void_p)]),
+    "gh_wordstream_result_soft": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, _c_i64p, _c_f64p]),
     "gh_stream_create": (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_double, C.c_double, C.c_double, C.c_double, C.c_int64, C.c_int,
                                    _c_f64p, _c_f64p, C.POINTER(C.c_void_p)]),
     "gh_stream_destroy": (None, [C.c_void_p]),
@@ -1520,6 +1523,18 @@ class Lattices:
             out["confidence"] = [conf[off[u]:off[u + 1]] for u in range(U)]
         return out
 
+    def chain_forward(self, batch):
+        """Forward scores of ONE graph of stacked word chains (gh_chain_forward): soft [U, n_end], -log P(x_u | chain) summed
+        over all paths, +inf where there is none.  The batch needs resident likelihoods; any graph a `WordStreamSession`
+        does not take raises `Unsupported`."""
+        lib = self.ctx.lib
+        soft = np.empty((batch.U, int(self.n_end[0])), dtype=np.float64)
+        rc = lib.gh_chain_forward(self.ctx.h, self.h, batch.h, _ptr(soft, _c_f64p))
+        if rc == GH_ERR_UNSUPPORTED:
+            raise Unsupported(lib.gh_last_error().decode("utf-8", "replace"))
+        _check(lib, rc)
+        return soft
+
     def close(self):
         if getattr(self, "h", None):
             if getattr(self.ctx, "h", None):  # a handle must not outlive its context (interpreter shutdown order)
@@ -1831,13 +1846,17 @@ class WordStreamSession:
     advances streams by chunks of resident likelihoods; `result` is, from two frames on, bitwise the end costs of the
     one-shot decode of the frames a stream has taken (one frame: column 0 of every longer decode).  `lat` (a `Lattices`
     with one graph whose chains all have the same 1 .. 8 consecutive states) must outlive the session; any other graph
-    raises `Unsupported`."""
+    raises `Unsupported`.  soft=True (gh_wordstream_create_soft): the session carries the log-alpha column as well, every
+    push runs the forward sweep behind the Viterbi sweep, and `result_soft` is, from one frame on, bitwise
+    `Lattices.chain_forward` of the frames a stream has taken."""
 
-    def __init__(self, ctx, lat, n_streams):
+    def __init__(self, ctx, lat, n_streams, soft=False):
         self.ctx, self.lat = ctx, lat
         self.n_streams = int(n_streams)
+        self.soft = bool(soft)
         h = C.c_void_p()
-        rc = ctx.lib.gh_wordstream_create(ctx.h, lat.h, self.n_streams, C.byref(h))
+        create = ctx.lib.gh_wordstream_create_soft if self.soft else ctx.lib.gh_wordstream_create
+        rc = create(ctx.h, lat.h, self.n_streams, C.byref(h))
         if rc == GH_ERR_UNSUPPORTED:
             raise Unsupported(ctx.lib.gh_last_error().decode("utf-8", "replace"))
         _check(ctx.lib, rc)
@@ -1878,6 +1897,14 @@ class WordStreamSession:
         _check(self.ctx.lib, self.ctx.lib.gh_wordstream_result(self.ctx.h, self.h, n, _ptr(ids, _c_i64p), _ptr(costs, _c_f64p),
                                                                _ptr(best, _c_i32p)))
         return dict(costs=costs, best=best, frames=T)
+
+    def result_soft(self, ids=None):
+        """soft [n, W]: -log P of the frames a stream has taken under every word, summed over all paths (+inf: no path, or
+        no frames), for the streams `ids` (None: all).  A session made without soft=True is refused by the library."""
+        ids = np.arange(self.n_streams, dtype=np.int64) if ids is None else self._i64(ids)
+        soft = np.empty((len(ids), self.n_end), dtype=np.float64)
+        _check(self.ctx.lib, self.ctx.lib.gh_wordstream_result_soft(self.ctx.h, self.h, len(ids), _ptr(ids, _c_i64p), _ptr(soft, _c_f64p)))
+        return soft
 
     def close(self):
         if getattr(self, "h", None):

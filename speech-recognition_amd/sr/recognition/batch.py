@@ -14,7 +14,7 @@ from . import _pack
 from .continuous_speech import packed_lattice, packed_loop_lattice, packed_bigram_lattice
 
 __all__ = ["IsolatedWordRecognizer", "ContinuousDecoder", "OnlineDecoder", "OnlineWordRecognizer", "InFlight", "path_to_words", "path_to_word_times", "word_spans",
-           "sequence_report", "train_words"]
+           "sequence_report", "train_words", "vocabulary_posteriors"]
 
 
 def _stack_models(ctx, models):
@@ -209,12 +209,79 @@ def _train_words_by_segments(templates_by_word, models, n_segments, n_gaussians,
     return models
 
 
+def _posterior_args(W, scale, log_prior):
+    """(scale, log_prior [W]) checked: scale finite and > 0; log_prior None (zeros) or W values, each finite or -inf."""
+    try:
+        scale = float(scale)
+    except (TypeError, ValueError):
+        raise ValueError("scale must be a finite number > 0")
+    if not (np.isfinite(scale) and scale > 0.0):
+        raise ValueError("scale must be a finite number > 0, not %r" % scale)
+    if log_prior is None:
+        return scale, np.zeros(W, dtype=np.float64)
+    lp = np.asarray(log_prior, dtype=np.float64)
+    if lp.shape != (W,):
+        raise ValueError("log_prior must hold one value per word (%d), not shape %r" % (W, lp.shape))
+    if np.any(np.isnan(lp)) or np.any(np.isposinf(lp)):
+        raise ValueError("every log_prior must be finite or -inf")
+    return scale, lp
+
+
+def vocabulary_posteriors(soft, scale=1.0, log_prior=None):
+    """The posterior over the vocabulary from soft costs [U, W] (soft[u, w] = -log P(x_u | w), +inf: no path): with
+    z[w] = scale * soft[u, w] - log_prior[w] and m = min_w z, p[w] = exp(m - z[w]) and post[u, w] = p[w] / sum_w p, the sum
+    taken in ascending w.  scale < 1 flattens the over-sharp acoustic scores; a word with log_prior -inf gets 0; a row
+    whose z are all +inf is a row of zeros.  The ONE statement of the softmax: the one-shot and the online recogniser both
+    call it, which makes their posteriors equal where their soft costs are."""
+    soft = np.asarray(soft, dtype=np.float64)
+    if soft.ndim != 2:
+        raise ValueError("soft costs are a [U, W] matrix")
+    U, W = soft.shape
+    scale, lp = _posterior_args(W, scale, log_prior)
+    post = np.zeros((U, W), dtype=np.float64)
+    if U == 0 or W == 0:
+        return post
+    with np.errstate(invalid="ignore"):
+        z = scale * soft - lp[None, :]
+    z[np.isnan(z)] = np.inf                               # (no path and no prior: still no word)
+    m = z.min(axis=1)
+    live = np.flatnonzero(np.isfinite(m))
+    if not len(live):
+        return post
+    p = np.exp(m[live, None] - z[live])
+    s = np.zeros(len(live), dtype=np.float64)
+    for w in range(W):                                    # ascending w: the order is part of the definition
+        s = s + p[:, w]
+    post[live] = p / s[:, None]
+    return post
+
+
+def _posterior_info(soft, words, scale, log_prior):
+    """The four keys a recogniser adds: soft_costs, posteriors, confidence = post[u, words[u]] (0.0 for a zero row or no
+    word) and soft_words, the first arg-max of every row (-1 for a zero row)."""
+    post = vocabulary_posteriors(soft, scale, log_prior)
+    words = np.asarray(words, dtype=np.int64)
+    U = len(words)
+    any_ = post.any(axis=1) if post.shape[1] else np.zeros(U, dtype=bool)
+    soft_words = np.where(any_, np.argmax(post, axis=1) if post.shape[1] else 0, -1).astype(np.int64)
+    conf = np.zeros(U, dtype=np.float64)
+    ok = words >= 0
+    conf[ok] = post[np.flatnonzero(ok), words[ok]]
+    return dict(soft_costs=soft, posteriors=post, confidence=conf, soft_words=soft_words)
+
+
 class IsolatedWordRecognizer:
     """Scores every utterance against every word model and returns the arg-min word
     (core.py:82-87: `costs = [m.evaluate(x) for m in models]; argmin`).
 
     The W word chains are stacked into one graph (W start rows, W end rows), so one
-    gh_loglik + one gh_viterbi launch replaces U x W calls of HMM.evaluate."""
+    gh_loglik + one gh_viterbi launch replaces U x W calls of HMM.evaluate.
+
+    POSTERIORS (not in the reference).  `soft_costs` gives -log P(x | w) summed over all paths of every
+    word (the forward sweep, gh_chain_forward), `posteriors` the softmax of them over the vocabulary
+    (`vocabulary_posteriors`), and `recognize(want_posteriors=True)` the confidence of the arg-min word, with
+    `min_confidence=` as a rejection threshold (word -1).  Single-Gaussian recognisers (one Gaussian per state: scored
+    inside the fused sweep, no likelihood matrix exists) raise `_hip.Unsupported`."""
 
     def __init__(self, models, device=None, dtype=np.float64, ctx=None):
         self.ctx = ctx if ctx is not None else _hip.default_context(device)
@@ -246,14 +313,52 @@ class IsolatedWordRecognizer:
             r = self.lat.viterbi(batch, want_path=False)
         return r["end_cost_flat"].reshape(batch.U, self.W)
 
-    def recognize(self, xs):
-        """xs: list of [T_u, D] arrays -> (words [U], costs [U, W])."""
+    def _refuse_single(self, what):
+        if self.gmm.M == 1:
+            raise _hip.Unsupported("%s need the likelihood matrix: a recogniser with one Gaussian per state is scored inside the "
+                                   "fused sweep, which has no forward form" % what)
+
+    def soft_costs(self, batch):
+        """[U, W] matrix of -log P(x_u | word w), summed over ALL paths of the word's chain (the forward sweep on the
+        resident likelihood matrix, computed here when the batch holds none); +inf where a word has no path."""
+        self._refuse_single("soft costs")
+        if batch.S is None:
+            batch.loglik(self.gmm, fetch=False)
+        return self.lat.chain_forward(batch).reshape(batch.U, self.W)
+
+    def posteriors(self, batch, scale=1.0, log_prior=None):
+        """(post [U, W], soft [U, W]): `vocabulary_posteriors` of `soft_costs(batch)`."""
+        self._refuse_single("posteriors")
+        _posterior_args(self.W, scale, log_prior)
+        soft = self.soft_costs(batch)
+        return vocabulary_posteriors(soft, scale, log_prior), soft
+
+    def recognize(self, xs, want_posteriors=False, scale=1.0, log_prior=None, min_confidence=None):
+        """xs: list of [T_u, D] arrays -> (words [U], costs [U, W]).  want_posteriors=True: (words, costs, info) with info =
+        dict(soft_costs [U, W], posteriors [U, W], confidence [U] = posteriors[u, words[u]], soft_words [U]: the first
+        arg-max of every row of the posteriors, -1 for a row of zeros); `words` stays the Viterbi arg-min.  min_confidence=c
+        (needs want_posteriors) sets words[u] = -1 where the confidence is below c."""
+        if not want_posteriors:
+            if min_confidence is not None:
+                raise ValueError("min_confidence needs want_posteriors=True")
+        else:
+            self._refuse_single("posteriors")
+            _posterior_args(self.W, scale, log_prior)
+            if min_confidence is not None and np.isnan(float(min_confidence)):
+                raise ValueError("min_confidence must be a number")
         batch = _hip.Batch(self.ctx, xs, dtype=self.dtype)
         try:
             c = self.costs(batch)
+            soft = self.soft_costs(batch) if want_posteriors else None
         finally:
             batch.close()
-        return np.argmin(c, axis=1), c
+        words = np.argmin(c, axis=1)
+        if not want_posteriors:
+            return words, c
+        info = _posterior_info(soft, words, scale, log_prior)
+        if min_confidence is not None:
+            words = np.where(info["confidence"] < float(min_confidence), -1, words)
+        return words, c, info
 
     def accuracy(self, xs, words, verbose=False):
         """The report of `sr/core.py:test` (core.py:63-94) as a call: fraction of utterances whose cheapest model is
@@ -267,12 +372,13 @@ class IsolatedWordRecognizer:
         return float(np.sum(got == words)) / len(words), got
 
 
-    def online(self, n_streams, frontend=None, endpointer=None):
+    def online(self, n_streams, frontend=None, endpointer=None, soft=False, scale=1.0, log_prior=None):
         """An `OnlineWordRecognizer` of `n_streams` live utterances sharing this recogniser's packed mixtures and graph
         (single-Gaussian word models raise `_hip.Unsupported`).  frontend / endpointer: as `ContinuousDecoder.online` -- a
         `sr.feature.StreamingFrontend` (`push_audio`) and a `sr.audio_capture.StreamingEndpointer` (`push_recording`) of
-        the same context and `n_streams`."""
-        return OnlineWordRecognizer(self, n_streams, frontend, endpointer)
+        the same context and `n_streams`.  soft=True: the streams carry the forward column too, and `result` / `finish` /
+        `push_recording` report posteriors and a confidence under `scale` and `log_prior` (as `recognize`)."""
+        return OnlineWordRecognizer(self, n_streams, frontend, endpointer, soft=soft, scale=scale, log_prior=log_prior)
 
 
 def sequence_report(decoded, labels, verbose=False):
@@ -1170,29 +1276,42 @@ class OnlineWordRecognizer(_OnlineStreams):
     AUDIO and RECORDINGS work as in `OnlineDecoder`: with `frontend=` the streams take int16 PCM (`push_audio`), with
     `endpointer=` as well whole recordings, and `push_recording` returns the utterances that ended with the call as dicts
     `stream`, `word`, `costs` [W], `begin`, `stop` (recording sample coordinates) and `open`.  With an endpointer `reset`
-    starts a new RECORDING (all three objects), `finish` a new utterance (recogniser and front-end only)."""
+    starts a new RECORDING (all three objects), `finish` a new utterance (recogniser and front-end only).
+
+    CONFIDENCE.  `online(..., soft=True, scale=, log_prior=)`: every stream carries one more column, the log-alphas of the
+    forward sweep, and `result` / `finish` add `soft_costs`, `posteriors`, `confidence` and `soft_words` to their info dict
+    (as `recognize(want_posteriors=True)`; `push_recording` dicts gain `confidence`).  From ONE frame on the soft costs are
+    bitwise `soft_costs` of the frames so far on the same likelihoods, and the posteriors come from the same
+    `vocabulary_posteriors`.  A stream without frames: soft costs +inf, a row of zeros, confidence 0.0."""
 
     _what = "recogniser"
 
-    def __init__(self, recognizer, n_streams, frontend=None, endpointer=None):
+    def __init__(self, recognizer, n_streams, frontend=None, endpointer=None, soft=False, scale=1.0, log_prior=None):
         if recognizer.single:
             raise _hip.Unsupported("online word recognition takes mixture word models: single-Gaussian models (use_gmm=False) are "
                                    "scored inside the fused sweep, which has no carried form")
         if int(n_streams) < 1:
             raise ValueError("n_streams must be positive")
+        self.soft = bool(soft)
+        if self.soft:
+            self._scale, self._log_prior = _posterior_args(recognizer.W, scale, log_prior)
         self._attach(recognizer.ctx, recognizer.dtype, recognizer.gmm, n_streams, frontend, endpointer)
         self.recognizer = recognizer
-        self.session = _hip.WordStreamSession(recognizer.ctx, recognizer.lat, self.n_streams)
+        self.session = _hip.WordStreamSession(recognizer.ctx, recognizer.lat, self.n_streams, **({"soft": True} if self.soft else {}))
 
     def _room(self, ids, counts):
         pass                                              # (a stream holds one column: it takes any number of frames)
 
     def result(self, ids=None):
         """(words int64 [n], dict(costs [n, W], frames [n])) of the streams `ids` (None: all) for the frames pushed so far:
-        what `recognize` returns for those frames as whole utterances (a stream without frames: word -1, costs +inf)."""
+        what `recognize` returns for those frames as whole utterances (a stream without frames: word -1, costs +inf).
+        A soft recogniser adds soft_costs, posteriors, confidence and soft_words."""
         ids = np.arange(self.n_streams, dtype=np.int64) if ids is None else self._ids(ids, distinct=False)
         r = self.session.result(ids)
-        return np.asarray(r["best"], dtype=np.int64), dict(costs=r["costs"], frames=r["frames"])
+        words, info = np.asarray(r["best"], dtype=np.int64), dict(costs=r["costs"], frames=r["frames"])
+        if self.soft:                                     # soft_costs, posteriors, confidence, soft_words: as `recognize`
+            info.update(_posterior_info(self.session.result_soft(ids), words, self._scale, self._log_prior))
+        return words, info
 
     def push_recording(self, ids, chunks, end=None):
         """Stream ids[i] takes the int16 samples chunks[i] of its RECORDING through the recogniser's `StreamingEndpointer`
@@ -1206,8 +1325,10 @@ class OnlineWordRecognizer(_OnlineStreams):
             if len(done):
                 words, info = self.result(done)
                 self._reset_utterance(done)
-                for k, w, c, rg in zip(done, words, info["costs"], ranges):
+                for i, (k, w, c, rg) in enumerate(zip(done, words, info["costs"], ranges)):
                     out.append(dict(stream=int(k), word=int(w), costs=c, begin=int(rg[0]), stop=int(rg[1]), open=bool(rg[2])))
+                    if self.soft:
+                        out[-1]["confidence"] = float(info["confidence"][i])
         return out
 
     def finish(self, ids):
