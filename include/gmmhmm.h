@@ -532,6 +532,27 @@ int gh_word_posteriors(gh_ctx* ctx, const gh_lattices* lat, gh_batch* b,
                        const int32_t* n_labels /*[U]*/,        /* all four NULL: no confidences */
                        double* out_conf /*laid out like labels, or NULL*/);
 
+/* ------------------------- word posteriors and per-word confidence (bigram form)
+ * NOT in the reference, like gh_word_posteriors; pinned by brute-force path enumeration in the tests.
+ * The same results for a handle whose graph 0 is in BIGRAM form, narrow or wide (the word loop with word-to-word costs:
+ * W words of n states, 2 <= W <= 64, 2 <= n <= 8; rows start | states 1..n-1 of every word | W entry rows | W state-0
+ * rows), i.e. for a decode under a language model.  Four utterances per block, one wave each, lane = word.
+ * DEFINITION.  In the notation above, with L_u the entry row of word u, last_w the last state of word w and
+ * B[w, u] = trans[L_u, last_w]: a path's WORD AT FRAME t is the word of the LAST emitting cell it visits in column t, and
+ *     q_t(w) = sum_s gamma_t(w, s)  -  sum_u exp( la[last_w, t] - B[w, u] + lb[L_u, t] - logP )
+ * (the subtracted sum: leaving word w through ANY entry row in column t).  Rows sum to 1, a result below 0 by rounding is
+ * stored as 0, log P = -inf gives zero rows and confidences of 0.0.  Forbidden pairs and starts (+inf) are ordinary input.
+ * Arguments, span table, confidences, scratch and launches exactly as for gh_word_posteriors; a label is a word of the
+ * bigram form, 0 <= label < W.
+ * Everything is checked before anything is enqueued.  GH_ERR_UNSUPPORTED, with a sentence per case: a loop-form handle
+ * (gh_word_posteriors takes it), a K-layer lattice, transcript graphs, a generic graph, words of 12 or 16 states, a rank
+ * beam on the handle.  GH_ERR_INVALID: as for gh_word_posteriors. */
+int gh_word_posteriors_bigram(gh_ctx* ctx, const gh_lattices* lat, gh_batch* b,
+                              double* out_logp /*[U] or NULL*/, double* out_post /*[N, W] or NULL*/,
+                              const int32_t* labels, const int32_t* begins, const int64_t* label_off /*[U+1]*/,
+                              const int32_t* n_labels /*[U]*/,        /* all four NULL: no confidences */
+                              double* out_conf /*laid out like labels, or NULL*/);
+
 /* ------------------------------------ Baum-Welch (soft) sufficient statistics
  * After gh_forward_backward(want_occ = 1): for every frame n and state s,
  *   r_nsm = occ[n,s] * w_sm pdf_sm(x_n) / sum_m' w_sm' pdf_sm'(x_n)

@@ -33,6 +33,8 @@ EXTRA = {"gh_loglik_mfma.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"],
          "gh_norm_running.hip": ["-ffp-contract=off"],
          # the loop-form forward-backward writes every sum the way the host statement of the word posteriors does
          "gh_fb_loop.hip": ["-ffp-contract=off"],
+         # ... and its bigram-form twin
+         "gh_fb_bigram.hip": ["-ffp-contract=off"],
          # ... and so does the forward sweep of the word chains
          "gh_forward_chain.hip": ["-ffp-contract=off"]}
 

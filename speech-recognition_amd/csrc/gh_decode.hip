@@ -1003,6 +1003,10 @@ extern "C" int gh_forward_backward(gh_ctx* ctx, const gh_lattices* lat, gh_batch
 }
 
 // ------------------------------------------- word posteriors (loop form)
+static int word_posteriors_run(const char* who, bool bigram, gh_ctx* ctx, const gh_lattices* lat, gh_batch* b, double* out_logp,
+                               double* out_post, const int32_t* labels, const int32_t* begins, const int64_t* label_off,
+                               const int32_t* n_labels, double* out_conf);
+
 extern "C" int gh_word_posteriors(gh_ctx* ctx, const gh_lattices* lat, gh_batch* b, double* out_logp, double* out_post,
                                   const int32_t* labels, const int32_t* begins, const int64_t* label_off, const int32_t* n_labels,
                                   double* out_conf) {
@@ -1025,29 +1029,63 @@ extern "C" int gh_word_posteriors(gh_ctx* ctx, const gh_lattices* lat, gh_batch*
         gh_set_error("gh_word_posteriors: a rank beam (%d) is set on the handle: posteriors are sums over all paths, not over a pruned decode", lat->beam);
         return GH_ERR_UNSUPPORTED;
     }
-    GH_REQUIRE(b->nll || b->N == 0, "gh_word_posteriors: gh_loglik has not been run on this batch");
+    return word_posteriors_run("gh_word_posteriors", false, ctx, lat, b, out_logp, out_post, labels, begins, label_off, n_labels, out_conf);
+}
+
+// ------------------------------------------- word posteriors (bigram form, narrow and wide)
+extern "C" int gh_word_posteriors_bigram(gh_ctx* ctx, const gh_lattices* lat, gh_batch* b, double* out_logp, double* out_post,
+                                         const int32_t* labels, const int32_t* begins, const int64_t* label_off, const int32_t* n_labels,
+                                         double* out_conf) {
+    GH_REQUIRE(ctx && lat && b, "gh_word_posteriors_bigram: NULL argument");
+    // what the handle is, before anything else: every refusal has a sentence of its own
+    if (!(lat->bigram_ok || lat->bigram_wide_ok)) {
+        if (lat->layers_ok && lat->h_layers.loop == 1) gh_set_error("gh_word_posteriors_bigram: the graph is in loop form (one loop row, no word-to-word costs): gh_word_posteriors takes it");
+        else if (lat->layers_ok) gh_set_error("gh_word_posteriors_bigram: the graph is a K-layer lattice (%d layers): word posteriors are built for the loop and the bigram form only", lat->h_layers.K);
+        else if (lat->seq_ok || lat->deferred_src) gh_set_error("gh_word_posteriors_bigram: the handle holds transcript graphs (sequence form): word posteriors are built for the loop and the bigram form only");
+        else gh_set_error("gh_word_posteriors_bigram: graph 0 is not in bigram form (generic graph): word posteriors are built for the loop and the bigram form only");
+        return GH_ERR_UNSUPPORTED;
+    }
+    if (lat->h_layers.N > 8) {
+        gh_set_error("gh_word_posteriors_bigram: words of %d states: the bigram-form forward-backward is built for 2 .. 8 states per word", lat->h_layers.N);
+        return GH_ERR_UNSUPPORTED;
+    }
+    if (lat->beam) {
+        gh_set_error("gh_word_posteriors_bigram: a rank beam (%d) is set on the handle: posteriors are sums over all paths, not over a pruned decode", lat->beam);
+        return GH_ERR_UNSUPPORTED;
+    }
+    GH_REQUIRE(lat->bigram_ok || lat->d_bigram_wide, "gh_word_posteriors_bigram: internal: wide bigram form without its cost table");
+    return word_posteriors_run("gh_word_posteriors_bigram", true, ctx, lat, b, out_logp, out_post, labels, begins, label_off, n_labels, out_conf);
+}
+
+// What the two entry points share once the handle's form is settled: the checks of the batch and of the span table
+// (everything before anything is enqueued), alpha scratch cut into launches, the sweep, the copies back.
+static int word_posteriors_run(const char* who, bool bigram, gh_ctx* ctx, const gh_lattices* lat, gh_batch* b, double* out_logp,
+                               double* out_post, const int32_t* labels, const int32_t* begins, const int64_t* label_off,
+                               const int32_t* n_labels, double* out_conf) {
+    const gh_layerform& f = lat->h_layers;
+    GH_REQUIRE(b->nll || b->N == 0, "%s: gh_loglik has not been run on this batch", who);
     const int64_t U = b->U;
     const int W = f.W, N = f.N;
     const bool spans = labels || begins || label_off || n_labels;
     GH_REQUIRE(!spans || (labels && begins && label_off && n_labels),
-               "gh_word_posteriors: the span table needs labels, begins, label_off and n_labels (all four, or none)");
-    GH_REQUIRE(!out_conf || spans, "gh_word_posteriors: out_conf needs the span table");
+               "%s: the span table needs labels, begins, label_off and n_labels (all four, or none)", who);
+    GH_REQUIRE(!out_conf || spans, "%s: out_conf needs the span table", who);
     if (U == 0) { ctx->last_chunks = 0; return GH_OK; }
     const int S = b->nll_S;
-    GH_REQUIRE(lat->lat[0].max_state < S, "gh_word_posteriors: the graph uses state %d but the model has %d", lat->lat[0].max_state, S);
+    GH_REQUIRE(lat->lat[0].max_state < S, "%s: the graph uses state %d but the model has %d", who, lat->lat[0].max_state, S);
     if (spans) {
-        GH_REQUIRE(label_off[0] >= 0, "gh_word_posteriors: label_off[0] = %lld", (long long)label_off[0]);
+        GH_REQUIRE(label_off[0] >= 0, "%s: label_off[0] = %lld", who, (long long)label_off[0]);
         for (int64_t u = 0; u < U; ++u) {
             const int64_t cap = label_off[u + 1] - label_off[u], T = b->offsets[u + 1] - b->offsets[u];
-            GH_REQUIRE(cap >= 0, "gh_word_posteriors: label_off decreases at utterance %lld", (long long)u);
-            GH_REQUIRE(n_labels[u] >= 0 && n_labels[u] <= cap, "gh_word_posteriors: n_labels[%lld] = %d lies beyond the slot of %lld entries",
-                       (long long)u, n_labels[u], (long long)cap);
+            GH_REQUIRE(cap >= 0, "%s: label_off decreases at utterance %lld", who, (long long)u);
+            GH_REQUIRE(n_labels[u] >= 0 && n_labels[u] <= cap, "%s: n_labels[%lld] = %d lies beyond the slot of %lld entries",
+                       who, (long long)u, n_labels[u], (long long)cap);
             for (int k = 0; k < n_labels[u]; ++k) {
                 const int32_t l = labels[label_off[u] + k], bg = begins[label_off[u] + k];
-                GH_REQUIRE(l >= 0 && l < W, "gh_word_posteriors: utterance %lld, word %d: label %d outside [0, %d)", (long long)u, k, l, W);
-                GH_REQUIRE(bg >= 0 && bg < T, "gh_word_posteriors: utterance %lld, word %d: begin %d outside [0, %lld)", (long long)u, k, bg, (long long)T);
-                GH_REQUIRE(k == 0 || bg > begins[label_off[u] + k - 1], "gh_word_posteriors: utterance %lld, word %d: begins do not strictly increase (%d after %d)",
-                           (long long)u, k, bg, begins[label_off[u] + k - 1]);
+                GH_REQUIRE(l >= 0 && l < W, "%s: utterance %lld, word %d: label %d outside [0, %d)", who, (long long)u, k, l, W);
+                GH_REQUIRE(bg >= 0 && bg < T, "%s: utterance %lld, word %d: begin %d outside [0, %lld)", who, (long long)u, k, bg, (long long)T);
+                GH_REQUIRE(k == 0 || bg > begins[label_off[u] + k - 1], "%s: utterance %lld, word %d: begins do not strictly increase (%d after %d)",
+                           who, (long long)u, k, bg, begins[label_off[u] + k - 1]);
             }
         }
     }
@@ -1070,10 +1108,12 @@ extern "C" int gh_word_posteriors(gh_ctx* ctx, const gh_lattices* lat, gh_batch*
     const int64_t n_lab = spans ? label_off[U] : 0;
     int64_t *d_soff, *d_laboff = nullptr;
     int32_t *d_labels = nullptr, *d_begins = nullptr, *d_nlab = nullptr;
-    double *d_scratch, *d_logp, *d_post = nullptr, *d_conf = nullptr;
+    double *d_scratch, *d_logp, *d_post = nullptr, *d_conf = nullptr, *d_bg = nullptr;
+    const bool fill_bg = bigram && !lat->bigram_wide_ok;   // up to 16 words: the costs lie in gh_layerform::bg, 16 x 16
     Carver cv;
     cv.add(&d_soff, U); cv.add(&d_logp, U); cv.add(&d_scratch, smax);
     if (out_post) cv.add(&d_post, (size_t)b->N * W);
+    if (fill_bg) cv.add(&d_bg, (size_t)GH_LAYERS_MAXW * GH_LAYERS_MAXW);
     if (want_conf) {
         cv.add(&d_laboff, U + 1); cv.add(&d_nlab, U); cv.add(&d_labels, std::max<int64_t>(n_lab, 1)); cv.add(&d_begins, std::max<int64_t>(n_lab, 1));
         cv.add(&d_conf, std::max<int64_t>(n_lab, 1));
@@ -1097,8 +1137,16 @@ extern "C" int gh_word_posteriors(gh_ctx* ctx, const gh_lattices* lat, gh_batch*
     a.utt_off = b->d_offsets; a.perm = b->d_perm; a.alpha_scratch = d_scratch; a.scratch_off = d_soff; a.logp = d_logp;
     a.post = d_post;
     if (want_conf) { a.labels = d_labels; a.begins = d_begins; a.label_off = d_laboff; a.n_labels = d_nlab; a.conf = d_conf; }
+    // bigram form: ONE [64][64] table of word-to-word costs, whichever the handle holds -- the wide form's own, or the narrow
+    // form's 16 x 16 spread out on the device (+inf behind the words)
+    if (fill_bg) {
+        rc = gh_fill_fb_bigram_table(ctx, lat->d_layers, d_bg);
+        if (rc) return rc;
+    } else if (bigram) d_bg = &lat->d_bigram_wide->bg[0][0];
     for (size_t c = 0; c + 1 < chunk_begin.size(); ++c) {
-        rc = gh_launch_fb_loop(ctx, a, f, chunk_begin[c], chunk_begin[c + 1] - chunk_begin[c], b->dtype == GH_F64);
+        const int64_t n = chunk_begin[c + 1] - chunk_begin[c];
+        rc = bigram ? gh_launch_fb_bigram(ctx, a, f, d_bg, chunk_begin[c], n, b->dtype == GH_F64)
+                    : gh_launch_fb_loop(ctx, a, f, chunk_begin[c], n, b->dtype == GH_F64);
         if (rc) return rc;
     }
     if (out_logp) GH_HIP(hipMemcpyAsync(out_logp, d_logp, U * 8, hipMemcpyDeviceToHost, st));

@@ -117,6 +117,13 @@ struct gh_fbloop_args {
     double* conf;                // optional, laid out like labels
 };
 int gh_launch_fb_loop(gh_ctx* ctx, const gh_fbloop_args& a, const gh_layerform& f, int64_t u_begin, int64_t n_utts, bool f64);
+// bigram form (gh_layerform with loop == 2, narrow or wide): the same argument block and the same results on fb_bigram_kernel
+// (gh_fb_bigram.hip: four utterances per block, lane = word).  d_bg: ONE [GH_LAYERS_MAXW][GH_LAYERS_MAXW] table of
+// word-to-word costs on the device, +inf behind the words -- gh_bigram_wide::bg as it is, or what gh_fill_fb_bigram_table
+// spreads out from the 16 x 16 of gh_layerform::bg (gh_word_posteriors_bigram)
+int gh_fill_fb_bigram_table(gh_ctx* ctx, const gh_layerform* d_lf, double* d_bg);
+int gh_launch_fb_bigram(gh_ctx* ctx, const gh_fbloop_args& a, const gh_layerform& f, const double* d_bg, int64_t u_begin, int64_t n_utts,
+                        bool f64);
 
 int gh_fb_seq_by_cell(const gh_fbseq_args& a, int N);
 int gh_launch_fb_seq(gh_ctx* ctx, const gh_fbseq_args& a, int N, int skip, int64_t u_begin, int64_t n_utts, bool f64);

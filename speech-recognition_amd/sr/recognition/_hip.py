@@ -125,6 +125,8 @@ SIGNATURES = {
                                       _c_f64p, _c_i64p, _c_f64p, _c_f64p]),
     "gh_word_posteriors": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, _c_f64p, _c_f64p, _c_i32p, _c_i32p, _c_i64p, _c_i32p,
                                      _c_f64p]),
+    "gh_word_posteriors_bigram": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, _c_f64p, _c_f64p, _c_i32p, _c_i32p, _c_i64p,
+                                            _c_i32p, _c_f64p]),
     "gh_bw_accumulate": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, _c_f64p, C.c_void_p]),
     "gh_em_accumulate": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int, _c_f64p, _c_f64p,
                                    _c_f64p, _c_f64p, _c_f64p]),
@@ -1490,10 +1492,30 @@ class Lattices:
         frames (`viterbi_labels(..., want_begin=True)`); the confidence of a word is the mean of its q over its frames.
         Without them `confidence` is left out; want_post=False: no [N, W] copy-back.  Any other graph form, words of 12 or
         16 states and a rank beam raise `Unsupported`."""
+        return self._word_posteriors("gh_word_posteriors", self._loop_words(), "loop", batch, labels, begins, want_post)
+
+    def _bigram_words(self):
+        """Words of graph 0 when it has the rows of the bigram form (start row, states 1 .. n-1 of every word, one entry row
+        per word, one first state per word), else None -- as `_loop_words`, this only sizes the posteriorgram."""
+        rs = getattr(self, "_row_state0", None)
+        if rs is None:
+            return None
+        nes = np.flatnonzero(rs < 0)
+        W = len(nes) - 1
+        if W < 2 or nes[0] != 0 or nes[-1] - nes[1] != W - 1 or len(rs) - 1 - nes[-1] != W:
+            return None
+        return int(W)
+
+    def word_posteriors_bigram(self, batch, labels=None, begins=None, want_post=True):
+        """`word_posteriors` for a graph in bigram form (gh_word_posteriors_bigram): the same dict -- logp [U], post [N, W],
+        confidence -- for a decode under word-to-word costs, 2 to 64 words of 2 to 8 states.  A loop-form graph (it goes to
+        `word_posteriors`), any other graph form, words of 12 or 16 states and a rank beam raise `Unsupported`."""
+        return self._word_posteriors("gh_word_posteriors_bigram", self._bigram_words(), "bigram", batch, labels, begins, want_post)
+
+    def _word_posteriors(self, entry, W, form, batch, labels, begins, want_post):
         lib, U = self.ctx.lib, batch.U
         if (labels is None) != (begins is None):
             raise ValueError("labels and begins come together")
-        W = self._loop_words()
         logp = np.empty(U)
         post = np.empty((batch.N, W)) if (want_post and W is not None) else None
         lab = beg = off = nl = conf = None
@@ -1508,14 +1530,14 @@ class Lattices:
                                                    if U else np.zeros(0, np.int32), dtype=np.int32)
             lab, beg = flat(labels), flat(begins)
             conf = np.zeros(int(off[-1]))
-        rc = lib.gh_word_posteriors(self.ctx.h, self.h, batch.h, _ptr(logp, _c_f64p) if W is not None else None,
-                                    _ptr(post, _c_f64p), _ptr(lab, _c_i32p), _ptr(beg, _c_i32p), _ptr(off, _c_i64p),
-                                    _ptr(nl, _c_i32p), _ptr(conf, _c_f64p))
+        rc = getattr(lib, entry)(self.ctx.h, self.h, batch.h, _ptr(logp, _c_f64p) if W is not None else None,
+                                 _ptr(post, _c_f64p), _ptr(lab, _c_i32p), _ptr(beg, _c_i32p), _ptr(off, _c_i64p),
+                                 _ptr(nl, _c_i32p), _ptr(conf, _c_f64p))
         if rc == GH_ERR_UNSUPPORTED:
             raise Unsupported(lib.gh_last_error().decode("utf-8", "replace"))
         _check(lib, rc)
         if W is None:
-            raise BackendError("word_posteriors: the library took a graph whose rows are not those of the loop form")
+            raise BackendError("%s: the library took a graph whose rows are not those of the %s form" % (entry, form))
         out = dict(logp=logp)
         if post is not None:
             out["post"] = post

@@ -494,13 +494,15 @@ class ContinuousDecoder:
         else:
             raise ValueError("grammar must be 'layers', 'loop' or 'bigram', not %r" % (grammar,))
         self.grammar = grammar
+        self.n_words = W
         self.row_state = graph["row_state"]
         self.lat = _hip.Lattices(self.ctx, [graph])
 
-    def _posteriors_refusal(self):
+    def _posteriors_refusal(self, lm=False):
         """Why this decoder has no word posteriors (None: it has).  Decided from what the decoder was built with, before the
-        GPU is touched; the library refuses the same cases on its own."""
-        if self.grammar == "bigram":
+        GPU is touched; the library refuses the same cases on its own.  lm=True permits the bigram grammar
+        (gh_word_posteriors_bigram); without it a bigram decoder is refused as it always was."""
+        if self.grammar == "bigram" and not lm:
             return ("word posteriors and confidences are built for the word-loop grammar (grammar='loop'); the bigram grammar "
                     "(one entry row per word) is not built")
         if self.grammar == "layers":
@@ -513,19 +515,29 @@ class ContinuousDecoder:
             return "word posteriors are built for words of 2 to 8 states, not %d" % self.n
         return None
 
-    def word_posteriors(self, batch):
+    def _posteriors_call(self, lm):
+        """The backend method that computes this decoder's word posteriors: `word_posteriors_bigram` for a permitted bigram
+        decoder, `word_posteriors` otherwise.  A one-word bigram grammar has the rows of the loop form; it goes by the form
+        the library reports for its handle."""
+        if self.grammar == "bigram" and lm and not (self.n_words == 1 and "loop" in self.lat.forms()):
+            return self.lat.word_posteriors_bigram
+        return self.lat.word_posteriors
+
+    def word_posteriors(self, batch, lm=False):
         """(post, logp): the word posteriorgram post [N, W] of the batch (row = frame in batch order, post[t, w] = the posterior
         that frame t belongs to word w -- a boundary frame belongs to the entering word, as in the begin times -- every row
         of an utterance with a path sums to 1) and log P [U] per utterance, from one forward-backward over the loop grammar
-        (gh_word_posteriors).  grammar="loop" with words of 2 to 8 states and no beam; anything else raises `_hip.Unsupported`."""
-        why = self._posteriors_refusal()
+        (gh_word_posteriors).  grammar="loop" with words of 2 to 8 states and no beam; anything else raises `_hip.Unsupported`.
+        lm=True is a permission, not a demand: a grammar="bigram" decoder (2 to 8 states, no beam) then answers too, from the
+        forward-backward over the bigram grammar (gh_word_posteriors_bigram); nothing else changes."""
+        why = self._posteriors_refusal(lm)
         if why:
             raise _hip.Unsupported(why)
         batch.loglik(self.gmm, fetch=False)
-        r = self.lat.word_posteriors(batch)
+        r = self._posteriors_call(lm)(batch)
         return r["post"], r["logp"]
 
-    def decode_batch(self, batch, want_path=False, want_times=False, want_confidence=False):
+    def decode_batch(self, batch, want_path=False, want_times=False, want_confidence=False, lm=False):
         """Word-index lists of every utterance (+ the raw result dict).  By default the paths stay on the device
         and only the decoded word sequences come back (gh_viterbi_labels); want_path=True also returns the
         reference-style (row, column) paths in `r["paths"]` and derives the words from them on the host.
@@ -536,15 +548,17 @@ class ContinuousDecoder:
         want_times=True, then one gh_word_posteriors call on the same likelihoods: `r["confidence"]` holds one float64 array
         per utterance, aligned with its words -- the mean over the word's frames of the posterior that the frame belongs to
         that word, in [0, 1] -- with `r["begins"]` and `r["logp"]` (log P per utterance).  Words, begins, end costs and
-        chosen ends are those of want_times=True bit for bit."""
+        chosen ends are those of want_times=True bit for bit.
+        lm=True (with want_confidence=True; a permission, ignored otherwise): a grammar="bigram" decoder of 2 to 8 states
+        without a beam is not refused -- the same decode, then one gh_word_posteriors_bigram call."""
         if want_confidence:
-            why = self._posteriors_refusal()
+            why = self._posteriors_refusal(lm)
             if why:
                 raise _hip.Unsupported(why)
             if want_path:
                 raise ValueError("want_confidence goes with the label decode, not with want_path")
             words, r = self.decode_batch(batch, want_times=True)
-            wp = self.lat.word_posteriors(batch, labels=r["labels"], begins=r["begins"], want_post=False)
+            wp = self._posteriors_call(lm)(batch, labels=r["labels"], begins=r["begins"], want_post=False)
             r["confidence"], r["logp"] = wp["confidence"], wp["logp"]
             return words, r
         batch.loglik(self.gmm, fetch=False)
@@ -562,18 +576,18 @@ class ContinuousDecoder:
             r = self.lat.viterbi_labels(batch, row_word, max_labels=self._max_labels(batch.lengths))
         return [[int(w) for w in l] for l in r["labels"]], r
 
-    def decode(self, xs, want_times=False, want_confidence=False):
+    def decode(self, xs, want_times=False, want_confidence=False, lm=False):
         """xs: list of [T_u, D] arrays -> list of word-index lists; want_times=True: (words, begins), begins one int32
         array per utterance (see `decode_batch`); want_confidence=True: (words, begins, confidence), confidence one
-        float64 array per utterance."""
+        float64 array per utterance; lm=True permits that for a grammar="bigram" decoder (see `decode_batch`)."""
         if want_confidence:
-            why = self._posteriors_refusal()
+            why = self._posteriors_refusal(lm)
             if why:
                 raise _hip.Unsupported(why)
         batch = _hip.Batch(self.ctx, xs, dtype=self.dtype)
         try:
             if want_confidence:
-                words, r = self.decode_batch(batch, want_confidence=True)
+                words, r = self.decode_batch(batch, want_confidence=True, lm=lm)
                 return words, r["begins"], r["confidence"]
             if want_times:
                 words, r = self.decode_batch(batch, want_times=True)
