@@ -55,10 +55,11 @@ __global__ __launch_bounds__(1024) void dtw_kernel(gh_dtw_args a) {
     // reads LDS.  (Reading template row and frame element by element from global memory inside the loop cost one
     // memory round trip per dimension: 16 k cycles per column for D = 39.)
     double* xs0 = reinterpret_cast<double*>(mark0 + 2 * np + ((8 - (2 * np) % 8) % 8));   // [2][D] frames, 8-byte aligned
-    double* ys = xs0 + 2 * D;                                 // [n][D] template rows (a.tpl_lds)
-    double* vs = ys + (STAGED ? n * D : 0);                   // [n][D] variances
-    double* ts = vs + ((STAGED && a.var) ? n * D : 0);        // [n][n] arc costs
     const bool own_dist = a.E == nullptr;
+    // (the layout gh_launch_dtw sized: a caller's distance matrix brings no template rows, the arcs follow the frames)
+    double* ys = xs0 + 2 * D;                                 // [n][D] template rows (a.tpl_lds)
+    double* vs = ys + ((STAGED && own_dist) ? n * D : 0);     // [n][D] variances
+    double* ts = vs + ((STAGED && own_dist && a.var) ? n * D : 0);   // [n][n] arc costs
     if (STAGED) {
         for (int k = i; k < n * n; k += np) ts[k] = m_trans[k];
         if (own_dist) for (int k = i; k < n * D; k += np) { ys[k] = m_y[k]; if (a.var) vs[k] = m_var[k]; }
