@@ -553,6 +553,34 @@ int gh_word_posteriors_bigram(gh_ctx* ctx, const gh_lattices* lat, gh_batch* b,
                               const int32_t* n_labels /*[U]*/,        /* all four NULL: no confidences */
                               double* out_conf /*laid out like labels, or NULL*/);
 
+/* ------------------------- word posteriors and per-word confidence (K-layer lattice)
+ * NOT in the reference, like gh_word_posteriors; pinned by brute-force path enumeration in the tests.
+ * The same results for a handle whose graph 0 is a K-LAYER LATTICE in the narrow layer form (the reference's continuous
+ * recogniser, main.py:35: the same W words of n states in each of K layers, 1 <= K <= 8, 1 <= W <= 16, 2 <= n <= 8).  One
+ * wave per utterance, lane = (layer mod 4, word), one or two register sets of layers per lane.
+ * DEFINITION.  In the notation above, with NES_k the non-emitting row in front of layer k (NES_0 = row 0; NES_K follows the
+ * last layer and has no successor) and last_{k,w} the last state of word w in layer k: a path's WORD AT FRAME t is the word
+ * of the LAST emitting cell it visits in column t (the boundary frame belongs to the entering word), and
+ *     q_t(k, w) = sum_s gamma_t(k, w, s)  -  exp( la[last_{k,w}, t] - trans[NES_{k+1}, last_{k,w}] + lb[NES_{k+1}, t] - logP )
+ *     q_t(w)    = sum over k = 0 .. K-1 of q_t(k, w)
+ * (the subtracted term: leaving word w of layer k through the next non-emitting row in column t; it is 0 for the last
+ * layer, lb[NES_K] = -inf).  The sum over layers runs in one fixed order, ((k = 0, 4) + (1, 5)) + ((2, 6) + (3, 7)), written
+ * down in csrc/gh_fb_layers.hip.  Rows sum to 1, 0 <= q <= 1, a q_t(k, w) below 0 by rounding counts as 0; log P = -inf (no
+ * path: fewer than K (n-1) + 1 frames without skip arcs) gives zero rows and confidences of 0.0.  out_post is [N, W], summed
+ * over the layers like the other two grammars'; on a word loop with word_penalty = 0,
+ * q_loop_t(w) = sum_K exp(logP_K - logP_loop) q^K_t(w) and logP_loop = LSE_K logP_K.
+ * Arguments, span table and confidences exactly as for gh_word_posteriors; a label is a word, 0 <= label < W.  Alpha
+ * scratch: 8 T K n W bytes per utterance, cut into launches by the scratch budget, longest first (gh_ctx_last_chunks);
+ * U == 0: GH_OK, 0 launches.
+ * Everything is checked before anything is enqueued.  GH_ERR_UNSUPPORTED, with a sentence per case: a loop-form handle, a
+ * bigram or wide bigram handle, the wide layer form (17 to 64 words), more than 8 layers, words of 12 or 16 states,
+ * transcript graphs, a generic graph, a rank beam on the handle.  GH_ERR_INVALID: as for gh_word_posteriors. */
+int gh_word_posteriors_layers(gh_ctx* ctx, const gh_lattices* lat, gh_batch* b,
+                              double* out_logp /*[U] or NULL*/, double* out_post /*[N, W] or NULL*/,
+                              const int32_t* labels, const int32_t* begins, const int64_t* label_off /*[U+1]*/,
+                              const int32_t* n_labels /*[U]*/,        /* all four NULL: no confidences */
+                              double* out_conf /*laid out like labels, or NULL*/);
+
 /* ------------------------------------ Baum-Welch (soft) sufficient statistics
  * After gh_forward_backward(want_occ = 1): for every frame n and state s,
  *   r_nsm = occ[n,s] * w_sm pdf_sm(x_n) / sum_m' w_sm' pdf_sm'(x_n)

@@ -35,6 +35,8 @@ EXTRA = {"gh_loglik_mfma.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"],
          "gh_fb_loop.hip": ["-ffp-contract=off"],
          # ... and its bigram-form twin
          "gh_fb_bigram.hip": ["-ffp-contract=off"],
+         # ... and its layer-form twin
+         "gh_fb_layers.hip": ["-ffp-contract=off"],
          # ... and so does the forward sweep of the word chains
          "gh_forward_chain.hip": ["-ffp-contract=off"]}
 

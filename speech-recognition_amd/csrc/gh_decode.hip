@@ -1003,7 +1003,8 @@ extern "C" int gh_forward_backward(gh_ctx* ctx, const gh_lattices* lat, gh_batch
 }
 
 // ------------------------------------------- word posteriors (loop form)
-static int word_posteriors_run(const char* who, bool bigram, gh_ctx* ctx, const gh_lattices* lat, gh_batch* b, double* out_logp,
+enum { GH_WP_LOOP = 0, GH_WP_BIGRAM = 1, GH_WP_LAYERS = 2 };   // the form word_posteriors_run sweeps
+static int word_posteriors_run(const char* who, int form, gh_ctx* ctx, const gh_lattices* lat, gh_batch* b, double* out_logp,
                                double* out_post, const int32_t* labels, const int32_t* begins, const int64_t* label_off,
                                const int32_t* n_labels, double* out_conf);
 
@@ -1029,7 +1030,7 @@ extern "C" int gh_word_posteriors(gh_ctx* ctx, const gh_lattices* lat, gh_batch*
         gh_set_error("gh_word_posteriors: a rank beam (%d) is set on the handle: posteriors are sums over all paths, not over a pruned decode", lat->beam);
         return GH_ERR_UNSUPPORTED;
     }
-    return word_posteriors_run("gh_word_posteriors", false, ctx, lat, b, out_logp, out_post, labels, begins, label_off, n_labels, out_conf);
+    return word_posteriors_run("gh_word_posteriors", GH_WP_LOOP, ctx, lat, b, out_logp, out_post, labels, begins, label_off, n_labels, out_conf);
 }
 
 // ------------------------------------------- word posteriors (bigram form, narrow and wide)
@@ -1054,12 +1055,46 @@ extern "C" int gh_word_posteriors_bigram(gh_ctx* ctx, const gh_lattices* lat, gh
         return GH_ERR_UNSUPPORTED;
     }
     GH_REQUIRE(lat->bigram_ok || lat->d_bigram_wide, "gh_word_posteriors_bigram: internal: wide bigram form without its cost table");
-    return word_posteriors_run("gh_word_posteriors_bigram", true, ctx, lat, b, out_logp, out_post, labels, begins, label_off, n_labels, out_conf);
+    return word_posteriors_run("gh_word_posteriors_bigram", GH_WP_BIGRAM, ctx, lat, b, out_logp, out_post, labels, begins, label_off, n_labels, out_conf);
 }
 
-// What the two entry points share once the handle's form is settled: the checks of the batch and of the span table
+// ------------------------------------------- word posteriors (K-layer lattice, narrow layer form)
+extern "C" int gh_word_posteriors_layers(gh_ctx* ctx, const gh_lattices* lat, gh_batch* b, double* out_logp, double* out_post,
+                                         const int32_t* labels, const int32_t* begins, const int64_t* label_off, const int32_t* n_labels,
+                                         double* out_conf) {
+    GH_REQUIRE(ctx && lat && b, "gh_word_posteriors_layers: NULL argument");
+    // what the handle is, before anything else: every refusal has a sentence of its own
+    if (!(lat->layers_ok && lat->h_layers.loop == 0)) {
+        if (lat->layers_ok) gh_set_error("gh_word_posteriors_layers: the graph is in loop form (one loop row): gh_word_posteriors takes it");
+        else if (lat->bigram_wide_ok) gh_set_error("gh_word_posteriors_layers: the graph is in wide bigram form: gh_word_posteriors_bigram takes it");
+        else if (lat->bigram_ok) gh_set_error("gh_word_posteriors_layers: the graph is in bigram form: gh_word_posteriors_bigram takes it");
+        else if (lat->seq_ok || lat->deferred_src) gh_set_error("gh_word_posteriors_layers: the handle holds transcript graphs (sequence form): word posteriors are built for the loop, the bigram and the layer form only");
+        else gh_set_error("gh_word_posteriors_layers: graph 0 is not in layer form (generic graph): word posteriors are built for the loop, the bigram and the layer form only");
+        return GH_ERR_UNSUPPORTED;
+    }
+    const gh_layerform& f = lat->h_layers;
+    if (f.W > GH_LAYERS_ROWW) {
+        gh_set_error("gh_word_posteriors_layers: %d words per layer (the wide layer form): the layer-form forward-backward is built for 1 .. %d words", f.W, GH_LAYERS_ROWW);
+        return GH_ERR_UNSUPPORTED;
+    }
+    if (f.K > 8) {
+        gh_set_error("gh_word_posteriors_layers: %d layers: the layer-form forward-backward is built for 1 .. 8 layers", f.K);
+        return GH_ERR_UNSUPPORTED;
+    }
+    if (f.N > 8) {
+        gh_set_error("gh_word_posteriors_layers: words of %d states: the layer-form forward-backward is built for 2 .. 8 states per word", f.N);
+        return GH_ERR_UNSUPPORTED;
+    }
+    if (lat->beam) {
+        gh_set_error("gh_word_posteriors_layers: a rank beam (%d) is set on the handle: posteriors are sums over all paths, not over a pruned decode", lat->beam);
+        return GH_ERR_UNSUPPORTED;
+    }
+    return word_posteriors_run("gh_word_posteriors_layers", GH_WP_LAYERS, ctx, lat, b, out_logp, out_post, labels, begins, label_off, n_labels, out_conf);
+}
+
+// What the three entry points share once the handle's form is settled: the checks of the batch and of the span table
 // (everything before anything is enqueued), alpha scratch cut into launches, the sweep, the copies back.
-static int word_posteriors_run(const char* who, bool bigram, gh_ctx* ctx, const gh_lattices* lat, gh_batch* b, double* out_logp,
+static int word_posteriors_run(const char* who, int form, gh_ctx* ctx, const gh_lattices* lat, gh_batch* b, double* out_logp,
                                double* out_post, const int32_t* labels, const int32_t* begins, const int64_t* label_off,
                                const int32_t* n_labels, double* out_conf) {
     const gh_layerform& f = lat->h_layers;
@@ -1090,13 +1125,15 @@ static int word_posteriors_run(const char* who, bool bigram, gh_ctx* ctx, const 
         }
     }
     GH_HIP(hipSetDevice(ctx->device));
-    // alpha scratch [T, N, W] doubles per utterance, chunked (<= gh_scratch_budget() bytes per launch), longest first
+    const bool bigram = form == GH_WP_BIGRAM;
+    const size_t cells = (size_t)N * W * (form == GH_WP_LAYERS ? f.K : 1);
+    // alpha scratch [T, N, W] (layer form: [T, K, N, W]) doubles per utterance, chunked (<= gh_scratch_budget() bytes per launch), longest first
     const size_t BUDGET = gh_scratch_budget(ctx);
     std::vector<int64_t> soff(U, 0), chunk_begin{0};
     size_t acc = 0, smax = 0;
     for (int64_t k = 0; k < U; ++k) {
         const int64_t u = b->perm[k];
-        const size_t need = (size_t)(b->offsets[u + 1] - b->offsets[u]) * N * W;
+        const size_t need = (size_t)(b->offsets[u + 1] - b->offsets[u]) * cells;
         if (acc && (acc + need) * 8 > BUDGET) { chunk_begin.push_back(k); smax = std::max(smax, acc); acc = 0; }
         soff[k] = (int64_t)acc;
         acc += need;
@@ -1146,7 +1183,8 @@ static int word_posteriors_run(const char* who, bool bigram, gh_ctx* ctx, const 
     for (size_t c = 0; c + 1 < chunk_begin.size(); ++c) {
         const int64_t n = chunk_begin[c + 1] - chunk_begin[c];
         rc = bigram ? gh_launch_fb_bigram(ctx, a, f, d_bg, chunk_begin[c], n, b->dtype == GH_F64)
-                    : gh_launch_fb_loop(ctx, a, f, chunk_begin[c], n, b->dtype == GH_F64);
+             : form == GH_WP_LAYERS ? gh_launch_fb_layers(ctx, a, f, chunk_begin[c], n, b->dtype == GH_F64)
+                                    : gh_launch_fb_loop(ctx, a, f, chunk_begin[c], n, b->dtype == GH_F64);
         if (rc) return rc;
     }
     if (out_logp) GH_HIP(hipMemcpyAsync(out_logp, d_logp, U * 8, hipMemcpyDeviceToHost, st));

@@ -124,6 +124,10 @@ int gh_launch_fb_loop(gh_ctx* ctx, const gh_fbloop_args& a, const gh_layerform& 
 int gh_fill_fb_bigram_table(gh_ctx* ctx, const gh_layerform* d_lf, double* d_bg);
 int gh_launch_fb_bigram(gh_ctx* ctx, const gh_fbloop_args& a, const gh_layerform& f, const double* d_bg, int64_t u_begin, int64_t n_utts,
                         bool f64);
+// narrow layer form (gh_layerform with loop == 0, up to GH_LAYERS_ROWW words, up to 8 layers of 2 .. 8 states): the same
+// argument block and the same results on fb_layers_kernel (gh_fb_layers.hip: one utterance per wave, lane = (layer mod 4,
+// word)); alpha_scratch is [T, K, N, W] per launch slot (gh_word_posteriors_layers)
+int gh_launch_fb_layers(gh_ctx* ctx, const gh_fbloop_args& a, const gh_layerform& f, int64_t u_begin, int64_t n_utts, bool f64);
 
 int gh_fb_seq_by_cell(const gh_fbseq_args& a, int N);
 int gh_launch_fb_seq(gh_ctx* ctx, const gh_fbseq_args& a, int N, int skip, int64_t u_begin, int64_t n_utts, bool f64);

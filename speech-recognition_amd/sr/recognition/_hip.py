@@ -127,6 +127,8 @@ SIGNATURES = {
                                      _c_f64p]),
     "gh_word_posteriors_bigram": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, _c_f64p, _c_f64p, _c_i32p, _c_i32p, _c_i64p,
                                             _c_i32p, _c_f64p]),
+    "gh_word_posteriors_layers": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, _c_f64p, _c_f64p, _c_i32p, _c_i32p, _c_i64p,
+                                            _c_i32p, _c_f64p]),
     "gh_bw_accumulate": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, _c_f64p, C.c_void_p]),
     "gh_em_accumulate": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int, _c_f64p, _c_f64p,
                                    _c_f64p, _c_f64p, _c_f64p]),
@@ -1193,6 +1195,7 @@ class Lattices:
         start_rows, end_rows = cat("start_rows", np.int32), cat("end_rows", np.int32)
         self.end_rows = [np.asarray(g["end_rows"], dtype=np.int64) for g in graphs]
         self._row_state0 = np.asarray(graphs[0]["row_state"], dtype=np.int64).ravel() if L else None
+        self._row0_fanout = int(np.count_nonzero(np.asarray(graphs[0]["arc_from"]).ravel() == 0)) if L else 0
         h = C.c_void_p()
         _check(ctx.lib, ctx.lib.gh_lattices_create(
             ctx.h, L, _ptr(self.row_off, _c_i64p), _ptr(row_state, _c_i32p), _ptr(self.arc_off, _c_i64p),
@@ -1511,6 +1514,30 @@ class Lattices:
         confidence -- for a decode under word-to-word costs, 2 to 64 words of 2 to 8 states.  A loop-form graph (it goes to
         `word_posteriors`), any other graph form, words of 12 or 16 states and a rank beam raise `Unsupported`."""
         return self._word_posteriors("gh_word_posteriors_bigram", self._bigram_words(), "bigram", batch, labels, begins, want_post)
+
+    def _layers_words(self):
+        """Words per layer of graph 0 when it has the rows of a K-layer lattice (start row, then K times P emitting rows
+        and one non-emitting row), else None.  The rows give K and P = W n; the layer is cut into words where the start row
+        feeds it, as the library does, so W is the number of arcs that leave row 0.  As `_loop_words`, this only sizes the
+        posteriorgram."""
+        rs = getattr(self, "_row_state0", None)
+        if rs is None:
+            return None
+        nes = np.flatnonzero(rs < 0)
+        K, W = len(nes) - 1, getattr(self, "_row0_fanout", 0)
+        if K < 1 or nes[0] != 0 or nes[-1] != len(rs) - 1:
+            return None
+        P = int(nes[1]) - 1
+        if P < 1 or np.any(np.diff(nes) != P + 1) or W < 1 or P % W:
+            return None
+        return int(W)
+
+    def word_posteriors_layers(self, batch, labels=None, begins=None, want_post=True):
+        """`word_posteriors` for a K-layer lattice in the narrow layer form (gh_word_posteriors_layers): the same dict -- logp
+        [U], post [N, W] summed over the layers, confidence -- for 1 to 8 layers of 1 to 16 words of 2 to 8 states.  A loop
+        or bigram graph, any other graph form, 17 to 64 words, more than 8 layers, words of 12 or 16 states and a rank beam
+        raise `Unsupported`."""
+        return self._word_posteriors("gh_word_posteriors_layers", self._layers_words(), "layer", batch, labels, begins, want_post)
 
     def _word_posteriors(self, entry, W, form, batch, labels, begins, want_post):
         lib, U = self.ctx.lib, batch.U

@@ -495,19 +495,26 @@ class ContinuousDecoder:
             raise ValueError("grammar must be 'layers', 'loop' or 'bigram', not %r" % (grammar,))
         self.grammar = grammar
         self.n_words = W
+        self.n_layers = n_layers if grammar == "layers" else None
         self.row_state = graph["row_state"]
         self.lat = _hip.Lattices(self.ctx, [graph])
 
-    def _posteriors_refusal(self, lm=False):
+    def _posteriors_refusal(self, lm=False, layers=False):
         """Why this decoder has no word posteriors (None: it has).  Decided from what the decoder was built with, before the
         GPU is touched; the library refuses the same cases on its own.  lm=True permits the bigram grammar
-        (gh_word_posteriors_bigram); without it a bigram decoder is refused as it always was."""
+        (gh_word_posteriors_bigram), layers=True the K-layer lattice (gh_word_posteriors_layers: 1 to 8 layers of up to 16
+        words); without its keyword either decoder is refused as it always was."""
         if self.grammar == "bigram" and not lm:
             return ("word posteriors and confidences are built for the word-loop grammar (grammar='loop'); the bigram grammar "
                     "(one entry row per word) is not built")
-        if self.grammar == "layers":
+        if self.grammar == "layers" and not layers:
             return ("word posteriors and confidences are built for the word-loop grammar (grammar='loop'); the K-layer lattice "
-                    "is not built")
+                    "is not built without layers=True")
+        if self.grammar == "layers" and self.n_words > 16:
+            return ("word posteriors on the K-layer lattice are built for up to 16 words per layer, not %d (the wide layer form)"
+                    % self.n_words)
+        if self.grammar == "layers" and self.n_layers > 8:
+            return "word posteriors on the K-layer lattice are built for up to 8 layers, not %d" % self.n_layers
         if getattr(self.lat, "beam", 0):
             return ("word posteriors are sums over all paths: a decoder with a rank beam (set_beam(%d)) has none"
                     % self.lat.beam)
@@ -515,29 +522,33 @@ class ContinuousDecoder:
             return "word posteriors are built for words of 2 to 8 states, not %d" % self.n
         return None
 
-    def _posteriors_call(self, lm):
+    def _posteriors_call(self, lm, layers=False):
         """The backend method that computes this decoder's word posteriors: `word_posteriors_bigram` for a permitted bigram
-        decoder, `word_posteriors` otherwise.  A one-word bigram grammar has the rows of the loop form; it goes by the form
-        the library reports for its handle."""
+        decoder, `word_posteriors_layers` for a permitted layers decoder, `word_posteriors` otherwise.  A one-word bigram
+        grammar has the rows of the loop form; it goes by the form the library reports for its handle."""
+        if self.grammar == "layers" and layers:
+            return self.lat.word_posteriors_layers
         if self.grammar == "bigram" and lm and not (self.n_words == 1 and "loop" in self.lat.forms()):
             return self.lat.word_posteriors_bigram
         return self.lat.word_posteriors
 
-    def word_posteriors(self, batch, lm=False):
+    def word_posteriors(self, batch, lm=False, layers=False):
         """(post, logp): the word posteriorgram post [N, W] of the batch (row = frame in batch order, post[t, w] = the posterior
         that frame t belongs to word w -- a boundary frame belongs to the entering word, as in the begin times -- every row
         of an utterance with a path sums to 1) and log P [U] per utterance, from one forward-backward over the loop grammar
         (gh_word_posteriors).  grammar="loop" with words of 2 to 8 states and no beam; anything else raises `_hip.Unsupported`.
         lm=True is a permission, not a demand: a grammar="bigram" decoder (2 to 8 states, no beam) then answers too, from the
-        forward-backward over the bigram grammar (gh_word_posteriors_bigram); nothing else changes."""
-        why = self._posteriors_refusal(lm)
+        forward-backward over the bigram grammar (gh_word_posteriors_bigram); nothing else changes.
+        layers=True is the same kind of permission for a grammar="layers" decoder of 1 to 8 layers of up to 16 words (2 to 8
+        states, no beam): post is summed over the layers (gh_word_posteriors_layers).  Loop and bigram decoders ignore it."""
+        why = self._posteriors_refusal(lm, layers)
         if why:
             raise _hip.Unsupported(why)
         batch.loglik(self.gmm, fetch=False)
-        r = self._posteriors_call(lm)(batch)
+        r = self._posteriors_call(lm, layers)(batch)
         return r["post"], r["logp"]
 
-    def decode_batch(self, batch, want_path=False, want_times=False, want_confidence=False, lm=False):
+    def decode_batch(self, batch, want_path=False, want_times=False, want_confidence=False, lm=False, layers=False):
         """Word-index lists of every utterance (+ the raw result dict).  By default the paths stay on the device
         and only the decoded word sequences come back (gh_viterbi_labels); want_path=True also returns the
         reference-style (row, column) paths in `r["paths"]` and derives the words from them on the host.
@@ -550,15 +561,17 @@ class ContinuousDecoder:
         that word, in [0, 1] -- with `r["begins"]` and `r["logp"]` (log P per utterance).  Words, begins, end costs and
         chosen ends are those of want_times=True bit for bit.
         lm=True (with want_confidence=True; a permission, ignored otherwise): a grammar="bigram" decoder of 2 to 8 states
-        without a beam is not refused -- the same decode, then one gh_word_posteriors_bigram call."""
+        without a beam is not refused -- the same decode, then one gh_word_posteriors_bigram call.
+        layers=True (likewise a permission): a grammar="layers" decoder of 1 to 8 layers of up to 16 words of 2 to 8 states
+        without a beam is not refused -- the same decode, then one gh_word_posteriors_layers call."""
         if want_confidence:
-            why = self._posteriors_refusal(lm)
+            why = self._posteriors_refusal(lm, layers)
             if why:
                 raise _hip.Unsupported(why)
             if want_path:
                 raise ValueError("want_confidence goes with the label decode, not with want_path")
             words, r = self.decode_batch(batch, want_times=True)
-            wp = self._posteriors_call(lm)(batch, labels=r["labels"], begins=r["begins"], want_post=False)
+            wp = self._posteriors_call(lm, layers)(batch, labels=r["labels"], begins=r["begins"], want_post=False)
             r["confidence"], r["logp"] = wp["confidence"], wp["logp"]
             return words, r
         batch.loglik(self.gmm, fetch=False)
@@ -576,18 +589,19 @@ class ContinuousDecoder:
             r = self.lat.viterbi_labels(batch, row_word, max_labels=self._max_labels(batch.lengths))
         return [[int(w) for w in l] for l in r["labels"]], r
 
-    def decode(self, xs, want_times=False, want_confidence=False, lm=False):
+    def decode(self, xs, want_times=False, want_confidence=False, lm=False, layers=False):
         """xs: list of [T_u, D] arrays -> list of word-index lists; want_times=True: (words, begins), begins one int32
         array per utterance (see `decode_batch`); want_confidence=True: (words, begins, confidence), confidence one
-        float64 array per utterance; lm=True permits that for a grammar="bigram" decoder (see `decode_batch`)."""
+        float64 array per utterance; lm=True permits that for a grammar="bigram" decoder, layers=True for a
+        grammar="layers" decoder (see `decode_batch`)."""
         if want_confidence:
-            why = self._posteriors_refusal(lm)
+            why = self._posteriors_refusal(lm, layers)
             if why:
                 raise _hip.Unsupported(why)
         batch = _hip.Batch(self.ctx, xs, dtype=self.dtype)
         try:
             if want_confidence:
-                words, r = self.decode_batch(batch, want_confidence=True, lm=lm)
+                words, r = self.decode_batch(batch, want_confidence=True, lm=lm, layers=layers)
                 return words, r["begins"], r["confidence"]
             if want_times:
                 words, r = self.decode_batch(batch, want_times=True)
